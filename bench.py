@@ -227,6 +227,10 @@ def parse():
                          "belongs to the timed workload, so a rocprofv3 --stats summary of this command can be compared with "
                          "roofline.avg_launch_ms directly (tools/rocprof_vs_bench.py)")
     ap.add_argument("--layers", type=int, default=24, help="encoder depth (24 = the named models; for debugging only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned -- top_scores.npy (float32) and top_rows.npy "
+                         "(float64), queries x top-n, a few KiB -- into DIR (world > 1: one pair per rank, suffixed _rank<r>); the "
+                         "inputs are seeded, so two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
 
 
@@ -257,6 +261,16 @@ MEASURED_BOUNDS = {
     "f16c": "9.0e-5 relative on the standard fixture (inside 1e-3); 7.2e-3 relative on the stress fixture's smallest scores "
             "(2.2e-3 absolute, ranking intact: Kendall tau 0.998-1.000) -- why it is not the default (same gate log)",
 }
+
+
+def dump_outputs(out_dir, last, rank=None):
+    """--dump-outputs: the last timed step's result as the caller receives it -- (top-n rerank scores, corpus rows), queries x
+    top-n -- as .npy files (rows as float64: exact for any row index below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank is None else f"_rank{rank}"
+    top_s, rows = last
+    np.save(os.path.join(out_dir, f"top_scores{sfx}.npy"), top_s.float().numpy())
+    np.save(os.path.join(out_dir, f"top_rows{sfx}.npy"), rows.to(torch.float64).numpy())
 
 
 def synth_corpus_shard(n_rows, dim, seed, device):
@@ -472,12 +486,14 @@ def main():
     sampler = ClockSampler(local_rank if not os.environ.get("TT_BENCH_ONE_DEVICE") else 0).start()
     t0 = time.perf_counter()
     for q in queries:
-        step(q)
+        last = step(q)
     sync_all()
     dt = time.perf_counter() - t0
     clock = sampler.stop()
     prof = read_prof()
     lib.tt_prof_enable(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank if world > 1 else None)
     # one more, untimed, step with every kernel family instrumented: the per-stage table
     lib.tt_prof_enable(1)
     step(queries[-1])
