@@ -247,6 +247,12 @@ int tt_layernorm_bf16(const void* in, void* out, const float* gamma, const float
 int tt_attention_varlen(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,
                         int ld_out, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads,
                         int head_dim, int max_len, void* stream);
+/* tt_attention_cls_varlen: the CLS-only kernel of the last layer on tt_attention_varlen's operands -- the first row of every
+ * sequence as the only query; out [n_seq][ld_out] (row b = sequence b).  head_dim 32 or 64; a max_len whose score buffer
+ * (max_len + 14 rounded down to 8 floats: up to 7 leading slots of the aligned key frame) exceeds 160 KiB is refused. */
+int tt_attention_cls_varlen(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,
+                            int ld_out, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads,
+                            int head_dim, int max_len, void* stream);
 
 /* fp8 building blocks (same kernels the fp8 forward uses).
  * tt_quantize_rows_fp8: q[r][c] = e4m3(x[r][c] * 448 / absmax_r), scale[r] = absmax_r / 448 (1 for a zero row).
@@ -347,6 +353,9 @@ int tt_layernorm_f16(const void* in, void* out, const float* gamma, const float*
 int tt_attention_varlen_f16(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,
                             int ld_out, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads,
                             int head_dim, int max_len, void* stream);
+int tt_attention_cls_varlen_f16(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,
+                                int ld_out, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads,
+                                int head_dim, int max_len, void* stream);
 
 /* ---- reference precision on the bf16 matrix cores: split-bf16 ("bf16x3") forward -------------------------------------
  * Same contract as the fp32 forward above (the unchanged reference call SentenceTransformerRerank(model=, top_n=, device=),
@@ -415,6 +424,13 @@ int tt_gemm_x3(const void* a_planes, const void* w_planes, const float* bias, co
 int tt_attention_x3(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi,
                     const void* vt_lo, int ldvt, void* out_planes, int ld_out, int out_lo_off,
                     const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len, void* stream);
+/* tt_attention_x3_hd: tt_attention_x3 with head_dim 32 or 64 (scale 1 / sqrt(head_dim)); cls_only = 1 runs the CLS-only
+ * kernel of the last layer instead -- out_planes then holds one row per sequence (row b = sequence b's first query), and a
+ * max_len past its score buffer (as tt_attention_cls_varlen) is refused. */
+int tt_attention_x3_hd(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi,
+                       const void* vt_lo, int ldvt, void* out_planes, int ld_out, int out_lo_off,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len,
+                       int head_dim, int cls_only, void* stream);
 
 /* ---- reference precision on TWO matrix-time units: the "f16c" forward (csrc/f16c_path.hip, round 4) --------------------
  * What the reference's unchanged calls compute -- fp32 semantics (services/model_manager.py:333-337 passes no dtype;
@@ -512,6 +528,10 @@ int tt_gemm_x3_f16(const void* a_planes, const void* w_planes, const float* bias
 int tt_attention_x3_f16(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi,
                         const void* vt_lo, int ldvt, void* out_planes, int ld_out, int out_lo_off,
                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len, void* stream);
+int tt_attention_x3_hd_f16(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi,
+                           const void* vt_lo, int ldvt, void* out_planes, int ld_out, int out_lo_off,
+                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len,
+                           int head_dim, int cls_only, void* stream);
 
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the

@@ -106,11 +106,15 @@ SIGNATURES = {
     "tt_layernorm_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "tt_attention_varlen_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "tt_attention_cls_varlen_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_rerank_head": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_adjacent_cosine": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "tt_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_layernorm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "tt_attention_varlen": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "tt_attention_cls_varlen": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_quantize_rows_fp8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_layernorm_bf16_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p,
@@ -136,6 +140,8 @@ SIGNATURES = {
     "tt_gemm_x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_attention_x3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tt_attention_x3_hd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                   c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     # the split-plane forward with fp16 planes ("f16x3": x3_path.hip's second instantiation)
     "tt_encoder_x3_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
     "tt_encoder_x3_cls_workspace_bytes_f16": (c_size_t, [c_void_p, c_int, c_int]),
@@ -148,6 +154,8 @@ SIGNATURES = {
     "tt_gemm_x3_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_attention_x3_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                     c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "tt_attention_x3_hd_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                       c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     # reference precision on two matrix-time units (csrc/f16c_path.hip)
     "tt_encoder_f16c_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "tt_encoder_f16c_cls_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),

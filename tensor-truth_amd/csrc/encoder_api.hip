@@ -479,4 +479,18 @@ int tt_attention_varlen(const void* qk, int ld_qk, int q_col0, int k_col0, const
     return tt_attention_launch(a, (hipStream_t)stream);
 }
 
+// the CLS-only kernel of the last layer on tt_attention_varlen's operands: out row b = sequence b's first query row
+int tt_attention_cls_varlen(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,
+                            int ld_out, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads,
+                            int head_dim, int max_len, void* stream) {
+    TT_CHECK_ARG(qk && vt && out && seq_start && seq_len, "null pointer");
+    TT_CHECK_ARG(head_dim == 64 || head_dim == 32, "head_dim=%d: the attention takes 64- or 32-wide heads", head_dim);
+    AttnParams a{};
+    a.qk = (const uint16_t*)qk; a.ld_qk = ld_qk; a.q_col0 = q_col0; a.k_col0 = k_col0;
+    a.vt = (const uint16_t*)vt; a.ldvt = ldvt; a.out = (uint16_t*)out; a.ld_out = ld_out;
+    a.seq_start = seq_start; a.seq_len = seq_len; a.n_seq = n_seq; a.heads = heads; a.head_dim = head_dim;
+    a.max_len = max_len; a.scale = 1.0f / sqrtf((float)head_dim);
+    return tt_attention_cls_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -36,3 +36,5 @@
 #define tt_split_planes tt_split_planes_f16
 #define tt_gemm_x3 tt_gemm_x3_f16
 #define tt_attention_x3 tt_attention_x3_f16
+#define tt_attention_x3_hd tt_attention_x3_hd_f16
+#define tt_attention_cls_varlen tt_attention_cls_varlen_f16

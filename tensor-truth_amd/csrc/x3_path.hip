@@ -919,8 +919,25 @@ int tt_attention_x3(const void* qk_planes, int ld_qk, int q_col0, int k_col0, in
     a.vt = (const uint16_t*)vt_hi; a.vt_lo = (const uint16_t*)vt_lo; a.ldvt = ldvt;
     a.out = (uint16_t*)out_planes; a.ld_out = ld_out; a.out_lo_off = out_lo_off;
     a.seq_start = seq_start; a.seq_len = seq_len; a.n_seq = n_seq; a.heads = heads; a.max_len = max_len; a.scale = 0.125f;
-    a.head_dim = 64;           // (the building block of the parity tests: 64-wide heads; 32-wide ones are tested through the forward)
+    a.head_dim = 64;           // (64-wide heads; 32-wide ones and the CLS-only kernel: tt_attention_x3_hd)
     return attention_x3_launch(a, (hipStream_t)stream);
+}
+
+// tt_attention_x3 with the head width named (32 or 64) and, cls_only = 1, the CLS-only kernel of the last layer: out_planes then
+// holds ONE row per sequence (row b = sequence b's first query), the layout attention_cls_x3_launch writes
+int tt_attention_x3_hd(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi, const void* vt_lo,
+                       int ldvt, void* out_planes, int ld_out, int out_lo_off, const int32_t* seq_start, const int32_t* seq_len,
+                       int n_seq, int heads, int max_len, int head_dim, int cls_only, void* stream) {
+    TT_CHECK_ARG(qk_planes && vt_hi && vt_lo && out_planes && seq_start && seq_len, "null pointer");
+    TT_CHECK_ARG(head_dim == 64 || head_dim == 32, "head_dim=%d: the split-plane attention takes 64- or 32-wide heads", head_dim);
+    TT_CHECK_ARG(cls_only == 0 || cls_only == 1, "cls_only=%d (0 or 1)", cls_only);
+    AttnX3Params a{};
+    a.qk = (const uint16_t*)qk_planes; a.ld_qk = ld_qk; a.q_col0 = q_col0; a.k_col0 = k_col0; a.lo_off = lo_off;
+    a.vt = (const uint16_t*)vt_hi; a.vt_lo = (const uint16_t*)vt_lo; a.ldvt = ldvt;
+    a.out = (uint16_t*)out_planes; a.ld_out = ld_out; a.out_lo_off = out_lo_off;
+    a.seq_start = seq_start; a.seq_len = seq_len; a.n_seq = n_seq; a.heads = heads; a.max_len = max_len;
+    a.head_dim = head_dim; a.scale = 1.0f / sqrtf((float)head_dim);
+    return cls_only ? attention_cls_x3_launch(a, (hipStream_t)stream) : attention_x3_launch(a, (hipStream_t)stream);
 }
 
 }  // extern "C"
