@@ -113,6 +113,42 @@ int tt_scan_topk_shadow(const void* corpus_bf16, const void* shadow, int64_t cap
                         float* out_scores, int32_t* out_idx,
                         void* workspace, size_t workspace_bytes, int32_t* status_flag, void* stream);
 
+/* ---- metadata-filtered exact search ----------------------------------------
+ * Replaces the `where=` metadata filter of the reference's vector-store query
+ * (src/tensortruth/rag_engine.py:286-365 builds it; index.as_retriever(filters=...)).
+ * Every filterable key is dictionary-encoded per row: codes[row] is an int32, 0 = key absent.  The host evaluates each clause once
+ * over the key's distinct values into a bitset over codes (bit c set = code c passes; bit 0 is never set), so every operator is
+ * the same device test.
+ *
+ * tt_filter_rows: rows r of [seg_offsets_host[0], seg_offsets_host[n_segments]) (NULL: one segment [0, n_rows)) that pass
+ * n_clauses (1..8) clauses, combined with AND (any = 0) or OR (any = 1); clause c is (codes_host[c]: device code column of
+ * n_rows entries, bitsets_host[c]: device bitset of ceil(n_codes_host[c] / 32) words; codes >= n_codes do not pass).
+ * Writes the passing rows in ASCENDING order to out_rows (capacity: the rows evaluated) and out_offsets[s] (device,
+ * n_segments + 1 entries) = list position of segment s's first row; out_offsets[n_segments] = the count.  No atomics: the list
+ * is deterministic.  n_segments <= 64.
+ *
+ * tt_scan_topk_rows: the exact top-k of tt_scan_topk over exactly the rows a tt_filter_rows list names (rows, list_offsets:
+ * both read on the device, no host round trip between the two calls).  max_rows = a host-side upper bound on the rows listed
+ * per segment (it sizes the workspace and picks the dense or the streaming path; a list longer than it raises status bit 8).
+ * Scores and indices are bit-identical to tt_scan_topk over the gathered rows (same fragments, MFMA order and selection),
+ * indices mapped back to rows.  seg_offsets_host == NULL: one segment, out [n_queries][k], index = idx_base + row.
+ * Otherwise the segments of tt_filter_rows (n_segments + 1 row offsets): out [n_queries][n_segments][k], indices
+ * SEGMENT-LOCAL rows (row - seg_offsets_host[s]).  Padding (-inf, -1).  status_flag as in tt_scan_topk (non-zero: re-run
+ * tt_scan_topk_exact over the gathered rows). */
+size_t tt_filter_rows_workspace_bytes(int64_t n_rows);
+int tt_filter_rows(int n_clauses, const int32_t* const* codes_host, const uint32_t* const* bitsets_host,
+                   const int32_t* n_codes_host, int any, int64_t n_rows,
+                   const int64_t* seg_offsets_host, int n_segments,
+                   int32_t* out_rows, int32_t* out_offsets,
+                   void* workspace, size_t workspace_bytes, void* stream);
+size_t tt_scan_topk_rows_workspace_bytes(int64_t max_rows, int dim, int n_queries, int k);
+int tt_scan_topk_rows(const void* corpus_bf16, int64_t n_rows, int dim,
+                      const void* queries_bf16, int n_queries, int k,
+                      const int32_t* rows, const int32_t* list_offsets, int64_t max_rows,
+                      const int64_t* seg_offsets_host, int n_segments, int32_t idx_base,
+                      float* out_scores, int32_t* out_idx,
+                      void* workspace, size_t workspace_bytes, int32_t* status_flag, void* stream);
+
 /* Merge per-shard partial top-k lists (the step after the RCCL all-gather of
  * SURVEY.md section 8e; also MultiIndexRetriever's concatenate+sort,
  * rag_engine.py:463-507, when indexes live in one matrix).

@@ -33,6 +33,13 @@ struct ScanParams {
     // row_cnt (device) = the number of table entries, read by the kernel -- row_hi is then only the launch's upper bound
     const int32_t* row_table;
     const int32_t* row_cnt;
+    // row-list launches (tt_scan_topk_rows: MODE 1, row_lo = 0, group_stride <= 1): launch row i is PHYSICAL row
+    // gather_rows[row_range[0] + i] of `corpus`, and the launch covers min(row_range[1] - row_range[0], row_hi) rows -- both ends
+    // are read on the device (the list and its length come from tt_filter_rows), row_hi is the host's upper bound.  Whole 128-B
+    // row segments are gathered through the list into the streaming kernel's own ring, transpose and MFMA order: the same score
+    // bits as a contiguous scan of those rows.
+    const int32_t* gather_rows;
+    const int32_t* row_range;
 };
 
 #define TT_SCAN_PRIV_SLOTS 16

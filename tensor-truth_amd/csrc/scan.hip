@@ -134,7 +134,8 @@ __device__ __forceinline__ void scan_epilogue(const ScanParams& p, f32x16 (&acc)
 // VAR bits (ablation / tuning knobs, D=1024 filter kernels only): 1 = default-policy corpus
 // loads instead of the non-temporal ones every shipped variant uses (+11 % kernel time), 2 = loads only (no LDS, no MFMA), 4 = loads + LDS transpose writes only,
 // 8 = everything but the MFMAs, 16 = MFMAs without the query-image reads.
-template <int D, int MODE, int OUT, int VAR>
+// G (MODE 1 only): row-list launch -- the rows come through p.gather_rows (see ScanParams), everything else is unchanged.
+template <int D, int MODE, int OUT, int VAR, bool G = false>
 __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
     using C = Cfg<D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -187,6 +188,14 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
             if (p.row_hi <= p.row_lo) return;
         }
     }
+    const int32_t* gtab = nullptr;
+    if constexpr (G) {            // (no early return on an empty list: the filter variant still writes its private-list counts)
+        const int32_t b = p.row_range[0];
+        const int64_t n = (int64_t)p.row_range[1] - b;
+        const int64_t span = p.row_hi - p.row_lo;
+        p.row_hi = p.row_lo + (n < 0 ? 0 : (n < span ? n : span));
+        gtab = p.gather_rows + b;
+    }
     const int64_t n_groups = (p.row_hi - p.row_lo + 31) / 32;
     const int64_t per_blk = n_groups / gridDim.x;
     const int64_t rem = n_groups % gridDim.x;
@@ -222,11 +231,26 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
         uint4 ring[P][4];
         const int lrow = lane >> 3;   // row inside an 8-row load
         const int lpiece = lane & 7;  // 16-B piece inside the 128-B chunk
-        auto issue = [&](uint4(&dst)[4], int64_t g, int c) {
+        // G: the physical rows of this lane's four load rows (8 j + lrow) in the current and the next group, looked up one group ahead
+        int32_t grow[4] = {0, 0, 0, 0}, grow_n[4] = {0, 0, 0, 0};
+        auto gload = [&](int32_t(&dst)[4], int64_t g) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                int64_t row = p.row_lo + g * gstride * 32 + 8 * j + lrow;
+                int64_t row = p.row_lo + g * 32 + 8 * j + lrow;
                 row = row < last_row ? row : last_row;
+                dst[j] = gtab[row];
+            }
+        };
+        auto issue = [&](uint4(&dst)[4], int64_t g, int c, const int32_t(&gr)[4]) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int64_t row;
+                if constexpr (G) {
+                    row = gr[j];
+                } else {
+                    row = p.row_lo + g * gstride * 32 + 8 * j + lrow;
+                    row = row < last_row ? row : last_row;
+                }
                 dst[j] = ldg16c<(VAR & 1) == 0>(corpus + (size_t)row * D + c * 64 + lpiece * 8);
             }
         };
@@ -242,12 +266,16 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
         const int rswz = (ql >> 1) & 7;
 
         if (grp < g_hi) {
+            if constexpr (G) gload(grow, grp);
 #pragma unroll
-            for (int c = 0; c < P; ++c) issue(ring[c], grp, c);
+            for (int c = 0; c < P; ++c) issue(ring[c], grp, c, grow);
         }
         while (grp < g_hi) {
             const int64_t nxt = grp + kWaves;
             const bool has_next = nxt < g_hi;
+            if constexpr (G) {
+                if (has_next) gload(grow_n, nxt);
+            }
 #pragma unroll
             for (int c = 0; c < C::NCH; ++c) {
                 const int s = c % P;
@@ -266,9 +294,9 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
                 // depth collapses to zero
                 __builtin_amdgcn_sched_barrier(0);
                 if (c + P < C::NCH) {
-                    issue(ring[s], grp, c + P);
+                    issue(ring[s], grp, c + P, grow);
                 } else if (has_next) {
-                    issue(ring[s], nxt, c + P - C::NCH);
+                    issue(ring[s], nxt, c + P - C::NCH, grow_n);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr ((VAR & 6) == 0)
@@ -295,6 +323,10 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
             }
             scan_epilogue<OUT>(p, acc, thr, qvalid, q0, ql, half, grp, pcnt, pbase);
             grp = nxt;
+            if constexpr (G) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) grow[j] = grow_n[j];
+            }
         }
     } else {
         constexpr int P = C::P0;
@@ -355,11 +387,11 @@ __global__ __launch_bounds__(kThreads) void scan_kernel(ScanParams p) {
 }  // namespace
 
 // ---- host-side launcher ---------------------------------------------------------
-template <int D, int MODE, int OUT, int VAR>
+template <int D, int MODE, int OUT, int VAR, bool G = false>
 static int launch_one(const ScanParams& p, int blocks, int q_tiles, hipStream_t stream) {
     using C = Cfg<D>;
     const size_t lds = (size_t)C::kQImageBytes + (MODE == 1 ? (size_t)kWaves * kScratchPerWave : 0);
-    auto kern = scan_kernel<D, MODE, OUT, VAR>;
+    auto kern = scan_kernel<D, MODE, OUT, VAR, G>;
     TT_SET_MAX_LDS(kern, lds);   // per instantiation, per thread, per device
     {
         TtProfScope prof(p.prof_id ? p.prof_id : (OUT == 0 ? TT_K_SCAN_FILTER : TT_K_SCAN_SAMPLE), stream);
@@ -373,6 +405,13 @@ template <int D>
 static int launch_d(const ScanParams& p, int mode, int out, int blocks, int q_tiles, hipStream_t stream) {
     const int load_mode = mode & 15;
     const int var = mode >> 4;
+    if (p.row_range) {   // row-list launch (tt_scan_topk_rows): full-line loads, no tuning variants
+        switch (out) {
+            case 0: return launch_one<D, 1, 0, 0, true>(p, blocks, q_tiles, stream);
+            case 1: return launch_one<D, 1, 1, 0, true>(p, blocks, q_tiles, stream);
+            default: return launch_one<D, 1, 2, 0, true>(p, blocks, q_tiles, stream);
+        }
+    }
     if constexpr (D == 1024) {
         // tuning / ablation variants exist for the headline shape only
         if (out == 0 && load_mode == 1) {

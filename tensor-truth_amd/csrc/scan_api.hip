@@ -80,7 +80,7 @@ bool scan_gemm_enabled() {
     return on;
 }
 
-Plan make_plan(int64_t n_rows, int dim, int n_queries, int k, int cus) {
+Plan make_plan(int64_t n_rows, int dim, int n_queries, int k, int cus, bool allow_gemm = true) {
     Plan pl{};
     pl.qpad = (n_queries + 63) / 64 * 64;
     pl.cap = kCap;
@@ -91,7 +91,7 @@ Plan make_plan(int64_t n_rows, int dim, int n_queries, int k, int cus) {
     // shard worth tiling) the filter pass runs as a 256-query-wide MFMA contraction instead: one pass over the rows per 256
     // queries.  It has no lane-private lists, so every survivor goes to the shared list: a larger sample (tighter threshold;
     // expected survivors ~ k * rows / sample rows per query) and a list sized for 4x that expectation.
-    pl.gemm = scan_gemm_enabled() && n_queries > 64 && dim % 128 == 0 && n_rows >= 262144 && n_rows >= (int64_t)2048 * k;
+    pl.gemm = allow_gemm && scan_gemm_enabled() && n_queries > 64 && dim % 128 == 0 && n_rows >= 262144 && n_rows >= (int64_t)2048 * k;
     if (pl.gemm) {
         static const int64_t n0_env = TT_DIAG_ENV_INT("TT_SCAN_GEMM_N0", 0);
         n0 = n0_env > 0 ? n0_env : 131072;   // (measured, 10M x 1024 x 256 queries: 65536 -> 5.50, 131072 -> 5.35, 262144 -> 5.52 ms per batch)
@@ -247,6 +247,39 @@ ShadowPlan shadow_plan(int64_t n_rows, int dim, int n_queries, int k, int cus) {
 __global__ void add_idx_base_kernel(int32_t* idx, int n, int32_t base) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && idx[i] >= 0) idx[i] += base;
+}
+
+// ---- row-list scan (tt_scan_topk_rows) ----
+// a segment whose listed rows are bounded by `bound` takes the dense path exactly when tt_scan_topk would take it for that many rows
+bool rows_dense(int64_t bound, int k) { return bound < (int64_t)128 * k || bound <= 8192; }
+size_t rows_head_bytes(int n_queries) { return tt_align_up((size_t)((n_queries + 63) / 64 * 64) * sizeof(int32_t), 256); }
+size_t rows_body_bytes(int64_t bound, int dim, int n_queries, int k, int cus) {
+    if (bound <= 0) return 0;
+    if (rows_dense(bound, k)) return tt_align_up((size_t)((n_queries + 63) / 64 * 64) * (size_t)((bound + 31) / 32 * 32) * sizeof(float), 256);
+    return make_plan(bound, dim, n_queries, k, cus, false).total;
+}
+// cnt_q[q] = listed rows of segment s (clamped to the host's bound: a list longer than the bound raises bit 8 of the status word)
+__global__ void rows_count_kernel(const int32_t* off, int s, int64_t bound, int32_t* cnt_q, int n, int32_t* flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t c = (int64_t)off[s + 1] - off[s];
+    if (i < n) cnt_q[i] = (int32_t)(c < bound ? c : bound);
+    if (i == 0 && c > bound && flag) atomicOr(flag, 8);
+}
+// list positions -> rows: idx[q * stride + j] = rows[off[s] + idx] + add (padding -1 stays)
+__global__ void rows_map_kernel(int32_t* idx, int n_queries, int k, int64_t stride, const int32_t* rows, const int32_t* off, int s, int32_t add) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_queries * k) return;
+    int32_t* e = idx + (size_t)(i / k) * stride + (i % k);
+    const int32_t pos = *e;
+    if (pos >= 0) *e = rows[(int64_t)off[s] + pos] + add;
+}
+__global__ void fill_pad_strided_kernel(float* s, int32_t* ix, int n_queries, int width, int64_t stride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_queries * width) {
+        const size_t o = (size_t)(i / width) * stride + (i % width);
+        s[o] = -__builtin_inff();
+        ix[o] = -1;
+    }
 }
 }  // namespace
 
@@ -652,6 +685,164 @@ int tt_scan_topk_shadow(const void* corpus_bf16, const void* shadow, int64_t cap
     if (idx_base != 0) {
         const int n = n_queries * k;
         hipLaunchKernelGGL(add_idx_base_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out_idx, n, idx_base);
+        TT_CHECK_LAUNCH();
+    }
+    return TT_OK;
+}
+
+// ---- row-list scan: the exact top-k over the rows a tt_filter_rows list names (filter.hip) ----
+size_t tt_scan_topk_rows_workspace_bytes(int64_t max_rows, int dim, int n_queries, int k) {
+    if (max_rows < 0 || n_queries <= 0 || k < 1 || k > 1024) return 0;
+    int cus = tt_cu_count_cached();
+    if (cus <= 0) cus = 256;
+    // any segment bound <= max_rows: the streaming plan grows with the rows, the dense one too -- the larger of the two ends covers both
+    const int64_t dense_max = (int64_t)128 * k - 1 > 8192 ? (int64_t)128 * k - 1 : 8192;
+    const size_t a = rows_body_bytes(max_rows, dim, n_queries, k, cus);
+    const size_t b = rows_body_bytes(max_rows < dense_max ? max_rows : dense_max, dim, n_queries, k, cus);
+    return rows_head_bytes(n_queries) + (a > b ? a : b);
+}
+
+int tt_scan_topk_rows(const void* corpus_bf16, int64_t n_rows, int dim, const void* queries_bf16, int n_queries, int k,
+                      const int32_t* rows, const int32_t* list_offsets, int64_t max_rows, const int64_t* seg_offsets_host, int n_segments,
+                      int32_t idx_base, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes,
+                      int32_t* status_flag, void* stream) {
+    int rc = check_common(corpus_bf16, n_rows, dim, queries_bf16, n_queries, k, out_scores, out_idx);
+    if (rc) return rc;
+    TT_CHECK_ARG(n_segments >= 1 && n_segments <= TT_SCAN_MAX_SEGMENTS, "n_segments=%d outside [1,%d]", n_segments, TT_SCAN_MAX_SEGMENTS);
+    TT_CHECK_ARG(max_rows >= 0, "max_rows=%lld", (long long)max_rows);
+    if (seg_offsets_host) {
+        TT_CHECK_ARG(seg_offsets_host[0] >= 0 && seg_offsets_host[n_segments] <= n_rows, "segment offsets outside [0, n_rows]");
+        for (int s = 0; s < n_segments; ++s)
+            TT_CHECK_ARG(seg_offsets_host[s] <= seg_offsets_host[s + 1], "segment offsets must be non-decreasing (segment %d)", s);
+    } else {
+        TT_CHECK_ARG(n_segments == 1, "n_segments=%d without segment offsets", n_segments);
+    }
+    if (n_queries == 0) return TT_OK;
+    TT_CHECK_ARG(list_offsets && (rows || max_rows == 0), "null row list");
+    hipStream_t st = (hipStream_t)stream;
+    if (status_flag) TT_CHECK_HIP(hipMemsetAsync(status_flag, 0, sizeof(int32_t), st));
+    int cus = tt_cu_count_cached();
+    if (cus <= 0) cus = 256;
+    const size_t need = tt_scan_topk_rows_workspace_bytes(max_rows, dim, n_queries, k);
+    if (!workspace || workspace_bytes < need) {
+        tt_set_error("tt_scan_topk_rows: workspace %zu < required %zu bytes", workspace_bytes, need);
+        return TT_E_WORKSPACE;
+    }
+    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    const int qpad = (n_queries + 63) / 64 * 64;
+    int32_t* cnt_q = (int32_t*)workspace;
+    char* ws = (char*)workspace + rows_head_bytes(n_queries);
+    const int64_t ostride = (int64_t)n_segments * k;
+    const int mode = 1;     // full-line loads through the list (scan.hip, row-list launches)
+    {
+        const int n = n_queries * n_segments * k;
+        hipLaunchKernelGGL(fill_pad_strided_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out_scores, out_idx, 1, n, (int64_t)n);
+        TT_CHECK_LAUNCH();
+    }
+    for (int s = 0; s < n_segments; ++s) {
+        const int64_t seg_rows = seg_offsets_host ? seg_offsets_host[s + 1] - seg_offsets_host[s] : n_rows;
+        const int64_t bound = max_rows < seg_rows ? max_rows : seg_rows;
+        if (bound <= 0) continue;      // (padding written above)
+        float* os = out_scores + (size_t)s * k;
+        int32_t* oi = out_idx + (size_t)s * k;
+        hipLaunchKernelGGL(rows_count_kernel, dim3((qpad + 255) / 256), dim3(256), 0, st, list_offsets, s, bound, cnt_q, qpad, status_flag);
+        TT_CHECK_LAUNCH();
+        ScanParams sp{};
+        sp.corpus = (const uint16_t*)corpus_bf16;
+        sp.queries = (const uint16_t*)queries_bf16;
+        sp.row_lo = 0;
+        sp.n_queries = n_queries;
+        sp.gather_rows = rows;
+        sp.row_range = list_offsets + s;
+        if (rows_dense(bound, k)) {
+            // every listed row scored, exact selection over the first cnt_q positions
+            const int64_t stride = (bound + 31) / 32 * 32;
+            sp.row_hi = bound;
+            sp.dense = (float*)ws;
+            sp.dense_stride = stride;
+            rc = tt_scan_launch(sp, dim, mode, 1, cus, st);
+            if (rc) return rc;
+            SelectParams se{};
+            se.scores = (float*)ws;
+            se.stride = stride;
+            se.cnt = cnt_q;
+            se.cap = INT_MAX;
+            se.k = k;
+            se.out_scores = os;
+            se.out_idx = oi;
+            se.out_stride = ostride;
+            rc = tt_select_launch(se, n_queries, st);
+            if (rc) return rc;
+        } else {
+            // tt_scan_topk's pipeline over the list: threshold from the group maxima of its first n0 rows, filter pass, exact selection
+            const Plan pl = make_plan(bound, dim, n_queries, k, cus, false);
+            float* dense = (float*)(ws + pl.off_dense);
+            float* cs = (float*)(ws + pl.off_cs);
+            int32_t* ci = (int32_t*)(ws + pl.off_ci);
+            int32_t* cnt = (int32_t*)(ws + pl.off_cnt);
+            float* thr = (float*)(ws + pl.off_thr);
+            {   // groups beyond a short list are never written: -inf, so that they cannot raise the threshold
+                const int n = pl.qpad * (int)pl.stride;
+                hipLaunchKernelGGL(fill_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dense, -__builtin_inff(), n);
+                TT_CHECK_LAUNCH();
+            }
+            sp.row_hi = pl.n0;
+            sp.dense = dense;
+            sp.dense_stride = pl.stride;
+            rc = tt_scan_launch(sp, dim, mode, 2, cus, st);
+            if (rc) return rc;
+            SelectParams s1{};
+            s1.scores = dense;
+            s1.stride = pl.stride;
+            s1.m_fixed = (int)((pl.n0 + 31) / 32);
+            s1.cap = INT_MAX;
+            s1.k = k;
+            s1.out_scores = cs;
+            s1.out_idx = ci;
+            s1.out_stride = pl.cap;
+            s1.thr_out = thr;
+            if (tt_select_fused_outputs(k)) {
+                s1.n_real = n_queries;
+                s1.zero_cnt = cnt;
+                rc = tt_select_launch(s1, pl.qpad, st);
+                if (rc) return rc;
+            } else {
+                rc = tt_select_launch(s1, n_queries, st);
+                if (rc) return rc;
+                TT_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)pl.qpad * sizeof(int32_t), st));
+            }
+            ScanParams mp = sp;
+            mp.row_hi = bound;
+            mp.dense = nullptr;
+            mp.thr = thr;
+            mp.cnt = cnt;
+            mp.cand_scores = cs;
+            mp.cand_idx = ci;
+            mp.cap = pl.cap;
+            mp.priv = (uint2*)(ws + pl.off_priv);
+            mp.priv_cnt = (int32_t*)(ws + pl.off_pcnt);
+            rc = tt_scan_launch(mp, dim, mode, 0, pl.main_blocks, st);
+            if (rc) return rc;
+            SelectParams s2{};
+            s2.scores = cs;
+            s2.idx = ci;
+            s2.stride = pl.cap;
+            s2.cnt = cnt;
+            s2.cap = pl.cap;
+            s2.k = k;
+            s2.out_scores = os;
+            s2.out_idx = oi;
+            s2.out_stride = ostride;
+            s2.overflow_flag = status_flag;
+            s2.priv = mp.priv;
+            s2.priv_cnt = mp.priv_cnt;
+            s2.n_sub = pl.n_sub;
+            rc = tt_select_launch(s2, n_queries, st);
+            if (rc) return rc;
+        }
+        const int n = n_queries * k;
+        const int32_t add = seg_offsets_host ? (int32_t)(-seg_offsets_host[s]) : idx_base;
+        hipLaunchKernelGGL(rows_map_kernel, dim3((n + 255) / 256), dim3(256), 0, st, oi, n_queries, k, ostride, rows, list_offsets, s, add);
         TT_CHECK_LAUNCH();
     }
     return TT_OK;

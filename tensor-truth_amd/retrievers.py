@@ -131,6 +131,12 @@ class MultiIndexRetriever:
         indexes = [b.index for b in bases]
         if len({(ix.dim, ix.device) for ix in indexes}) != 1 or len({id(ix) for ix in indexes}) != len(indexes):
             return None
+        # one pass applies ONE metadata filter to every module: only when all retrievers carry the same one
+        fkeys = {getattr(b, "filter_key", None) for b in bases}
+        if len(fkeys) != 1:
+            return None
+        fkey = fkeys.pop()
+        filters = bases[0].filters if fkey is not None else None
         with self._group_lock:   # retrieve() is called from several threads (rag_engine.py:392,420)
             if self._group is None or [id(ix) for ix in self._group.indexes] != [id(ix) for ix in indexes]:
                 self._group = HipIndexGroup(indexes)
@@ -138,7 +144,7 @@ class MultiIndexRetriever:
         k = max(min(b.similarity_top_k, ix.num_live) for b, ix in zip(bases, indexes))
         if k < 1:
             return [[] for _ in bases]
-        scores, rows, snap_ids = self._scan_front.submit((group, bundle.embedding, k))
+        scores, rows, snap_ids = self._scan_front.submit((group, bundle.embedding, k, fkey, filters))
         out = []
         for i, (r, b) in enumerate(zip(self.retrievers, bases)):
             kk = min(b.similarity_top_k, indexes[i].num_live)
@@ -148,19 +154,20 @@ class MultiIndexRetriever:
 
     @staticmethod
     def _group_scan_many(items):
-        """[(group, query embedding, k)] -> [(scores [S][k'], rows [S][k'], id lists)]: one ``HipIndexGroup.search_host`` per group
-        (there is one) with k' = the largest k asked for -- an exact top-k list is a prefix of every longer one (score descending,
-        row ascending among equals), and every caller slices its own k per module."""
+        """[(group, query embedding, k[, filter key, filters])] -> [(scores [S][k'], rows [S][k'], id lists)]: one
+        ``HipIndexGroup.search_host`` per (group, filter key) with k' = the largest k asked for -- an exact top-k list is a prefix of
+        every longer one (score descending, row ascending among equals), and every caller slices its own k per module."""
         import torch
 
         out = [None] * len(items)
         by_group = {}
-        for i, (group, _, _) in enumerate(items):
-            by_group.setdefault(id(group), (group, []))[1].append(i)
-        for group, members in by_group.values():
+        for i, it in enumerate(items):
+            fkey = it[3] if len(it) > 3 else None
+            by_group.setdefault((id(it[0]), fkey), (it[0], it[4] if len(it) > 4 else None, []))[2].append(i)
+        for group, filters, members in by_group.values():
             k = max(items[i][2] for i in members)
             q = torch.tensor([items[i][1] for i in members], dtype=torch.float32)
-            scores, rows, ids = group.search_host(q, k)
+            scores, rows, ids = group.search_host(q, k) if filters is None else group.search_host(q, k, filters=filters)
             scores, rows = scores.tolist(), rows.tolist()
             for j, i in enumerate(members):
                 out[i] = (scores[j], rows[j], ids)

@@ -232,6 +232,128 @@ def scan_topk_segmented(corpus: torch.Tensor, queries: torch.Tensor, k: int, seg
     return out_s, out_i
 
 
+def filter_rows(compiled, n_rows: int, device, seg_offsets=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``tt_filter_rows``: the rows of ``[0, n_rows)`` (or of the segments ``seg_offsets``) that pass a compiled metadata filter
+    (``metadata_filter.compile_filter``) -> (rows int32 [capacity], list offsets int32 [S + 1]), both on the device: the list
+    is ascending, segment s is ``rows[offsets[s]:offsets[s+1]]`` and ``offsets[S]`` is the count.  No host sync."""
+    import ctypes
+    lib = _lib.load_library()
+    offs = [0, int(n_rows)] if seg_offsets is None else [int(o) for o in seg_offsets]
+    n_seg = len(offs) - 1
+    span = offs[-1] - offs[0]
+    rows = torch.empty(max(span, 1), dtype=torch.int32, device=device)
+    list_off = torch.empty(n_seg + 1, dtype=torch.int32, device=device)
+    n_cl = len(compiled.columns)
+    c_codes = (ctypes.c_void_p * n_cl)(*[c.data_ptr() for c in compiled.columns])
+    c_bits = (ctypes.c_void_p * n_cl)(*[b.data_ptr() for b in compiled.bitsets])
+    c_ncodes = (ctypes.c_int32 * n_cl)(*compiled.n_codes)
+    c_offs = (ctypes.c_int64 * (n_seg + 1))(*offs) if seg_offsets is not None else None
+    with torch.cuda.device(device):
+        need = lib.tt_filter_rows_workspace_bytes(span)
+        ws = _filter_ws.get(device, need + 256)
+        base = (ws.data_ptr() + 255) // 256 * 256
+        rc = lib.tt_filter_rows(n_cl, c_codes, c_bits, c_ncodes, 1 if compiled.any else 0, int(n_rows), c_offs, n_seg,
+                                rows.data_ptr(), list_off.data_ptr(), base, ws.numel() - (base - ws.data_ptr()), _stream_ptr(device))
+        _lib.check(rc, "tt_filter_rows")
+    return rows, list_off
+
+
+_filter_ws = _Workspace()      # (tt_filter_rows' masks live across the call only; own buffers: a rows scan follows on the same thread)
+
+
+def scan_topk_rows(corpus: torch.Tensor, queries: torch.Tensor, k: int, rows: torch.Tensor, list_offsets: torch.Tensor,
+                   max_rows: int, seg_offsets=None, idx_base: int = 0, check_overflow: bool = True, return_flag: bool = False,
+                   _packed: Optional[torch.Tensor] = None):
+    """``tt_scan_topk_rows``: the exact top-k over exactly the rows a ``filter_rows`` list names -- bit-identical to ``scan_topk``
+    over ``corpus.index_select(0, listed rows)`` with the indices mapped back to rows.  ``max_rows`` = the host's upper bound on
+    the rows listed per segment.  ``seg_offsets`` None -> (scores [Q, k], idx_base + rows [Q, k]); else (scores [Q, S, k],
+    segment-local rows [Q, S, k]).  Padding (-inf, -1).  An overflowed candidate list (status word) re-runs the dense exact path
+    over the gathered rows, as ``scan_topk`` does.  The fp8 shadow is not used here."""
+    import ctypes
+    lib = _lib.load_library()
+    _require_cuda(corpus, "corpus")
+    _require_cuda(queries, "queries")
+    if corpus.dtype != torch.bfloat16 or queries.dtype != torch.bfloat16:
+        raise TypeError("corpus and queries must be torch.bfloat16")
+    if corpus.dim() != 2 or queries.dim() != 2 or corpus.shape[1] != queries.shape[1]:
+        raise ValueError(f"shape mismatch: corpus {tuple(corpus.shape)} queries {tuple(queries.shape)}")
+    if not corpus.is_contiguous() or not queries.is_contiguous():
+        raise ValueError("corpus and queries must be contiguous row-major")
+    n, d = corpus.shape
+    q = queries.shape[0]
+    dev = corpus.device
+    n_seg = 1 if seg_offsets is None else len(seg_offsets) - 1
+    shape = (q, k) if seg_offsets is None else (q, n_seg, k)
+    if _packed is not None:
+        out_s = _packed[: q * n_seg * k].view(torch.float32).view(shape)
+        out_i = _packed[q * n_seg * k: 2 * q * n_seg * k].view(shape)
+    else:
+        out_s = torch.empty(shape, dtype=torch.float32, device=dev)
+        out_i = torch.empty(shape, dtype=torch.int32, device=dev)
+    if q == 0:
+        return out_s, out_i
+    c_offs = (ctypes.c_int64 * (n_seg + 1))(*[int(o) for o in seg_offsets]) if seg_offsets is not None else None
+    with torch.cuda.device(dev):
+        st = _stream_ptr(dev)
+        need = lib.tt_scan_topk_rows_workspace_bytes(int(max_rows), d, q, k)
+        ws = _ws.get(dev, need + 256)
+        base = (ws.data_ptr() + 255) // 256 * 256
+        if _packed is not None:
+            flag = _packed[2 * q * n_seg * k:]
+            flag.zero_()
+        else:
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        rc = lib.tt_scan_topk_rows(corpus.data_ptr(), n, d, queries.data_ptr(), q, k, rows.data_ptr(), list_offsets.data_ptr(),
+                                   int(max_rows), c_offs, n_seg, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
+                                   ws.numel() - (base - ws.data_ptr()), flag.data_ptr(), st)
+        _lib.check(rc, "tt_scan_topk_rows")
+        if _packed is not None:
+            return out_s, out_i
+        if return_flag:
+            return out_s, out_i, int(flag.item())
+        if check_overflow and int(flag.item()) != 0:
+            return scan_topk_rows_exact(corpus, queries, k, rows, list_offsets, seg_offsets, idx_base)
+    return out_s, out_i
+
+
+def scan_topk_rows_exact(corpus, queries, k, rows, list_offsets, seg_offsets=None, idx_base: int = 0):
+    """The fallback of ``scan_topk_rows``: the dense exact path over ``index_select``ed rows, per segment (one host sync)."""
+    offs = list_offsets.cpu().tolist()
+    n_seg = len(offs) - 1
+    q = queries.shape[0]
+    s_out = torch.full((q, n_seg, k), float("-inf"), dtype=torch.float32, device=corpus.device)
+    i_out = torch.full((q, n_seg, k), -1, dtype=torch.int32, device=corpus.device)
+    for s in range(n_seg):
+        sub = rows[offs[s]:offs[s + 1]].long()
+        if sub.numel() == 0:
+            continue
+        es, ei = scan_topk(corpus.index_select(0, sub).contiguous(), queries, k, exact_dense=True)
+        add = idx_base if seg_offsets is None else -int(seg_offsets[s])
+        mapped = torch.where(ei >= 0, sub[ei.clamp_min(0).long()].to(torch.int32) + add, ei)
+        s_out[:, s], i_out[:, s] = es, mapped
+    if seg_offsets is None:
+        return s_out[:, 0].contiguous(), i_out[:, 0].contiguous()
+    return s_out, i_out
+
+
+def scan_topk_rows_host(corpus, queries, k, rows, list_offsets, max_rows: int, seg_offsets=None, idx_base: int = 0):
+    """``scan_topk_rows`` with the hits on the host: scores, indices and the status word come back in ONE copy (one sync), as
+    ``scan_topk_host``; a flagged overflow re-runs the dense exact path over the gathered rows.  -> CPU tensors."""
+    q = queries.shape[0]
+    n_seg = 1 if seg_offsets is None else len(seg_offsets) - 1
+    shape = (q, k) if seg_offsets is None else (q, n_seg, k)
+    if q == 0:
+        return torch.empty(shape, dtype=torch.float32), torch.empty(shape, dtype=torch.int32)
+    m = q * n_seg * k
+    packed = torch.empty(2 * m + 1, dtype=torch.int32, device=corpus.device)
+    scan_topk_rows(corpus, queries, k, rows, list_offsets, max_rows, seg_offsets, idx_base, _packed=packed)
+    host = packed.cpu()
+    if int(host[-1]) != 0:
+        s, i = scan_topk_rows_exact(corpus, queries, k, rows, list_offsets, seg_offsets, idx_base)
+        return s.cpu(), i.cpu()
+    return host[:m].view(torch.float32).view(shape), host[m: 2 * m].view(shape)
+
+
 def topk_merge(scores: torch.Tensor, idx: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Merge candidate lists [Q, M] (fp32 scores, int32 global indices, idx<0 =
     padding) into the top-k by (score desc, idx asc)."""

@@ -89,5 +89,45 @@ except Exception:  # noqa: BLE001
             return self.custom_embedding_strs or [self.query_str]
 
 
+try:  # pragma: no cover - llama_index is absent in the build container
+    from llama_index.core.vector_stores.types import (  # type: ignore
+        FilterCondition,
+        FilterOperator,
+        MetadataFilter,
+        MetadataFilters,
+    )
+except Exception:  # noqa: BLE001
+    from enum import Enum
+
+    class FilterOperator(str, Enum):
+        """The ten operators of the reference's filter specs (rag_engine.py:286-297), with llama-index's values."""
+
+        EQ = "=="
+        NE = "!="
+        GT = ">"
+        GTE = ">="
+        LT = "<"
+        LTE = "<="
+        IN = "in"
+        NIN = "nin"
+        CONTAINS = "contains"
+        TEXT_MATCH = "text_match"
+
+    class FilterCondition(str, Enum):
+        AND = "and"
+        OR = "or"
+
+    @dataclass
+    class MetadataFilter:
+        key: str
+        value: Any
+        operator: FilterOperator = FilterOperator.EQ
+
+    @dataclass
+    class MetadataFilters:
+        filters: List[Any] = field(default_factory=list)      # MetadataFilter (a nested MetadataFilters is refused by the search)
+        condition: FilterCondition = FilterCondition.AND
+
+
 def as_query_bundle(q) -> "QueryBundle":
     return q if hasattr(q, "query_str") else QueryBundle(query_str=str(q))

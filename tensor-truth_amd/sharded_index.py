@@ -232,8 +232,10 @@ class ShardedHipVectorIndex:
         q = query_emb.to(self.device, dtype=torch.float32)
         return (q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)).to(torch.bfloat16).contiguous()
 
-    def search(self, query_emb: torch.Tensor, k: int):
+    def search(self, query_emb: torch.Tensor, k: int, filters=None):
         """query_emb [Q, D] (this rank's queries) -> (cosine scores [Q, k] fp32, GLOBAL rows [Q, k] int32) for them."""
+        if filters is not None:
+            raise NotImplementedError("metadata filters are not supported on a row-sharded index")
         q16 = self._unit_bf16(query_emb)
         world, rank = _world(self.group)
         if world == 1:
@@ -275,6 +277,8 @@ class ShardedHipVectorIndex:
         collective rounds in lock step, so coalescing stays on and each rank embeds (and, above this retriever, reranks)
         only ITS OWN callers' queries: N GPUs serve N times the queries, not N copies of the same ones.
         ``queries="replicated"`` keeps one collective round per call (the front end hands every rank the same request)."""
+        if _kw.get("filters") is not None:
+            raise NotImplementedError("metadata filters are not supported on a row-sharded index")
         if self.leaf_ids is None or self.docstore is None:
             raise ValueError("this ShardedHipVectorIndex was built without node tables (search-only)")
         world, _ = _world(self.group)

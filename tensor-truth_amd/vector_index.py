@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from . import scan as _scan
+from . import metadata_filter as _mf
 from .coalesce import Coalescer
 from .schema import MetadataMode, NodeWithScore, TextNode, as_query_bundle
 
@@ -74,6 +75,12 @@ class HipVectorIndex:
         # on the next search) when rows are rewritten in place or the matrix is replaced.  + 50 % of the matrix's HBM; TT_SCAN_SHADOW=0: off
         self.fp8_shadow = os.environ.get("TT_SCAN_SHADOW", "1") != "0"
         self._shadow = None
+        # metadata-filter code columns (metadata_filter.CodeColumn), one per key, built on the first filtered search that names the key
+        # and kept in step with the matrix (add appends, _reserve grows, _compact replaces).  _generation numbers the row order:
+        # bumped whenever rows are renumbered (compaction), and carried by every snapshot() so that a snapshot taken before a
+        # compaction is never handed the renumbered columns
+        self._cols: Dict[str, _mf.CodeColumn] = {}
+        self._generation = 0
 
     def _mark_written(self) -> None:
         """Searches may run on another stream than the one that wrote the matrix (the retrievers' own stream, below):
@@ -90,6 +97,8 @@ class HipVectorIndex:
             grown = torch.empty((cap, self.dim), dtype=torch.bfloat16, device=self.device)
             grown[: self.n] = self._mat[: self.n]
             self._mat = grown
+            for col in self._cols.values():
+                col.reserve(cap)
 
     def add(self, nodes: Sequence[TextNode], embeddings=None, show_progress: bool = False, token_ids=None) -> List[str]:
         """Insert leaf nodes (embedding them with ``embed_model`` unless ``embeddings`` is given).
@@ -117,6 +126,8 @@ class HipVectorIndex:
         with self._lock:
             self._reserve(len(nodes))
             self._mat[self.n:self.n + len(nodes)] = emb.to(torch.bfloat16)
+            for key, col in self._cols.items():
+                col.append(_mf.VOCAB.key(key).codes(_mf.metadata_values({nd.id_: nd for nd in nodes}, [nd.id_ for nd in nodes], key)))
             self._mark_written()
             for j, nd in enumerate(nodes):
                 self.leaf_ids.append(nd.id_)
@@ -210,6 +221,10 @@ class HipVectorIndex:
             idx = torch.tensor(keep, dtype=torch.long, device=self.device)
             self._mat = self._mat[: self.n].index_select(0, idx) if keep else torch.empty(
                 (0, self.dim), dtype=torch.bfloat16, device=self.device)
+            # code columns: copy-on-write with the same keep list (a snapshot of the old generation keeps the old tensors)
+            self._cols = {key: _mf.CodeColumn.from_device(key, self.device, col.dev[: self.n].index_select(0, idx))
+                          for key, col in self._cols.items()}
+            self._generation += 1
             self._mark_written()
             self.leaf_ids = [self.leaf_ids[i] for i in keep]
             self.n, self._dead, self._row_of = len(keep), 0, None
@@ -231,7 +246,36 @@ class HipVectorIndex:
         caller holds it -- the scan and the row -> node mapping run WITHOUT the index lock, and the reference's
         eight retriever threads (rag_engine.py:392,420) search one index concurrently."""
         with self._lock:
-            return self._mat[: self.n], self.leaf_ids
+            return _Snapshot((self._mat[: self.n], self.leaf_ids), self._generation)
+
+    def _column(self, key: str, snapshot=None) -> "_mf.CodeColumn":
+        """The code column of ``key`` for the rows of ``snapshot`` (default: the current rows): the index's own column when the
+        snapshot is of the current generation (built from the leaves' metadata on first use), else a one-off column built from
+        the snapshot's own row -> id list."""
+        with self._lock:
+            rows = self.n if snapshot is None else int(snapshot[0].shape[0])
+            gen = getattr(snapshot, "generation", None) if snapshot is not None else self._generation
+            if gen == self._generation and rows <= self.n:
+                col = self._cols.get(key)
+                if col is None:
+                    codes = _mf.VOCAB.key(key).codes(_mf.metadata_values(self.docstore, self.leaf_ids[: self.n], key))
+                    col = self._cols[key] = _mf.CodeColumn(key, self.device, codes, cap=self._mat.shape[0])
+                return col
+            ids = list(snapshot[1][:rows])
+            docstore = self.docstore
+        if len(ids) < rows:
+            raise ValueError(f"snapshot holds {rows} rows but {len(ids)} leaf ids")
+        codes = _mf.VOCAB.key(key).codes(_mf.metadata_values(docstore, ids, key))
+        return _mf.CodeColumn(key, self.device, codes)
+
+    def _filtered(self, snap, q16: torch.Tensor, k: int, filters, host: bool):
+        """Exact top-k over the rows of ``snap`` that pass ``filters``: one tt_filter_rows, one tt_scan_topk_rows."""
+        mat = snap[0]
+        cf = _mf.compile_filter(filters, lambda key: self._column(key, snap), mat.shape[0], self.device)
+        rows, offs = _scan.filter_rows(cf, mat.shape[0], self.device)
+        if host:
+            return _scan.scan_topk_rows_host(mat, q16, k, rows, offs, cf.bound)
+        return _scan.scan_topk_rows(mat, q16, k, rows, offs, cf.bound)
 
     def _unit_bf16(self, query_emb: torch.Tensor) -> torch.Tensor:
         q = query_emb.to(self.device, dtype=torch.float32)
@@ -256,22 +300,33 @@ class HipVectorIndex:
                 sh.extend(self._mat, self.n)                     # rows appended since
             return sh if sh.rows >= mat.shape[0] else None
 
-    def search(self, query_emb: torch.Tensor, k: int, snapshot=None):
-        """query_emb fp32/bf16 [Q, D] -> (scores [Q,k] fp32 cosine, rows [Q,k] int32)."""
-        mat, _ = snapshot if snapshot is not None else self.snapshot()
+    def search(self, query_emb: torch.Tensor, k: int, snapshot=None, filters=None):
+        """query_emb fp32/bf16 [Q, D] -> (scores [Q,k] fp32 cosine, rows [Q,k] int32).
+        ``filters`` (a ``MetadataFilters``, see metadata_filter.py): the exact top-k over the matching rows only, padded with
+        (-inf, -1) when fewer than k rows match; filtered searches never use the fp8 shadow."""
+        snap = snapshot if snapshot is not None else self.snapshot()
+        mat = snap[0]
+        if _mf.filter_key(filters) is not None:
+            return self._filtered(snap, self._unit_bf16(query_emb), k, filters, host=False)
         return _scan.scan_topk(mat, self._unit_bf16(query_emb), k, shadow=self._shadow_for(mat, query_emb.shape[0]))
 
-    def search_host(self, query_emb: torch.Tensor, k: int, snapshot=None):
+    def search_host(self, query_emb: torch.Tensor, k: int, snapshot=None, filters=None):
         """``search`` with the hits on the host (CPU tensors): one copy back, one sync per scan batch (``scan.scan_topk_host``)."""
-        mat, _ = snapshot if snapshot is not None else self.snapshot()
+        snap = snapshot if snapshot is not None else self.snapshot()
+        mat = snap[0]
+        if _mf.filter_key(filters) is not None:
+            return self._filtered(snap, self._unit_bf16(query_emb), k, filters, host=True)
         return _scan.scan_topk_host(mat, self._unit_bf16(query_emb), k, shadow=self._shadow_for(mat, query_emb.shape[0]))
 
     def node_score(self, cos: float) -> float:
         return math.exp(-(2.0 - 2.0 * cos)) if self.score_mode == "chroma" else cos
 
     def as_retriever(self, similarity_top_k: int = 10, coalesce: bool = True, max_batch: int = 64,
-                     max_wait_s: float = 0.0, **_kw) -> "HipVectorRetriever":
-        return HipVectorRetriever(self, similarity_top_k, coalesce=coalesce, max_batch=max_batch, max_wait_s=max_wait_s)
+                     max_wait_s: float = 0.0, filters=None, **_kw) -> "HipVectorRetriever":
+        """``filters``: a ``MetadataFilters`` (``metadata_filter.build_metadata_filters`` turns the reference's filter specs into
+        one) every search of the retriever applies."""
+        return HipVectorRetriever(self, similarity_top_k, coalesce=coalesce, max_batch=max_batch, max_wait_s=max_wait_s,
+                                  filters=filters)
 
     # ---- persistence ---------------------------------------------------------------------------------
     def persist(self, persist_dir: str, embedding_model: Optional[str] = None, chunk_sizes=None,
@@ -384,6 +439,15 @@ class HipVectorIndex:
                     idx.leaf_token_ids = {nid: flat[e - n:e] for nid, e, n in zip(idx.leaf_ids, ends, lens) if n > 0 and nid is not None}
                     idx.leaf_token_origin = (sig, instr)
         return idx
+
+
+class _Snapshot(tuple):
+    """(matrix view, leaf_ids) as ``snapshot()`` returns it, plus the row-order generation it was taken in."""
+
+    def __new__(cls, pair, generation: int):
+        t = super().__new__(cls, pair)
+        t.generation = generation
+        return t
 
 
 _LINK_KEYS = ("parent_id", "child_ids", "prev_id", "next_id")
@@ -531,9 +595,13 @@ class HipVectorRetriever:
     depend on the batch a query travels in (tests/test_coalesce_gpu.py)."""
 
     def __init__(self, index: HipVectorIndex, similarity_top_k: int = 10, coalesce: bool = True, max_batch: int = 64,
-                 max_wait_s: float = 0.0):
+                 max_wait_s: float = 0.0, filters=None):
         self.index = index
         self.similarity_top_k = similarity_top_k
+        # metadata filters of every search (llama-index: a property of the retriever, so one coalesced batch shares one filter
+        # and one row list); ValueError here for nested filters / unknown operators
+        self.filters = filters
+        self.filter_key = _mf.filter_key(filters)
         self._front = Coalescer(self._retrieve_batch, max_batch, max_wait_s) if coalesce else None
         self._stream: Optional[torch.cuda.Stream] = None
 
@@ -609,15 +677,16 @@ class HipVectorRetriever:
         if k < 1:
             return [[] for _ in bundles]
         stream = self._gpu_stream()
+        fkw = {} if self.filter_key is None else {"filters": self.filters}
         if stream is None:
-            scores, rows = idx.search_host(self._query_matrix(bundles), k, snapshot=snap)
+            scores, rows = idx.search_host(self._query_matrix(bundles), k, snapshot=snap, **fkw)
             scores, rows = scores.tolist(), rows.tolist()
         else:
             written = getattr(idx, "_written", None)        # (read after the snapshot: covers every row the snapshot holds)
             with torch.cuda.stream(stream):
                 if written is not None:
                     stream.wait_event(written)
-                scores, rows = idx.search_host(self._query_matrix(bundles), k, snapshot=snap)     # waits for THIS stream only
+                scores, rows = idx.search_host(self._query_matrix(bundles), k, snapshot=snap, **fkw)     # waits for THIS stream only
                 scores, rows = scores.tolist(), rows.tolist()
         return [self.nodes_from_hits(s, r, leaf_ids) for s, r in zip(scores, rows)]
 
@@ -669,6 +738,7 @@ class HipIndexGroup:
         # <= 4 queries then take one exact-prefilter pass per module instead of the dense segmented pass -- same bits, half the bytes
         self.fp8_shadow = os.environ.get("TT_SCAN_SHADOW", "1") != "0"
         self._seg_shadows: Dict[int, object] = {}
+        self._packed_cols: Dict[str, object] = {}   # metadata-filter code columns of this packing: the modules' columns concatenated
 
     def _pack(self) -> None:
         for ix in self.indexes:
@@ -690,6 +760,7 @@ class HipIndexGroup:
             self._mat, self.offsets, self._stamp = mat, offs, stamp
             self._leaf_ids = [ix.leaf_ids for ix in self.indexes]
             self._seg_shadows = {}               # (they mirrored the previous packing)
+            self._packed_cols = {}
         finally:
             for ix in self.indexes:
                 ix._lock.release()
@@ -735,12 +806,50 @@ class HipIndexGroup:
             s[:, m], r[:, m] = es.to(s.device), er.to(r.device)
         return s, r
 
-    def search(self, query_emb: torch.Tensor, k: int, return_snapshot: bool = False):
+    def _packed_column(self, key: str):
+        """(group lock and every member's lock held, packing current) the modules' code columns concatenated: codes are
+        process-wide, so no remapping."""
+        col = self._packed_cols.get(key)
+        if col is None:
+            parts = [ix._column(key) for ix in self.indexes]
+            codes = torch.cat([c.dev[: ix.n] for c, ix in zip(parts, self.indexes)]) if self.indexes else None
+            width = max(len(c.counts) for c in parts)
+            counts = np.zeros(width, np.int64)
+            for c in parts:
+                counts[: len(c.counts)] += c.counts
+            col = self._packed_cols[key] = _mf.CodeColumn.from_device(key, self.device, codes, counts)
+        return col
+
+    def _filtered_search(self, q: torch.Tensor, k: int, filters, host: bool):
+        """One tt_filter_rows over the packed code columns with the module offsets, one segmented tt_scan_topk_rows."""
+        with self._lock:
+            self._pack()
+            for ix in self.indexes:
+                ix._lock.acquire()
+            try:
+                if tuple((ix._version, ix.n) for ix in self.indexes) != self._stamp:
+                    self._pack()
+                mat, offs, ids = self._mat, list(self.offsets), list(self._leaf_ids)
+                cf = _mf.compile_filter(filters, self._packed_column, offs[-1], self.device)
+            finally:
+                for ix in self.indexes:
+                    ix._lock.release()
+        rows, loff = _scan.filter_rows(cf, mat.shape[0], self.device, seg_offsets=offs)
+        if host:
+            s, r = _scan.scan_topk_rows_host(mat, q, k, rows, loff, cf.bound, seg_offsets=offs)
+        else:
+            s, r = _scan.scan_topk_rows(mat, q, k, rows, loff, cf.bound, seg_offsets=offs)
+        return s, r, ids
+
+    def search(self, query_emb: torch.Tensor, k: int, return_snapshot: bool = False, filters=None):
         """query_emb [Q, D] -> (cosine scores [Q, S, k] fp32, module-local rows [Q, S, k] int32); with
         ``return_snapshot`` also the per-module row -> id lists of the matrix that was scanned.  The scan runs
         outside the group lock on a snapshot (matrix, offsets, id lists) taken under it."""
         q = query_emb.to(self.device, dtype=torch.float32)
         q = (q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)).to(torch.bfloat16).contiguous()
+        if _mf.filter_key(filters) is not None:
+            s, r, ids = self._filtered_search(q, k, filters, host=False)
+            return (s, r, ids) if return_snapshot else (s, r)
         mat, offs, ids, shadows = self._snapshot_for(q, k)
         if shadows is None:
             s, r = _scan.scan_topk_segmented(mat, q, k, offs)
@@ -748,11 +857,13 @@ class HipIndexGroup:
             s, r = self._unpack_modules(self._scan_modules(mat, offs, q, k, shadows), mat, offs, q, k)
         return (s, r, ids) if return_snapshot else (s, r)
 
-    def search_host(self, query_emb: torch.Tensor, k: int):
+    def search_host(self, query_emb: torch.Tensor, k: int, filters=None):
         """``search`` with the hits on the host (the retriever turns rows into nodes): -> (scores [Q, S, k], rows [Q, S, k], id lists),
         CPU tensors.  The per-module passes come back in ONE copy, which is the only host sync of the call."""
         q = query_emb.to(self.device, dtype=torch.float32)
         q = (q / q.norm(dim=1, keepdim=True).clamp_min(1e-12)).to(torch.bfloat16).contiguous()
+        if _mf.filter_key(filters) is not None:
+            return self._filtered_search(q, k, filters, host=True)
         mat, offs, ids, shadows = self._snapshot_for(q, k)
         if shadows is None:
             s, r = _scan.scan_topk_segmented(mat, q, k, offs)
