@@ -12,6 +12,11 @@ weights) or host token arrays (what the reference's tokenizer would hand over).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  `--full` adds
+everything measured beside the headline -- the instrumented per-stage step, the scan-only, fp8, reference-precision,
+fp16, ingest, plugin-surface, reference-defaults and config-5 legs and the CPU baseline (each of which the --no-* switches
+still turn off) -- and fills the fields of the line that report them; without it those fields are null.
+
 Prints ONE JSON line on rank 0 (see the driver contract in the task description).
 """
 from __future__ import annotations
@@ -203,11 +208,14 @@ def parse():
     ap.add_argument("--query-len", type=int, default=32)
     ap.add_argument("--chunk-len", type=int, default=256)
     ap.add_argument("--embed-chunks", type=int, default=1024, help="chunks per GPU in the ingest (chunks embedded/s) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what is measured beside it: the per-stage step, the side legs and the CPU "
+                         "baseline (the --no-* switches and --headline-only below choose among them; a plain run does none)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-surface-leg", action="store_true", help="skip the plugin-surface leg (32 request threads through retrieve() / postprocess_nodes())")
     ap.add_argument("--surface-leg", action="store_true",
-                    help="world > 1: run the plugin-surface leg too (off by default there until it has run over RCCL on a real multi-GPU box: "
-                         "its collectives are issued from the retriever's tick thread, under a deadline)")
+                    help="world > 1, with --full: run the plugin-surface leg too (off by default there until it has run over RCCL on a real "
+                         "multi-GPU box: its collectives are issued from the retriever's tick thread, under a deadline)")
     ap.add_argument("--no-config5-leg", action="store_true", help="skip the composed BASELINE config 5 leg (semantic-hierarchical ingest + auto-merging retrieval + fp8 reranker)")
     ap.add_argument("--surface-threads", type=int, default=32)
     ap.add_argument("--surface-queries", type=int, default=256, help="queries the surface leg issues in all (N=1 only)")
@@ -223,15 +231,19 @@ def parse():
     ap.add_argument("--surface-timeout", type=float, default=300.0,
                     help="world > 1: deadline of the plugin-surface leg in seconds (the headline is printed regardless)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="run only the warm-up and timed steps (no scan-only / fp8 / ingest legs): every kernel of the process then "
-                         "belongs to the timed workload, so a rocprofv3 --stats summary of this command can be compared with "
-                         "roofline.avg_launch_ms directly (tools/rocprof_vs_bench.py)")
+                    help="with --full: no side legs, only the per-stage step after the timed ones; every kernel of the process then "
+                         "belongs to steps of the timed workload's shape, so a rocprofv3 --stats summary of this command can be "
+                         "compared with roofline.avg_launch_ms directly (tools/rocprof_vs_bench.py).  A plain run (no --full) is "
+                         "headline-only already, without the per-stage step")
     ap.add_argument("--layers", type=int, default=24, help="encoder depth (24 = the named models; for debugging only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned -- top_scores.npy (float32) and top_rows.npy "
                          "(float64), queries x top-n, a few KiB -- into DIR (world > 1: one pair per rank, suffixed _rank<r>); the "
                          "inputs are seeded, so two builds run with the same arguments can be compared output for output")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.surface_leg and not args.full:
+        ap.error("--surface-leg is a leg beside the headline: it runs with --full")
+    return args
 
 
 def csrc_sha256() -> str:
@@ -494,15 +506,18 @@ def main():
     lib.tt_prof_enable(0)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, last, rank if world > 1 else None)
-    # one more, untimed, step with every kernel family instrumented: the per-stage table
-    lib.tt_prof_enable(1)
-    step(queries[-1])
-    sync_all()
-    stage_prof = read_prof()
-    lib.tt_prof_enable(0)
+    # --full: one more, untimed, step with every kernel family instrumented: the per-stage table
+    stage_prof = None
+    if args.full:
+        lib.tt_prof_enable(1)
+        step(queries[-1])
+        sync_all()
+        stage_prof = read_prof()
+        lib.tt_prof_enable(0)
+    legs = args.full and not args.headline_only     # the side legs below, each still subject to its --no-* switch
 
     scan_only = None
-    if not args.headline_only:
+    if legs:
         # ---- the similarity scan alone (BASELINE configs 2 / 4): 256 resident query embeddings (256 / world per GPU, gathered)
         # against the sharded corpus
         nq_scan = max(1, 256 // world)
@@ -533,7 +548,7 @@ def main():
     # shard of corpus_rows / 8 rows (10M / 8 = 1.25M): sample + threshold select + tiled filter pass + tail + final select,
     # per-stage device times from HIP events, and the whole batch as a fraction of the HBM roofline on ALGORITHMIC bytes
     scan_shard = None
-    if world == 1 and not args.headline_only and (hi - lo) >= args.corpus_rows // 8 >= 262144:
+    if world == 1 and legs and (hi - lo) >= args.corpus_rows // 8 >= 262144:
         rows8 = args.corpus_rows // 8
         shard8 = shard_rows[:rows8]
         q8 = torch.nn.functional.normalize(torch.randn(256, D, device=dev, generator=torch.Generator(device=dev).manual_seed(4322)), dim=1).to(torch.bfloat16)
@@ -580,7 +595,7 @@ def main():
     # ---- BASELINE config 5's "fp8 MFMA reranker": the same steps with the cross-encoder's Q/K/V and FFN-up
     # projections on e4m3 operands.  Reported beside the headline (which stays bf16), never as it.
     fp8_leg = None
-    if not args.no_fp8_leg and not args.headline_only:
+    if legs and not args.no_fp8_leg:
         # static scale of the FFN intermediate per layer: one bf16 calibration forward over 64 synthetic pairs
         cal = rng.integers(4, vocab, size=(64, args.query_len + args.chunk_len + 4), dtype=np.int32)
         cal[:, 0], cal[:, -1] = 0, 2
@@ -619,7 +634,7 @@ def main():
     # faster variant with a stated stress bound.  Fresh UNROUNDED fp32 weights (their lo / correction planes are not zero: zero
     # operands would flatter the clock).  Reported beside the headline, never as it.
     reference_leg = None
-    if not args.no_reference_leg and not args.headline_only:
+    if legs and not args.no_reference_leg:
         from tensor_truth_amd.encoder_f16c import EncoderF16C, EncoderWeightsF16C
         from tensor_truth_amd.encoder_x3 import EncoderWeightsX3, EncoderX3
 
@@ -674,7 +689,7 @@ def main():
     # fp16 elements and v_mfma_*_f16 -- the bf16 rate, scores several times closer to the reference.  A labelled variant
     # beside the headline (BASELINE's configurations name bf16), never the headline.
     fp16_leg = None
-    if not args.no_fp16_leg and not args.headline_only:
+    if legs and not args.no_fp16_leg:
         quality16 = None
         if rank == 0:
             quality16 = rank_quality(reranker, rr_cfg, tokens_step["last_pairs"][: 4 * K], K, topn, dev, modes=("bf16", "fp16"))
@@ -707,7 +722,7 @@ def main():
                     "score_quality_vs_fp32_path": quality16}
 
     chunks_per_s, roofline_embed = None, None
-    if not args.headline_only:
+    if legs:
         # ---- second half of the BASELINE metric: batch chunk embedding (ingest), separately timed ----
         chunk_tok = rng.integers(4, vocab, size=(args.embed_chunks, args.chunk_len), dtype=np.int32)
         chunk_seqs = [np.concatenate(([0], c, [2])) for c in chunk_tok]
@@ -764,7 +779,7 @@ def main():
     # merges them into shared embed / scan / rerank batches.  Strings in, NodeWithScore out; the SAME resident corpus.
     surface = None
     hard_exit = comm_hung        # (a pre-flight thread still sits in an RCCL call: leave without destroying the groups)
-    if not args.headline_only and not args.no_surface_leg and (world == 1 or args.surface_leg):
+    if legs and not args.no_surface_leg and (world == 1 or args.surface_leg):
         if world == 1:
             # (optional blocks: one that throws is reported under its own key, the headline line is printed regardless)
             def _optional(fn):
@@ -830,13 +845,13 @@ def main():
                 surface["surface_failed"] = True
                 hard_exit = True
     reference_defaults = None
-    if not args.headline_only and not args.no_surface_leg and world == 1 and not args.no_reference_defaults_leg:
+    if legs and not args.no_surface_leg and world == 1 and not args.no_reference_defaults_leg:
         try:
             reference_defaults = reference_defaults_leg(args, dev, shard_rows, emb_cfg, rr_cfg)
         except Exception as exc:  # noqa: BLE001 - an optional block: the headline line is printed regardless
             reference_defaults = {"error": f"{type(exc).__name__}: {exc}"[:300]}
     config5 = None
-    if world == 1 and not args.headline_only and not args.no_config5_leg:
+    if world == 1 and legs and not args.no_config5_leg:
         try:
             config5 = config5_leg(args, dev, emb_cfg, rr_cfg)
         except Exception as exc:  # noqa: BLE001 - an optional block, as above
@@ -985,9 +1000,9 @@ def main():
             "algorithmic_bytes_per_launch": scan_bytes, "queries_per_launch": Bq * world, "reread_factor": q_tiles,
         },
         "roofline_embed": roofline_embed,
-        "stage_ms_per_step": {k: v[0] for k, v in stage_prof.items()},
+        "stage_ms_per_step": {k: v[0] for k, v in stage_prof.items()} if stage_prof is not None else None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, emb_cfg, rr_cfg, embedder, reranker, corpus, queries[0], vocab)
     if rank == 0:
         print(json.dumps(out))

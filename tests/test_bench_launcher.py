@@ -6,6 +6,8 @@ import subprocess
 import sys
 import textwrap
 
+import pytest
+
 import bench
 
 
@@ -176,3 +178,20 @@ def test_clock_sampler_degrades_to_nulls_without_a_driver():
     assert set(got) >= {"sclk_mhz_median", "sclk_mhz_spec", "socket_power_w_mean", "power_cap_w", "samples", "error"}
     if got["samples"] == 0:
         assert got["sclk_mhz_median"] is None and got["socket_power_w_mean"] is None and got["error"]
+
+
+def test_side_legs_are_opt_in_with_full(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs only what its headline needs; the per-stage step, the side legs and
+    the CPU baseline run with --full, where the --no-* switches still choose among them.  --surface-leg asks for a side leg:
+    without --full it is refused rather than silently ignored."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-fp8-leg", "--headline-only"])
+    a = bench.parse()
+    assert a.full and a.no_fp8_leg and a.headline_only
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full", "--surface-leg"])
+    assert bench.parse().surface_leg
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--surface-leg"])
+    with pytest.raises(SystemExit):
+        bench.parse()

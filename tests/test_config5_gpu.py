@@ -9,7 +9,7 @@ auto-merging retrieval -> fp8 MFMA reranker -- through the same entry points the
   D. fp8 cross-encoder scores -> final top-n ids: rank agreement with the fp32 oracle.
 
 Small model shapes (2 layers) keep the oracle in seconds; every kernel and every host path is the one the full-size
-run takes (the full-size timing of this workload is ``bench.py``'s ``config5`` leg)."""
+run takes (the full-size timing of this workload is ``bench.py --full``'s ``config5`` leg)."""
 import math
 
 import numpy as np

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 export TT_LIB_NAME=libtt_hip_diag.so
 for rep in 1 2; do
   for x in 0 1; do
-    TT_ATT_XCD=$x timeout 600 python bench.py --headline-only --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
+    TT_ATT_XCD=$x timeout 600 python bench.py --full --headline-only --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); s=d['stage_ms_per_step']
 print('TT_ATT_XCD=$x  %.1f q/s  step %.1f ms  attention %.2f ms  gemm %.1f ms  clock %s MHz' % (d['value'], d['ms_per_step'], s['attention'], s['gemm'], d['roofline']['clock']['sclk_mhz_median']))"

@@ -1,13 +1,15 @@
 #!/bin/bash
 # The bench with the reference-precision leg only (+ headline): stage split of the f16c step.
 cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}       # where the outputs go
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout 900 python bench.py --no-cpu-baseline --no-surface-leg --no-config5-leg --no-fp8-leg --no-fp16-leg ${BENCH_ARGS} > gpurun_out/bench_ref.json 2> gpurun_out/bench_ref.err
-tail -3 gpurun_out/bench_ref.err
-python - <<'PY'
+timeout 900 python bench.py --full --no-cpu-baseline --no-surface-leg --no-config5-leg --no-fp8-leg --no-fp16-leg ${BENCH_ARGS} > "$OUT"/bench_ref.json 2> "$OUT"/bench_ref.err
+tail -3 "$OUT"/bench_ref.err
+OUT=$OUT python - <<'PY'
 import json
-j = json.load(open("gpurun_out/bench_ref.json"))
+import os
+j = json.load(open(os.environ["OUT"] + "/bench_ref.json"))
 c = j["config"]
 print("headline", j["value"], "ms/step", j["ms_per_step"], "stage", j["stage_ms_per_step"])
 r = c["reference_precision"]

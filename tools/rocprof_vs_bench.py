@@ -3,8 +3,8 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 bench.py --headline-only ... > bench.json
     python tools/rocprof_vs_bench.py DIR/**/*kernel_stats.csv bench.json
 
-With --headline-only every kernel of the process belongs to warm-up / timed / instrumented steps of the SAME shape, so
-rocprof's per-kernel averages are averages over identical steps.  Compared: the GEMM family (all gemm_* kernels: calls
+With --headline-only every kernel of the process belongs to warm-up / timed steps (with --full, + the instrumented
+per-stage step) of the SAME shape, so rocprof's per-kernel averages are averages over identical steps.  Compared: the GEMM family (all gemm_* kernels: calls
 and total duration -> average launch) with roofline.avg_launch_ms, and the scan filter kernel with
 roofline_scan.avg_launch_ms."""
 import csv
@@ -28,7 +28,7 @@ def main():
             elif "scan_kernel<" in name and ", 0, 0>" in name:      # OUT = 0: the filter pass
                 scan_calls += calls
                 scan_ns += tot
-    steps_total = bench["steps"] + bench["warmup"] + 1                # + the untimed instrumented step
+    steps_total = bench["steps"] + bench["warmup"] + (bench.get("stage_ms_per_step") is not None)   # + the per-stage step (--full)
     out = []
     out.append(f"bench.py --headline-only: {bench['value']:.1f} {bench['unit']}, {bench['ms_per_step']:.1f} ms/step, "
                f"{steps_total} identical steps in the process")
