@@ -6,12 +6,18 @@ Mirrors what the reference obtains from ``HuggingFaceEmbedding`` (built at
 ``src/tensortruth/services/model_manager.py:254-260``) and ``SentenceTransformerRerank``
 (``model_manager.py:333-337``): XLM-R / BERT encoder forward -> CLS pooling + L2
 normalisation (embeddings), or -> classification head + sigmoid (rerank scores).
-Computation is bf16 with fp32 accumulation (the reference's ``torch_dtype: bfloat16``
-option, ``model_manager.py:218-229``); there is no CPU path.
+There is no CPU path.
+
+``Encoder`` drives every precision: the weights object it is given names its path through the library as an
+``EncoderPath`` record.  The 16-bit path is here (``EncoderWeights``: bf16 with fp32 accumulation, the reference's
+``torch_dtype: bfloat16`` option, ``model_manager.py:218-229``; or fp16); the reference-precision paths keep their weight
+classes in ``encoder_x3`` (split planes), ``encoder_f16c`` and ``encoder_f32``, all built by the one checkpoint walk of
+``_CheckpointWeights``.
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import itertools
 import os
 import threading
@@ -67,22 +73,67 @@ KNOWN_CONFIGS = {
 }
 
 
+# the twelve tensors of a layer, in the order tt_layer_weights, tt_layer_weights_f32 and tt_layer_weights_x3 of
+# include/tt_hip.h start with them (tt_layer_weights_f16c interleaves block-scale pointers: encoder_f16c._LayerWC)
+_LAYER_FIELDS = ("qkv_w", "qkv_b", "o_w", "o_b", "ln1_g", "ln1_b", "ffn1_w", "ffn1_b", "ffn2_w", "ffn2_b", "ln2_g", "ln2_b")
+
+
 class _LayerW(Structure):
-    _fields_ = [(n, c_void_p) for n in ("qkv_w", "qkv_b", "o_w", "o_b", "ln1_g", "ln1_b", "ffn1_w", "ffn1_b",
-                                        "ffn2_w", "ffn2_b", "ln2_g", "ln2_b",
-                                        "qkv_w8", "qkv_wscale", "ffn1_w8", "ffn1_wscale",
-                                        "o_w8", "o_wscale", "ffn2_w8", "ffn2_wscale")] + [("ffn_act_scale", c_float)]
+    """tt_layer_weights: the layer's tensors, then the fp8 operands of its projections (``set_gemm_dtype("fp8")``)."""
+    _fields_ = [(n, c_void_p) for n in _LAYER_FIELDS + ("qkv_w8", "qkv_wscale", "ffn1_w8", "ffn1_wscale",
+                                                         "o_w8", "o_wscale", "ffn2_w8", "ffn2_wscale")] + [("ffn_act_scale", c_float)]
 
 
-class _EncW(Structure):
-    _fields_ = [
-        ("hidden", c_int32), ("layers", c_int32), ("heads", c_int32), ("ffn", c_int32), ("vocab", c_int32),
-        ("max_pos", c_int32), ("type_vocab", c_int32), ("ln_eps", c_float),
-        ("word_emb", c_void_p), ("pos_emb", c_void_p), ("type_emb", c_void_p), ("emb_ln_g", c_void_p),
-        ("emb_ln_b", c_void_p), ("layer", POINTER(_LayerW)),
-        ("cls_dense_w", c_void_p), ("cls_dense_b", c_void_p), ("cls_out_w", c_void_p), ("cls_out_b", c_void_p),
-        ("ffn_absmax_out", c_void_p),
-    ]
+class _PlainLayerW(Structure):
+    """tt_layer_weights_f32 and tt_layer_weights_x3: the layer's tensors and nothing else."""
+    _fields_ = [(n, c_void_p) for n in _LAYER_FIELDS]
+
+
+def _weights_struct(name: str, layer: type, *extra) -> type:
+    """ctypes mirror of one of the tt_encoder_weights* structs: the header they share, with a ``layer`` array of ``layer``
+    structs, then ``extra`` fields.  The struct type's ``layer_type`` is ``layer``."""
+    fields = ([(n, c_int32) for n in ("hidden", "layers", "heads", "ffn", "vocab", "max_pos", "type_vocab")] + [("ln_eps", c_float)]
+              + [(n, c_void_p) for n in ("word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b")] + [("layer", POINTER(layer))]
+              + [(n, c_void_p) for n in ("cls_dense_w", "cls_dense_b", "cls_out_w", "cls_out_b")] + list(extra))
+    return type(name, (Structure,), {"_fields_": fields, "layer_type": layer})
+
+
+_EncW = _weights_struct("_EncW", _LayerW, ("ffn_absmax_out", c_void_p))
+
+
+@dataclass(frozen=True, kw_only=True)
+class EncoderPath:
+    """What a weights class tells ``Encoder`` about its path through libtt_hip.so: the entry points, the ``_scratch`` keys of
+    their workspaces, the element type of the hidden states and how a batch's rows are padded.
+
+    ``row_tile``: the path's GEMMs run whole tiles of this many rows, so a batch's rows are rounded up to a multiple of it (0:
+    the rows as packed).  ``skinny``: up to 256 rows in multiples of 64 are kept (weight-streaming skinny GEMMs), and the
+    CLS-only output is padded to 64 rows up to 256 sequences; otherwise that output is padded to 256 rows."""
+
+    forward: str                 # the whole forward, and its workspace size
+    workspace: str
+    cls_forward: Optional[str]   # the last layer for the CLS rows only, and its workspace size; None: pooling and the head
+    cls_workspace: Optional[str]  # read the full forward's hidden states at the sequence starts
+    pool: str                    # CLS and mean pooling
+    pool_mean: str
+    head: str                    # classification head; its workspace holds two padded [B, H] tiles of hidden-state elements
+    scratch: str                 # _scratch keys of the forward's and the head's workspaces
+    head_scratch: str
+    hidden: torch.dtype          # element type of the hidden states
+    row_tile: int = 0
+    skinny: bool = False
+    pool_writes_bf16: bool = True  # the pooling kernel writes the bf16 copy of an embedding (else it is rounded from fp32 here)
+    no_fp8: Optional[str] = None   # why ``calibrate_fp8`` does not apply; None: it does
+
+
+BF16_PATH = EncoderPath(forward="tt_encoder_forward", workspace="tt_encoder_workspace_bytes",
+                        cls_forward="tt_encoder_forward_cls", cls_workspace="tt_encoder_cls_workspace_bytes",
+                        pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head="tt_rerank_head",
+                        scratch="enc", head_scratch="head", hidden=torch.bfloat16)
+FP16_PATH = EncoderPath(forward="tt_encoder_forward_f16", workspace="tt_encoder_workspace_bytes_f16",
+                        cls_forward="tt_encoder_forward_cls_f16", cls_workspace="tt_encoder_cls_workspace_bytes_f16",
+                        pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head="tt_rerank_head_f16",
+                        scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False)
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -102,49 +153,94 @@ def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-class EncoderWeights:
-    """Device-resident weights in the layout libtt_hip.so expects.
+class _CheckpointWeights:
+    """Device-resident weights built from an HF state dict (``embeddings.word_embeddings.weight``,
+    ``encoder.layer.{i}.attention.self.query.weight`` ... optional ``roberta.``/``bert.`` prefix, ``classifier.dense`` /
+    ``classifier.out_proj`` for the reranker), in the struct layout of one path of libtt_hip.so.
 
-    ``state`` maps HF checkpoint names (``embeddings.word_embeddings.weight``,
-    ``encoder.layer.{i}.attention.self.query.weight`` ... optional ``roberta.``/``bert.``
-    prefix, ``classifier.dense`` / ``classifier.out_proj`` for the reranker) to tensors.
-    Matrices are stored bf16, biases and LayerNorm parameters fp32.
-    """
+    ``_load`` walks the checkpoint for every weight class; biases and LayerNorm parameters are fp32 on every path.  A
+    subclass says how it stores the projections (``_matrix``) and the embedding tables and classifier matrices
+    (``_table``; fp32 here), and carries its ``path`` and ctypes ``_Struct``."""
+
+    path: EncoderPath
+    _Struct: type
+
+    def _load(self, cfg: EncoderConfig, state: Dict[str, torch.Tensor], device: torch.device) -> None:
+        if device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} need a HIP device; tensor_truth_amd has no CPU path")
+        self.cfg, self.device = cfg, device
+        self._keep: List[torch.Tensor] = []
+        sd = _strip_prefix(state)
+
+        def take(*names):
+            return sd[names[0]] if len(names) == 1 else torch.cat([sd[n] for n in names], 0)
+
+        def vec(*names):
+            return self._kept(names, take(*names).to(device=device, dtype=torch.float32).contiguous()).data_ptr()
+
+        def table(name):
+            return self._table([name], sd[name])
+
+        H = cfg.hidden
+        word, pos, typ = (table(f"embeddings.{n}_embeddings.weight") for n in ("word", "position", "token_type"))
+        if word.shape != (cfg.vocab_size, H) or pos.shape != (cfg.max_pos, H):
+            raise ValueError(f"embedding tables {tuple(word.shape)} / {tuple(pos.shape)} do not match {cfg}")
+        w = self._Struct(hidden=H, layers=cfg.layers, heads=cfg.heads, ffn=cfg.ffn, vocab=cfg.vocab_size, max_pos=cfg.max_pos,
+                         type_vocab=cfg.type_vocab, ln_eps=cfg.ln_eps, word_emb=word.data_ptr(), pos_emb=pos.data_ptr(),
+                         type_emb=typ.data_ptr(), emb_ln_g=vec("embeddings.LayerNorm.weight"),
+                         emb_ln_b=vec("embeddings.LayerNorm.bias"))
+        self._layers = (self._Struct.layer_type * max(cfg.layers, 1))()
+        for i in range(cfg.layers):
+            p = f"encoder.layer.{i}."
+            L = self._layers[i]
+            for field, mods in (("qkv", [f"attention.self.{n}." for n in ("query", "key", "value")]),   # one [3H][H] matrix
+                                ("o", ["attention.output.dense."]), ("ffn1", ["intermediate.dense."]), ("ffn2", ["output.dense."])):
+                names = [p + m + "weight" for m in mods]
+                self._matrix(L, field + "_w", names, take(*names))
+                setattr(L, field + "_b", vec(*(p + m + "bias" for m in mods)))
+            L.ln1_g, L.ln1_b = vec(p + "attention.output.LayerNorm.weight"), vec(p + "attention.output.LayerNorm.bias")
+            L.ln2_g, L.ln2_b = vec(p + "output.LayerNorm.weight"), vec(p + "output.LayerNorm.bias")
+        w.layer = ctypes.cast(self._layers, POINTER(self._Struct.layer_type))
+        if cfg.num_labels:
+            if cfg.num_labels != 1:
+                raise ValueError("only single-label (sigmoid) cross-encoder heads are supported")
+            w.cls_dense_w, w.cls_dense_b = table("classifier.dense.weight").data_ptr(), vec("classifier.dense.bias")
+            w.cls_out_w, w.cls_out_b = table("classifier.out_proj.weight").data_ptr(), vec("classifier.out_proj.bias")
+        self.struct = w
+
+    def _kept(self, names: Sequence[str], t: torch.Tensor) -> torch.Tensor:
+        """Keep ``t`` (the tensor of the checkpoint entries ``names``, concatenated) resident."""
+        self._keep.append(t)
+        return t
+
+    def _table(self, names: Sequence[str], x: torch.Tensor) -> torch.Tensor:
+        return self._kept(names, x.to(device=self.device, dtype=torch.float32).contiguous())
+
+    def _matrix(self, L: Structure, field: str, names: Sequence[str], x: torch.Tensor) -> None:
+        """Store one projection ``x`` [out][in] (checkpoint entries ``names``) and point ``L.<field>`` at it."""
+        setattr(L, field, self._table(names, x).data_ptr())
+
+    def parameters(self) -> Iterable[torch.Tensor]:
+        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
+        return iter(self._keep)
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self._keep)
+
+
+class EncoderWeights(_CheckpointWeights):
+    """The 16-bit path (``tt_encoder_forward``): matrices and embedding tables in bf16, or fp16 (the library's ``*_f16``
+    entry points); biases and LayerNorm parameters fp32."""
+
+    _Struct = _EncW
 
     def __init__(self, cfg: EncoderConfig, state: Dict[str, torch.Tensor], device: torch.device,
                  dtype: torch.dtype = torch.bfloat16):
-        if device.type != "cuda":
-            raise RuntimeError("EncoderWeights need a HIP device; tensor_truth_amd has no CPU path")
         if dtype not in (torch.bfloat16, torch.float16):
             raise ValueError("EncoderWeights: the 16-bit path computes in bfloat16 or float16")
-        self.cfg = cfg
-        self.device = device
         self.dtype = dtype           # element type of matrices and activations: bf16, or fp16 (libtt_hip's *_f16 entry points)
-        sd = _strip_prefix(state)
-        self._keep: List[torch.Tensor] = []
+        self.path = FP16_PATH if dtype == torch.float16 else BF16_PATH
         self._named: Dict[str, torch.Tensor] = {}     # HF name -> the resident tensor (state_dict())
-
-        def mat(name):
-            t = sd[name].to(device=device, dtype=dtype).contiguous()
-            self._keep.append(t)
-            self._named[name] = t
-            return t
-
-        def vec(name):
-            t = sd[name].to(device=device, dtype=torch.float32).contiguous()
-            self._keep.append(t)
-            self._named[name] = t
-            return t
-
-        H = cfg.hidden
-        self.word = mat("embeddings.word_embeddings.weight")
-        self.pos = mat("embeddings.position_embeddings.weight")
-        self.type = mat("embeddings.token_type_embeddings.weight")
-        self.emb_g = vec("embeddings.LayerNorm.weight")
-        self.emb_b = vec("embeddings.LayerNorm.bias")
-        if self.word.shape != (cfg.vocab_size, H) or self.pos.shape != (cfg.max_pos, H):
-            raise ValueError(f"embedding tables {tuple(self.word.shape)} / {tuple(self.pos.shape)} do not match {cfg}")
-        self._layers = (_LayerW * max(cfg.layers, 1))()
         self._qkv_w: List[torch.Tensor] = []
         self._ffn1_w: List[torch.Tensor] = []
         self._o_w: List[torch.Tensor] = []
@@ -152,46 +248,19 @@ class EncoderWeights:
         self._fp8: List[torch.Tensor] = []
         self.ffn_act_scales: Optional[List[float]] = None   # per layer, from calibrate_fp8()
         self.gemm_dtype = "bf16"
-        for i in range(cfg.layers):
-            p = f"encoder.layer.{i}."
-            qkv_w = torch.cat([sd[p + f"attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)
-            qkv_b = torch.cat([sd[p + f"attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
-            qkv_w = qkv_w.to(device=device, dtype=dtype).contiguous()
-            qkv_b = qkv_b.to(device=device, dtype=torch.float32).contiguous()
-            self._keep += [qkv_w, qkv_b]
-            for j, nm in enumerate(("query", "key", "value")):
-                self._named[p + f"attention.self.{nm}.weight"] = qkv_w[j * H:(j + 1) * H]
-                self._named[p + f"attention.self.{nm}.bias"] = qkv_b[j * H:(j + 1) * H]
-            self._qkv_w.append(qkv_w)
-            L = self._layers[i]
-            L.qkv_w, L.qkv_b = qkv_w.data_ptr(), qkv_b.data_ptr()
-            o_w = mat(p + "attention.output.dense.weight")
-            self._o_w.append(o_w)
-            L.o_w, L.o_b = o_w.data_ptr(), vec(p + "attention.output.dense.bias").data_ptr()
-            L.ln1_g = vec(p + "attention.output.LayerNorm.weight").data_ptr()
-            L.ln1_b = vec(p + "attention.output.LayerNorm.bias").data_ptr()
-            ffn1_w = mat(p + "intermediate.dense.weight")
-            self._ffn1_w.append(ffn1_w)
-            L.ffn1_w, L.ffn1_b = ffn1_w.data_ptr(), vec(p + "intermediate.dense.bias").data_ptr()
-            ffn2_w = mat(p + "output.dense.weight")
-            self._ffn2_w.append(ffn2_w)
-            L.ffn2_w, L.ffn2_b = ffn2_w.data_ptr(), vec(p + "output.dense.bias").data_ptr()
-            L.ln2_g = vec(p + "output.LayerNorm.weight").data_ptr()
-            L.ln2_b = vec(p + "output.LayerNorm.bias").data_ptr()
-        w = _EncW()
-        w.hidden, w.layers, w.heads, w.ffn = H, cfg.layers, cfg.heads, cfg.ffn
-        w.vocab, w.max_pos, w.type_vocab, w.ln_eps = cfg.vocab_size, cfg.max_pos, cfg.type_vocab, cfg.ln_eps
-        w.word_emb, w.pos_emb, w.type_emb = self.word.data_ptr(), self.pos.data_ptr(), self.type.data_ptr()
-        w.emb_ln_g, w.emb_ln_b = self.emb_g.data_ptr(), self.emb_b.data_ptr()
-        w.layer = ctypes.cast(self._layers, POINTER(_LayerW))
-        if cfg.num_labels:
-            if cfg.num_labels != 1:
-                raise ValueError("only single-label (sigmoid) cross-encoder heads are supported")
-            w.cls_dense_w = mat("classifier.dense.weight").data_ptr()
-            w.cls_dense_b = vec("classifier.dense.bias").data_ptr()
-            w.cls_out_w = mat("classifier.out_proj.weight").data_ptr()
-            w.cls_out_b = vec("classifier.out_proj.bias").data_ptr()
-        self.struct = w
+        self._load(cfg, state, device)
+
+    def _kept(self, names, t):
+        self._named.update(zip(names, t.chunk(len(names)) if len(names) > 1 else [t]))    # Q / K / V: row slices
+        return super()._kept(names, t)
+
+    def _table(self, names, x):
+        return self._kept(names, x.to(device=self.device, dtype=self.dtype).contiguous())
+
+    def _matrix(self, L, field, names, x):
+        t = self._table(names, x)
+        getattr(self, "_" + field).append(t)
+        setattr(L, field, t.data_ptr())
 
     @staticmethod
     def _quantize_rows(w: torch.Tensor):
@@ -222,6 +291,7 @@ class EncoderWeights:
                 for i in range(n):
                     for w in (self._qkv_w[i], self._ffn1_w[i], self._o_w[i], self._ffn2_w[i]):
                         self._fp8 += list(self._quantize_rows(w))
+                self._keep += self._fp8
             for i in range(n):
                 L = self._layers[i]
                 q8, qs, f8, fs, o8, os_, d8, ds = self._fp8[8 * i: 8 * i + 8]
@@ -236,17 +306,10 @@ class EncoderWeights:
                 L.ffn_act_scale = 0.0
         self.gemm_dtype = dtype
 
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep + self._fp8)
-
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """HF checkpoint name -> the resident (bf16 / fp32) tensor: what these weights ARE after rounding to bf16,
         e.g. to run the same model through the fp32 path (``encoder_f32.EncoderWeightsF32(cfg, w.state_dict(), dev)``)."""
         return dict(self._named)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep + self._fp8)
 
 
 def synthetic_state(cfg: EncoderConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
@@ -526,21 +589,38 @@ class _Stager:
 _stager = _Stager()
 
 
-class Encoder:
-    """Runs the HIP encoder for one set of weights."""
+def _pad_rows(batch: PackedBatch, multiple: int, skinny: bool) -> PackedBatch:
+    """``batch`` with its rows rounded up to a multiple of ``multiple`` (the tiled GEMMs of a path run whole tiles), padding
+    with the last token id and position 0.  ``skinny``: up to 256 rows in multiples of 64 stay as they are -- the projections
+    then run as weight-streaming skinny GEMMs (``_round_rows`` packs exactly that)."""
+    if skinny and batch.n_rows <= 256 and batch.n_rows % 64 == 0:
+        return batch
+    n = (batch.n_rows + multiple - 1) // multiple * multiple
+    if n == batch.n_rows:
+        return batch
 
-    def __init__(self, weights: EncoderWeights):
+    def pad(a, fill):
+        if a is None:
+            return None
+        out = np.full(n, fill, dtype=a.dtype)
+        out[: a.size] = a
+        return out
+
+    return dataclasses.replace(batch, ids=pad(batch.ids, batch.ids[-1] if batch.ids.size else 0), pos=pad(batch.pos, 0),
+                               types=pad(batch.types, 0), n_rows=n)
+
+
+class Encoder:
+    """Runs the HIP encoder for one set of weights, on the path they carry (``weights.path``)."""
+
+    def __init__(self, weights: _CheckpointWeights):
         self.w = weights
         self.cfg = weights.cfg
         self.device = weights.device
+        self.path = weights.path
         self.lib = _lib.load_library()
         # one forward (scratch lookup + every launch of it) is enqueued atomically: the workspace is shared per stream
         self._enqueue_lock = _ENQUEUE_LOCKS.setdefault((self.device.type, self.device.index), threading.Lock())
-        self._sfx = "_f16" if weights.dtype == torch.float16 else ""
-
-    def _fn(self, name: str):
-        """The entry point for this encoder's element type: ``name`` (bf16) or its fp16 twin ``name_f16``."""
-        return getattr(self.lib, name + self._sfx)
 
     def _upload(self, batch: PackedBatch):
         """Token arrays of a batch -> device int32 views (ids, pos, types | None, seq_start, seq_len): one pinned
@@ -567,25 +647,37 @@ class Encoder:
             slot["lock"].release()
         return tuple(devbuf[o:o + a.size] if a is not None else None for a, o in zip(parts, offs))
 
-    def forward_packed(self, batch: PackedBatch, want_lens: bool = False):
-        """-> (hidden [n_rows, H] bf16, cls_rows [B] int32 device tensor[, seq_len [B] int32 device tensor])."""
-        lib, dev, H = self.lib, self.device, self.cfg.hidden
+    def _padded(self, batch: PackedBatch) -> PackedBatch:
+        return _pad_rows(batch, self.path.row_tile, self.path.skinny) if self.path.row_tile else batch
+
+    def _run(self, name: str, workspace: str, batch: PackedBatch, out_rows: int, *ws_args):
+        """Upload ``batch`` and enqueue the forward entry point ``name`` (sized by ``workspace(struct, n_rows, *ws_args)``)
+        -> (its output [out_rows, H] in the path's hidden dtype, seq_start, seq_len device tensors)."""
+        dev, w = self.device, ctypes.byref(self.w.struct)
         ids, pos, types, starts, lens = self._upload(batch)
-        hidden = torch.empty((batch.n_rows, H), dtype=self.w.dtype, device=dev)
-        need = self._fn("tt_encoder_workspace_bytes")(ctypes.byref(self.w.struct), batch.n_rows)
+        out = torch.empty((out_rows, self.cfg.hidden), dtype=self.path.hidden, device=dev)
+        need = getattr(self.lib, workspace)(w, batch.n_rows, *ws_args)
         with self._enqueue_lock, torch.cuda.device(dev):
-            ws, base = _scratch.get("enc", dev, need)
-            rc = self._fn("tt_encoder_forward")(ctypes.byref(self.w.struct), ids.data_ptr(), pos.data_ptr(),
-                                        types.data_ptr() if types is not None else None, starts.data_ptr(),
-                                        lens.data_ptr(), len(batch.seq_len), batch.n_rows, batch.max_len,
-                                        hidden.data_ptr(), base, need, torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "tt_encoder_forward")
+            ws, base = _scratch.get(self.path.scratch, dev, need)
+            rc = getattr(self.lib, name)(w, ids.data_ptr(), pos.data_ptr(), types.data_ptr() if types is not None else None,
+                                         starts.data_ptr(), lens.data_ptr(), len(batch.seq_len), batch.n_rows, batch.max_len,
+                                         out.data_ptr(), base, need, torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, name)
+        return out, starts, lens
+
+    def forward_packed(self, batch: PackedBatch, want_lens: bool = False):
+        """-> (hidden [n_rows, H] (the weights' dtype on the 16-bit path, fp32 elsewhere), seq_start [B] int32 device
+        tensor[, seq_len [B] int32 device tensor]); ``n_rows`` after the path's padding."""
+        batch = self._padded(batch)
+        hidden, starts, lens = self._run(self.path.forward, self.path.workspace, batch, batch.n_rows)
         return (hidden, starts, lens) if want_lens else (hidden, starts)
 
     def calibrate_fp8(self, batch: PackedBatch, margin: float = 2.0) -> List[float]:
         """One bf16 forward over ``batch`` that records max |GELU output| per layer (``ffn_absmax_out`` hook) and sets
         the static e4m3 scales of the FFN intermediate, ``margin * max / 448`` (values beyond saturate).  Call before
         ``weights.set_gemm_dtype("fp8")`` to move the FFN output projection to fp8 as well."""
+        if self.path.no_fp8:
+            raise RuntimeError(self.path.no_fp8)
         w = self.w
         prev = w.gemm_dtype
         w.set_gemm_dtype("bf16")
@@ -601,69 +693,57 @@ class Encoder:
         return w.ffn_act_scales
 
     def cls_hidden_packed(self, batch: PackedBatch) -> Tuple[torch.Tensor, torch.Tensor]:
-        """-> (final hidden state of every sequence's CLS token [round_up(B,256), H] bf16, row ids [B] int32).
-        The last layer is evaluated for the CLS rows only (``tt_encoder_forward_cls``)."""
-        lib, dev, H = self.lib, self.device, self.cfg.hidden
-        if self.cfg.layers == 0:
-            hidden, starts = self.forward_packed(batch)
-            return hidden, starts
+        """-> (final hidden state of every sequence's CLS token, row ids [B] int32).  Where the path has a CLS-only forward,
+        the last layer is evaluated for the CLS rows only, into [pad(B), H] with rows 0..B-1; otherwise (and for a model
+        without layers) this is the full forward and its sequence starts."""
+        p = self.path
+        if p.cls_forward is None or self.cfg.layers == 0:
+            return self.forward_packed(batch)
         B = len(batch.seq_len)
-        ids, pos, types, starts, lens = self._upload(batch)
-        b_pad = (B + 255) // 256 * 256
-        cls = torch.empty((b_pad, H), dtype=self.w.dtype, device=dev)
-        need = self._fn("tt_encoder_cls_workspace_bytes")(ctypes.byref(self.w.struct), batch.n_rows, B)
-        with self._enqueue_lock, torch.cuda.device(dev):
-            ws, base = _scratch.get("enc", dev, need)
-            rc = self._fn("tt_encoder_forward_cls")(ctypes.byref(self.w.struct), ids.data_ptr(), pos.data_ptr(),
-                                            types.data_ptr() if types is not None else None, starts.data_ptr(),
-                                            lens.data_ptr(), B, batch.n_rows, batch.max_len, cls.data_ptr(), base, need,
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "tt_encoder_forward_cls")
-        rows = torch.arange(B, dtype=torch.int32, device=dev)
-        return cls, rows
+        b_pad = (B + 63) // 64 * 64 if p.skinny and B <= 256 else (B + 255) // 256 * 256
+        cls, _, _ = self._run(p.cls_forward, p.cls_workspace, self._padded(batch), b_pad, B)
+        return cls, torch.arange(B, dtype=torch.int32, device=self.device)
 
     def embed_packed(self, batch: PackedBatch, pooling: str = "cls") -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (embeddings fp32 [B, H] L2-normalised, same rounded to bf16).  ``pooling``: "cls" (the BGE family: the last layer
         runs for the CLS rows only) or "mean" (sentence-transformers mean pooling over a sequence's tokens: full last layer)."""
+        p, dev = self.path, self.device
         B, H = len(batch.seq_len), self.cfg.hidden
-        out = torch.empty((B, H), dtype=torch.float32, device=self.device)
-        # the 16-bit copy of an embedding is a SCAN QUERY, i.e. bf16 like the corpus: the bf16 kernels write it themselves, in
-        # the fp16 mode it is rounded from the fp32 vector here (round to nearest even either way)
-        f16 = self.w.dtype == torch.float16
-        out16 = None if f16 else torch.empty((B, H), dtype=torch.bfloat16, device=self.device)
-        o16 = None if f16 else out16.data_ptr()
+        out = torch.empty((B, H), dtype=torch.float32, device=dev)
+        # the 16-bit copy of an embedding is a SCAN QUERY, i.e. bf16 like the corpus: the pooling kernels write it themselves,
+        # except in the fp16 mode, where it is rounded from the fp32 vector here (round to nearest even either way)
+        out16 = torch.empty((B, H), dtype=torch.bfloat16, device=dev) if p.pool_writes_bf16 else None
         if pooling == "mean":
             hidden, starts, lens = self.forward_packed(batch, want_lens=True)
-            with torch.cuda.device(self.device):
-                rc = self._fn("tt_embed_pool_mean")(hidden.data_ptr(), H, starts.data_ptr(), lens.data_ptr(), B, H, out.data_ptr(),
-                                                    o16, torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "tt_embed_pool_mean")
-            return out, (out.to(torch.bfloat16) if f16 else out16)
-        if pooling != "cls":
+            name, rows = p.pool_mean, (starts.data_ptr(), lens.data_ptr())
+        elif pooling == "cls":
+            hidden, cls_rows = self.cls_hidden_packed(batch)
+            name, rows = p.pool, (cls_rows.data_ptr(),)
+        else:
             raise ValueError(f"pooling '{pooling}' (supported: 'cls', 'mean')")
-        hidden, cls_rows = self.cls_hidden_packed(batch)
-        with torch.cuda.device(self.device):
-            rc = self._fn("tt_embed_pool")(hidden.data_ptr(), H, cls_rows.data_ptr(), B, H, out.data_ptr(), o16,
-                                           torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, "tt_embed_pool")
-        return out, (out.to(torch.bfloat16) if f16 else out16)
+        with torch.cuda.device(dev):
+            rc = getattr(self.lib, name)(hidden.data_ptr(), H, *rows, B, H, out.data_ptr(),
+                                         out16.data_ptr() if out16 is not None else None, torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, name)
+        return out, (out16 if out16 is not None else out.to(torch.bfloat16))
 
     def rerank_packed(self, batch: PackedBatch, want_logits: bool = False):
         """-> sigmoid scores fp32 [B] (and logits)."""
         if not self.cfg.num_labels:
             raise RuntimeError("these weights carry no classification head")
+        p, dev = self.path, self.device
         hidden, cls_rows = self.cls_hidden_packed(batch)
         B, H = len(batch.seq_len), self.cfg.hidden
-        scores = torch.empty(B, dtype=torch.float32, device=self.device)
-        logits = torch.empty(B, dtype=torch.float32, device=self.device) if want_logits else None
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        logits = torch.empty(B, dtype=torch.float32, device=dev) if want_logits else None
         n_pad = (B + 127) // 128 * 128
-        need = 2 * ((n_pad * H * 2 + 255) // 256 * 256)
-        with self._enqueue_lock, torch.cuda.device(self.device):
-            ws, base = _scratch.get("head", self.device, need)
-            rc = self._fn("tt_rerank_head")(ctypes.byref(self.w.struct), hidden.data_ptr(), cls_rows.data_ptr(), B,
-                                         scores.data_ptr(), logits.data_ptr() if want_logits else None, base, need,
-                                         torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, "tt_rerank_head")
+        need = 2 * ((n_pad * H * hidden.element_size() + 255) // 256 * 256)
+        with self._enqueue_lock, torch.cuda.device(dev):
+            ws, base = _scratch.get(p.head_scratch, dev, need)
+            rc = getattr(self.lib, p.head)(ctypes.byref(self.w.struct), hidden.data_ptr(), cls_rows.data_ptr(), B,
+                                           scores.data_ptr(), logits.data_ptr() if want_logits else None, base, need,
+                                           torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, p.head)
         return (scores, logits) if want_logits else scores
 
     # -- convenience over python lists -------------------------------------------------------

@@ -36,9 +36,10 @@ mode is logged when a model is loaded.
 """
 from __future__ import annotations
 
+import functools
 import logging
 import os
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Callable, Dict, Optional, Tuple
 
 logger = logging.getLogger(__name__)
 
@@ -93,51 +94,44 @@ def reference_impl(cfg, environ=None) -> str:
     return "f16x3" if encoder_x3.supports(cfg) else "fp32"
 
 
+def _implementations() -> Dict[str, Tuple[Callable, str]]:
+    """Mode (or, for mode "reference", implementation) -> (weights factory ``f(cfg, state, device)``, description)."""
+    import torch
+
+    from .encoder import EncoderWeights
+    from .encoder_f16c import EncoderWeightsF16C
+    from .encoder_f32 import EncoderWeightsF32
+    from .encoder_x3 import EncoderWeightsX3
+
+    return {
+        "f16c": (EncoderWeightsF16C, "reference (fp32 semantics as fp16 products + block-scaled e4m3 correction terms on the "
+                                     "matrix cores, fp32 residual stream)"),
+        "f16x3": (functools.partial(EncoderWeightsX3, dtype=torch.float16),
+                  "reference (fp32 semantics as split-fp16 on the fp16 matrix cores, fp32 residual stream)"),
+        "bf16x3": (EncoderWeightsX3, "reference (fp32 semantics as split-bf16 on the bf16 matrix cores, fp32 residual stream)"),
+        "fp32": (EncoderWeightsF32, "reference (fp32 weights, activations and MFMA)"),
+        "fp16": (functools.partial(EncoderWeights, dtype=torch.float16), "fp16 (fp32 accumulate)"),
+        "bf16": (EncoderWeights, "bf16 (fp32 accumulate)"),
+        "fp8": (EncoderWeights, "fp8 e4m3 layer projections, bf16 elsewhere"),
+    }
+
+
 def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], what: str) -> Tuple[Any, Any, str]:
     """-> (weights, encoder, description) for the resolved precision; logs it."""
-    from .encoder import Encoder, EncoderWeights
+    from .encoder import Encoder
 
     mode = resolve(model_kwargs)
-    if mode == "reference":
-        impl = reference_impl(cfg)
-        if impl == "f16c":
-            from .encoder_f16c import EncoderF16C, EncoderWeightsF16C
-
-            w = EncoderWeightsF16C(cfg, state, device)
-            enc, desc = EncoderF16C(w), ("reference (fp32 semantics as fp16 products + block-scaled e4m3 correction terms on the "
-                                         "matrix cores, fp32 residual stream)")
-        elif impl == "f16x3":
-            import torch
-
-            from .encoder_x3 import EncoderWeightsX3, EncoderX3
-
-            w = EncoderWeightsX3(cfg, state, device, dtype=torch.float16)
-            enc, desc = EncoderX3(w), "reference (fp32 semantics as split-fp16 on the fp16 matrix cores, fp32 residual stream)"
-        elif impl == "bf16x3":
-            from .encoder_x3 import EncoderWeightsX3, EncoderX3
-
-            w = EncoderWeightsX3(cfg, state, device)
-            enc, desc = EncoderX3(w), "reference (fp32 semantics as split-bf16 on the bf16 matrix cores, fp32 residual stream)"
-        else:
-            from .encoder_f32 import EncoderF32, EncoderWeightsF32
-
-            w = EncoderWeightsF32(cfg, state, device)
-            enc, desc = EncoderF32(w), "reference (fp32 weights, activations and MFMA)"
-            if os.environ.get("TT_REFERENCE_IMPL", "").strip().lower() not in ("fp32", "float32", "f32"):
-                # the rate cliff of the default mode (ADVICE r04): the split-plane kernels take hidden sizes that are multiples of 128
-                # with 64- or 32-wide heads (bge-m3, the bge rerankers; round 6: bge-small 384 and MiniLM's 32-wide heads too); any
-                # other shape runs on the fp32 MFMA -- ~1/16 of the bf16 matrix rate instead of 1/3
-                logger.warning("%s: hidden=%d heads=%d has no split-plane kernel: the reference precision falls back to the fp32 MFMA "
-                               "path (about 1/16 of the bf16 rate; name torch_dtype=bfloat16 / float16 or TT_PRECISION for the "
-                               "16-bit modes)", what, getattr(cfg, "hidden", -1), getattr(cfg, "heads", -1))
-    elif mode == "fp16":
-        import torch
-
-        w = EncoderWeights(cfg, state, device, dtype=torch.float16)
-        enc, desc = Encoder(w), "fp16 (fp32 accumulate)"
-    else:
-        w = EncoderWeights(cfg, state, device)
-        w.set_gemm_dtype(mode)
-        enc, desc = Encoder(w), ("bf16 (fp32 accumulate)" if mode == "bf16" else "fp8 e4m3 layer projections, bf16 elsewhere")
+    impl = reference_impl(cfg) if mode == "reference" else mode
+    make, desc = _implementations()[impl]
+    w = make(cfg, state, device)
+    if impl == "fp8":
+        w.set_gemm_dtype("fp8")
+    if impl == "fp32" and os.environ.get("TT_REFERENCE_IMPL", "").strip().lower() not in ("fp32", "float32", "f32"):
+        # the rate cliff of the default mode (ADVICE r04): the split-plane kernels take hidden sizes that are multiples of 128
+        # with 64- or 32-wide heads (bge-m3, the bge rerankers; round 6: bge-small 384 and MiniLM's 32-wide heads too); any
+        # other shape runs on the fp32 MFMA -- ~1/16 of the bf16 matrix rate instead of 1/3
+        logger.warning("%s: hidden=%d heads=%d has no split-plane kernel: the reference precision falls back to the fp32 MFMA "
+                       "path (about 1/16 of the bf16 rate; name torch_dtype=bfloat16 / float16 or TT_PRECISION for the "
+                       "16-bit modes)", what, getattr(cfg, "hidden", -1), getattr(cfg, "heads", -1))
     logger.info("%s: precision = %s", what, desc)
-    return w, enc, desc
+    return w, Encoder(w), desc

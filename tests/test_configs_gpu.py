@@ -85,14 +85,14 @@ def test_config_c1_bge_small_in_the_default_precision_runs_on_the_split_planes(d
     from tensor_truth_amd import precision
     from tensor_truth_amd import scan as tscan
     from tensor_truth_amd.encoder import BGE_SMALL_EN_V15
-    from tensor_truth_amd.encoder_x3 import EncoderX3
+    from tensor_truth_amd.encoder_x3 import EncoderWeightsX3
 
     cfg = BGE_SMALL_EN_V15
     ocfg = oe.EncoderConfig(**cfg.__dict__)
     W = oe.synth_weights(ocfg, seed=3)
     assert precision.resolve(None) == "reference" and precision.reference_impl(cfg) == "f16x3"
     _, enc, desc = precision.build_encoder(cfg, W, dev, None, "config 1 embedder")
-    assert isinstance(enc, EncoderX3) and enc.w.gemm_dtype == "f16x3" and "split-fp16" in desc
+    assert isinstance(enc.w, EncoderWeightsX3) and enc.w.gemm_dtype == "f16x3" and "split-fp16" in desc
     g = torch.Generator().manual_seed(777)
     lens = torch.randint(16, 129, (1000,), generator=g).tolist()
     chunks = [[101] + torch.randint(1000, cfg.vocab_size, (n - 2,), generator=g).tolist() + [102] for n in lens]

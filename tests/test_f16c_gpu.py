@@ -232,9 +232,9 @@ def test_the_unchanged_reference_calls_and_their_implementations(dev, built_lib,
     holds 1e-3 on the stress weights too); TT_REFERENCE_IMPL=f16c selects this file's faster path, bf16x3 / fp32 the older ones --
     all within 1e-3 relative of the fp32 oracle here."""
     from tensor_truth_amd.encoder import EncoderConfig
-    from tensor_truth_amd.encoder_f16c import EncoderF16C
-    from tensor_truth_amd.encoder_f32 import EncoderF32
-    from tensor_truth_amd.encoder_x3 import EncoderX3
+    from tensor_truth_amd.encoder_f16c import EncoderWeightsF16C
+    from tensor_truth_amd.encoder_f32 import EncoderWeightsF32
+    from tensor_truth_amd.encoder_x3 import EncoderWeightsX3
     from tensor_truth_amd.embedding import HipHuggingFaceEmbedding
     from tensor_truth_amd.rerank import HipSentenceTransformerRerank
 
@@ -245,11 +245,11 @@ def test_the_unchanged_reference_calls_and_their_implementations(dev, built_lib,
     texts = [" ".join(f"w{(7 * i + j) % 50}" for j in range(5 + 3 * i)) for i in range(9)]
     query = "w1 w2 w3 which one"
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr._encoder, EncoderX3) and rr._encoder.w.dtype == torch.float16 and rr.precision.startswith("reference")
+    assert isinstance(rr._encoder.w, EncoderWeightsX3) and rr._encoder.w.dtype == torch.float16 and rr.precision.startswith("reference")
     got_default = torch.tensor(rr.predict([(query, t) for t in texts]))
     monkeypatch.setenv("TT_REFERENCE_IMPL", "f16c")
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr._encoder, EncoderF16C) and rr.precision.startswith("reference")
+    assert isinstance(rr._encoder.w, EncoderWeightsF16C) and rr.precision.startswith("reference")
     got = torch.tensor(rr.predict([(query, t) for t in texts]))
     toks = [rr._tokenizer.encode_pair(query, t, rr.max_length)[0] for t in texts]
     L = max(len(t) for t in toks)
@@ -263,9 +263,9 @@ def test_the_unchanged_reference_calls_and_their_implementations(dev, built_lib,
     assert ((got_default - want).abs() / want.abs()).max().item() < 1e-4
     emb = HipHuggingFaceEmbedding("test/emb", device="cuda",
                                   model_kwargs={"encoder_config": EncoderConfig(**{**XLMR, "num_labels": 0}), "state_dict": W})
-    assert isinstance(emb._encoder, EncoderF16C)
+    assert isinstance(emb._encoder.w, EncoderWeightsF16C)
     monkeypatch.setenv("TT_REFERENCE_IMPL", "bf16x3")
     rr3 = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr3._encoder, EncoderX3) and rr3._encoder.w.dtype == torch.bfloat16
+    assert isinstance(rr3._encoder.w, EncoderWeightsX3) and rr3._encoder.w.dtype == torch.bfloat16
     monkeypatch.setenv("TT_REFERENCE_IMPL", "fp32")
-    assert isinstance(HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))._encoder, EncoderF32)
+    assert isinstance(HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))._encoder.w, EncoderWeightsF32)

@@ -104,7 +104,7 @@ def test_float32_through_the_plugin_surface(dev, built_lib, monkeypatch):
     monkeypatch.setenv("TT_REFERENCE_IMPL", "fp32")
     from tensor_truth_amd.embedding import HipHuggingFaceEmbedding
     from tensor_truth_amd.encoder import EncoderConfig
-    from tensor_truth_amd.encoder_f32 import EncoderF32
+    from tensor_truth_amd.encoder_f32 import EncoderWeightsF32
     from tensor_truth_amd.rerank import HipSentenceTransformerRerank
     from tensor_truth_amd.schema import NodeWithScore, QueryBundle, TextNode
 
@@ -112,7 +112,7 @@ def test_float32_through_the_plugin_surface(dev, built_lib, monkeypatch):
     W = oe.synth_weights(cfg_o, seed=31)
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda",
                                       model_kwargs={"encoder_config": cfg, "state_dict": W, "torch_dtype": torch.float32})
-    assert isinstance(rr._encoder, EncoderF32) and sum(p.numel() for p in rr.model.parameters()) > 0
+    assert isinstance(rr._encoder.w, EncoderWeightsF32) and sum(p.numel() for p in rr.model.parameters()) > 0
     texts = [" ".join(f"w{(7 * i + j) % 50}" for j in range(5 + 3 * i)) for i in range(9)]
     query = "w1 w2 w3 which one"
     got = torch.tensor(rr.predict([(query, t) for t in texts]))
@@ -126,13 +126,13 @@ def test_float32_through_the_plugin_surface(dev, built_lib, monkeypatch):
     emb = HipHuggingFaceEmbedding("test/embed", device="cuda",
                                   model_kwargs={"encoder_config": EncoderConfig(**{**XLMR, "num_labels": 0}), "state_dict": W,
                                                 "torch_dtype": "float32"})
-    assert isinstance(emb._encoder, EncoderF32)
+    assert isinstance(emb._encoder.w, EncoderWeightsF32)
     e = torch.tensor(emb.get_text_embedding_batch(texts))
     seqs = [emb._tokenizer.encode(t, emb.max_length) for t in texts]
     ids, mask = _pad(seqs, cfg.pad_id)
     want_e = oe.embed(ids, mask, W, cfg_o)
     assert (e - want_e).abs().max().item() <= 2e-5
     # bf16 stays the default
-    from tensor_truth_amd.encoder import Encoder
+    from tensor_truth_amd.encoder import EncoderWeights
     assert isinstance(HipSentenceTransformerRerank(model="test/xenc", device="cuda",
-                                                   model_kwargs={"encoder_config": cfg, "state_dict": W})._encoder, Encoder)
+                                                   model_kwargs={"encoder_config": cfg, "state_dict": W})._encoder.w, EncoderWeights)

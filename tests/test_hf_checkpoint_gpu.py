@@ -264,9 +264,9 @@ def test_bert_cross_encoder_checkpoint_vs_transformers(dev, built_lib, tmp_path)
     # round 6: this 384-wide, 32-wide-head family runs the reference precision on the matrix cores (f16x3), not
     # on the fp32 MFMA; probabilities within north_star's 1e-3 relative of the upstream fp32 forward
     from tensor_truth_amd import precision as _prec
-    from tensor_truth_amd.encoder_x3 import EncoderX3
+    from tensor_truth_amd.encoder_x3 import EncoderWeightsX3
 
-    assert _prec.reference_impl(rr_ref.config) == "f16x3" and isinstance(rr_ref._encoder, EncoderX3) and "split-fp16" in rr_ref.precision
+    assert _prec.reference_impl(rr_ref.config) == "f16x3" and isinstance(rr_ref._encoder.w, EncoderWeightsX3) and "split-fp16" in rr_ref.precision
     assert (got_ref - want_logit).abs().max().item() < 2e-4 * max(1.0, want_logit.abs().max().item())
     rr_sig = HipSentenceTransformerRerank(model=str(mdir), top_n=3, device="cuda",
                                           model_kwargs={"tokenizer": tk, "precision": "reference", "activation": "sigmoid"})

@@ -248,9 +248,9 @@ def test_precision_selector_reaches_both_surfaces(dev, built_lib, monkeypatch):
     (process level), ModelManager.set_precision (config key) and model_kwargs name another mode; TT_REFERENCE_IMPL=fp32
     picks the fp32-MFMA implementation of the reference mode."""
     from tensor_truth_amd import model_manager as mm
-    from tensor_truth_amd.encoder import Encoder, EncoderConfig
-    from tensor_truth_amd.encoder_f32 import EncoderF32
-    from tensor_truth_amd.encoder_x3 import EncoderX3
+    from tensor_truth_amd.encoder import EncoderConfig, EncoderWeights
+    from tensor_truth_amd.encoder_f32 import EncoderWeightsF32
+    from tensor_truth_amd.encoder_x3 import EncoderWeightsX3
     from tensor_truth_amd.rerank import HipSentenceTransformerRerank
 
     cfg, cfg_o = EncoderConfig(**XLMR), oe.EncoderConfig(**XLMR)
@@ -268,21 +268,21 @@ def test_precision_selector_reaches_both_surfaces(dev, built_lib, monkeypatch):
     monkeypatch.delenv("TT_PRECISION", raising=False)
     monkeypatch.setenv("TT_REFERENCE_IMPL", "bf16x3")      # this file tests the split-bf16 implementation (the default one: test_f16c_gpu.py)
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr._encoder, EncoderX3) and rr.precision.startswith("reference") and scores_of(rr) <= 2e-4    # the default
+    assert isinstance(rr._encoder.w, EncoderWeightsX3) and rr.precision.startswith("reference") and scores_of(rr) <= 2e-4    # the default
     monkeypatch.setenv("TT_PRECISION", "bf16")
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr._encoder, Encoder) and rr.precision.startswith("bf16")          # the process setting names bf16
+    assert isinstance(rr._encoder.w, EncoderWeights) and rr.precision.startswith("bf16")          # the process setting names bf16
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs={**base, "torch_dtype": "bfloat16"})
-    assert isinstance(rr._encoder, Encoder)                                                # the reference's own config spelling
+    assert isinstance(rr._encoder.w, EncoderWeights)                                                # the reference's own config spelling
     monkeypatch.setenv("TT_PRECISION", "reference")
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr._encoder, EncoderX3) and scores_of(rr) <= 2e-4
+    assert isinstance(rr._encoder.w, EncoderWeightsX3) and scores_of(rr) <= 2e-4
     monkeypatch.setenv("TT_REFERENCE_IMPL", "fp32")
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs=dict(base))
-    assert isinstance(rr._encoder, EncoderF32) and scores_of(rr) <= 1e-4
+    assert isinstance(rr._encoder.w, EncoderWeightsF32) and scores_of(rr) <= 1e-4
     monkeypatch.setenv("TT_REFERENCE_IMPL", "bf16x3")
     rr = HipSentenceTransformerRerank(model="test/xenc", top_n=3, device="cuda", model_kwargs={**base, "precision": "bf16"})
-    assert isinstance(rr._encoder, Encoder)                                                # an explicit kwarg beats the environment
+    assert isinstance(rr._encoder.w, EncoderWeights)                                                # an explicit kwarg beats the environment
     monkeypatch.delenv("TT_PRECISION")
     # the ModelManager config key, through the reference's own lifecycle calls
     mm.ModelManager.reset_instance()
@@ -290,13 +290,13 @@ def test_precision_selector_reaches_both_surfaces(dev, built_lib, monkeypatch):
     mgr.model_kwargs_overrides["test/xenc"] = dict(base)
     mgr.model_kwargs_overrides["test/emb"] = {"encoder_config": EncoderConfig(**{**XLMR, "num_labels": 0}), "state_dict": W}
     rr = mgr.get_reranker("test/xenc", top_n=3, device="cuda")                            # nothing named anywhere: the default
-    assert isinstance(rr._encoder, EncoderX3) and scores_of(rr) <= 2e-4
+    assert isinstance(rr._encoder.w, EncoderWeightsX3) and scores_of(rr) <= 2e-4
     mgr.set_precision("bf16")
-    assert isinstance(mgr.get_reranker("test/xenc", top_n=3, device="cuda")._encoder, Encoder)
-    assert isinstance(mgr.get_embedder("test/emb", "cuda")._encoder, Encoder)
+    assert isinstance(mgr.get_reranker("test/xenc", top_n=3, device="cuda")._encoder.w, EncoderWeights)
+    assert isinstance(mgr.get_embedder("test/emb", "cuda")._encoder.w, EncoderWeights)
     mgr.set_precision(None)
     emb = mgr.get_embedder("test/emb", "cuda")
-    assert isinstance(emb._encoder, EncoderX3) and emb.precision.startswith("reference")
+    assert isinstance(emb._encoder.w, EncoderWeightsX3) and emb.precision.startswith("reference")
     e = torch.tensor(emb.get_text_embedding_batch(texts))
     ids, mask = _pad([emb._tokenizer.encode(t, emb.max_length) for t in texts], cfg.pad_id)
     assert (e - oe.embed(ids, mask, W, cfg_o)).abs().max().item() <= 5e-5
