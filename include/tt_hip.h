@@ -569,6 +569,70 @@ int tt_attention_x3_hd_f16(const void* qk_planes, int ld_qk, int q_col0, int k_c
                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len,
                            int head_dim, int cls_only, void* stream);
 
+/* ---- decoder embedder: Qwen3Model-architecture checkpoints (Qwen3-Embedding; csrc/decoder.hip) ------------------------------
+ * The reference embeds with whatever Hugging Face model its config names (api/routes/startup.py:108-133,
+ * app_utils/config_schema.py:41-61, services/model_manager.py:214-252); the Qwen3-Embedding model card runs it in bf16 with
+ * left padding and pools the LAST token.  Pre-norm decoder block, no biases: RMSNorm -> QKV projection -> per-head RMSNorm of
+ * q and k, rotate-half RoPE (positions 0-based within each sequence) -> causal grouped-query attention (query head h reads KV
+ * head h / (heads / kv_heads)) -> output projection + residual -> RMSNorm -> gate|up projection -> SiLU(gate) * up -> down
+ * projection + residual; a final RMSNorm.  Same packed token layout as tt_encoder_forward (`pos` = position within the
+ * sequence, type_ids must be NULL), same projections (the 16-bit GEMMs), bf16 -- or fp16 for the `_f16` twins.
+ * Matrices [out][in] in the element type, norm weights fp32.  hidden a multiple of 128 and <= 1024 (the scan's limit),
+ * head_dim 64 or 128, heads a multiple of kv_heads, (heads + 2 kv_heads) * head_dim a multiple of 128, heads * head_dim and
+ * ffn multiples of 64; anything else is refused before a launch. */
+typedef struct tt_decoder_layer_weights {
+    const void* qkv_w;        /* [(heads + 2 kv_heads) * head_dim][H]: q_proj, k_proj, v_proj rows concatenated */
+    const float* q_norm;      /* [head_dim] self_attn.q_norm */
+    const float* k_norm;      /* [head_dim] self_attn.k_norm */
+    const void* o_w;          /* [H][heads * head_dim] */
+    const float* attn_norm;   /* [H] input_layernorm */
+    const float* ffn_norm;    /* [H] post_attention_layernorm */
+    const void* gate_up_w;    /* [2F][H]: gate_proj rows, then up_proj rows */
+    const void* down_w;       /* [H][F] */
+} tt_decoder_layer_weights;
+
+typedef struct tt_decoder_weights {
+    int32_t hidden, layers, heads, kv_heads, head_dim, ffn, vocab;
+    float rms_eps, rope_theta;
+    const void* embed;        /* [vocab][H] embed_tokens */
+    const tt_decoder_layer_weights* layer; /* host array [layers] */
+    const float* final_norm;  /* [H] norm */
+} tt_decoder_weights;
+
+size_t tt_decoder_workspace_bytes(const tt_decoder_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state (after the final norm) */
+int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* sentence-transformers Pooling(lasttoken) + Normalize: out[b] = h[r] / ||h[r]||_2 with r = seq_start[b] + seq_len[b] - 1;
+ * out_16 (optional) the same vector in the element type (bf16: ready to be a scan query). */
+int tt_embed_pool_last(const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden_size,
+                       float* out_f32, void* out_16, void* stream);
+/* building blocks (parity tests; the forward's own kernels).
+ * tt_qk_norm_rope: rows of qkv [n_rows][ld] (q heads at column h * head_dim, k heads behind them, v heads behind those; n_rows a
+ *   multiple of 8): q and k heads RMSNorm-ed with q_norm / k_norm and rotated by RoPE at pos[row] in place; the v heads copied to
+ *   the V8 layout of tt_attention_varlen, vt[(row / 8) * ldvt + feature * 8 + row % 8].
+ * tt_attention_causal_gqa: out[q][h * head_dim ...] = softmax over keys seq_start <= k <= q of (Q_h . K_{h/g}) / sqrt(head_dim),
+ *   applied to V_{h/g}; Q at q_col0 + h * head_dim, K at k_col0 + kvh * head_dim of rows of ld elements, V in the V8 layout; any
+ *   sequence start; rows of no sequence are not written. */
+int tt_qk_norm_rope(void* qkv, int ld, const int32_t* pos, const float* q_norm, const float* k_norm, int n_rows, int heads,
+                    int kv_heads, int head_dim, float eps, float rope_theta, void* vt, int ldvt, void* stream);
+int tt_attention_causal_gqa(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads,
+                            int head_dim, int max_len, void* stream);
+/* the fp16 twins (decoder.hip compiled a second time, like the encoder's _f16 entry points) */
+size_t tt_decoder_workspace_bytes_f16(const tt_decoder_weights* w, int n_rows);
+int tt_decoder_forward_f16(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int tt_embed_pool_last_f16(const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden_size,
+                           float* out_f32, void* out_16, void* stream);
+int tt_qk_norm_rope_f16(void* qkv, int ld, const int32_t* pos, const float* q_norm, const float* k_norm, int n_rows, int heads,
+                        int kv_heads, int head_dim, float eps, float rope_theta, void* vt, int ldvt, void* stream);
+int tt_attention_causal_gqa_f16(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                                const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads,
+                                int head_dim, int max_len, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

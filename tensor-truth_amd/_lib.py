@@ -176,6 +176,23 @@ SIGNATURES = {
                              c_int, c_void_p]),
     "tt_attention_f16c": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                   c_int, c_int, c_void_p]),
+    # decoder embedder (Qwen3Model architecture) and its fp16 twins (same signatures)
+    "tt_decoder_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "tt_decoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_embed_pool_last": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tt_qk_norm_rope": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
+                             c_void_p, c_int, c_void_p]),
+    "tt_attention_causal_gqa": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "tt_decoder_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
+    "tt_decoder_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_embed_pool_last_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tt_qk_norm_rope_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
+                                 c_void_p, c_int, c_void_p]),
+    "tt_attention_causal_gqa_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

@@ -38,3 +38,9 @@
 #define tt_attention_x3 tt_attention_x3_f16
 #define tt_attention_x3_hd tt_attention_x3_hd_f16
 #define tt_attention_cls_varlen tt_attention_cls_varlen_f16
+// decoder.hip a second time: the decoder embedder in fp16
+#define tt_decoder_workspace_bytes tt_decoder_workspace_bytes_f16
+#define tt_decoder_forward tt_decoder_forward_f16
+#define tt_embed_pool_last tt_embed_pool_last_f16
+#define tt_attention_causal_gqa tt_attention_causal_gqa_f16
+#define tt_qk_norm_rope tt_qk_norm_rope_f16

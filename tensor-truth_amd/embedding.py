@@ -34,7 +34,7 @@ def query_instruction_for(model_name: str) -> str:
     return ""
 
 
-def _report_unused_kwargs(model_name: str, model_kwargs, tokenizer_kwargs) -> None:
+def _report_unused_kwargs(model_name: str, model_kwargs, tokenizer_kwargs, decoder: bool = False) -> None:
     """The reference passes these through to sentence-transformers (model_manager.py:214-252); say what happens to
     them here instead of dropping them silently."""
     mk = model_kwargs or {}
@@ -47,8 +47,12 @@ def _report_unused_kwargs(model_name: str, model_kwargs, tokenizer_kwargs) -> No
                     "(no padding tokens are computed)", model_name, mk["attn_implementation"])
     side = (tokenizer_kwargs or {}).get("padding_side")
     if side:
-        logger.info("%s: padding_side=%s has no effect -- sequences are packed without padding and CLS pooling "
-                    "reads the first token of every sequence", model_name, side)
+        if decoder:
+            logger.info("%s: padding_side=%s has no effect -- sequences are packed without padding and last-token pooling "
+                        "reads the last token of every sequence", model_name, side)
+        else:
+            logger.info("%s: padding_side=%s has no effect -- sequences are packed without padding and CLS pooling "
+                        "reads the first token of every sequence", model_name, side)
 
 
 class HipHuggingFaceEmbedding:
@@ -68,17 +72,19 @@ class HipHuggingFaceEmbedding:
         self.embed_batch_size = embed_batch_size
         self.normalize = normalize
         self.tokenizer_kwargs = tokenizer_kwargs
-        _report_unused_kwargs(model_name, model_kwargs, tokenizer_kwargs)
         cfg, state, mdir = _weights.resolve(model_name, model_kwargs, dev, want_head=False)
+        _report_unused_kwargs(model_name, model_kwargs, tokenizer_kwargs, decoder=cfg.arch == "qwen3")
         self.config = cfg
         # sentence-transformers pooling: what the checkpoint directory declares (1_Pooling/config.json), unless the caller says
-        # (model_kwargs["pooling"]); "cls" for the BGE family the reference defaults to, "mean" for e5 / all-MiniLM / gte ...
-        pooling = (model_kwargs or {}).get("pooling") or _weights.pooling_mode(mdir)
-        pooling = {"cls_token": "cls", "mean_tokens": "mean"}.get(pooling, pooling)
-        if pooling not in ("cls", "mean"):
-            # no silent wrong vectors: anything else (max, weighted mean, last token ...) has no kernel here
+        # (model_kwargs["pooling"]); "cls" for the BGE family the reference defaults to, "mean" for e5 / all-MiniLM / gte ...,
+        # "last" for the decoder embedders (also when their directory declares nothing)
+        pooling = (model_kwargs or {}).get("pooling") or _weights.pooling_mode(mdir, "last" if cfg.arch == "qwen3" else "cls")
+        pooling = {"cls_token": "cls", "mean_tokens": "mean", "lasttoken": "last"}.get(pooling, pooling)
+        if pooling not in ("cls", "mean", "last") or (pooling == "last" and cfg.arch != "qwen3"):
+            # no silent wrong vectors: anything else (max, weighted mean, last token of an encoder ...) has no kernel here
             raise NotImplementedError(f"{model_name}: sentence-transformers pooling '{pooling}' is not supported "
-                                      f"(CLS and mean pooling, both followed by L2 normalisation, are)")
+                                      f"(CLS and mean pooling, and last-token pooling of decoder embedders, all followed by "
+                                      f"L2 normalisation, are)")
         self.pooling = pooling
         # precision.resolve(): model_kwargs (torch_dtype float32 = the reference's own default, config_schema.py:66-76),
         # ModelManager.precision, TT_PRECISION; default: the reference's fp32 semantics.  (`_model.parameters()` is read by the memory accounting.)
@@ -87,6 +93,14 @@ class HipHuggingFaceEmbedding:
         self.max_length = min(max_length or cfg.max_seq_len, cfg.max_seq_len)
         self.query_instruction = query_instruction_for(model_name) if query_instruction is None else query_instruction
         self.text_instruction = text_instruction or ""
+        if cfg.arch == "qwen3":
+            # decoder embedders carry their instructions as sentence-transformers prompts (config_sentence_transformers.json):
+            # "query" for queries, "document" for texts -- the prompt_name the reference's stack passes for each
+            pr = _weights.prompts(mdir)
+            if query_instruction is None:
+                self.query_instruction = pr.get("query", "")
+            if text_instruction is None:
+                self.text_instruction = pr.get("document", "")
         # texts tokenized per pipeline step (see _embed_texts): one encoder batch -- sequences are packed without
         # padding tokens, so nothing is lost by sorting by length inside a window only
         self.pipeline_window = int((model_kwargs or {}).get("pipeline_window", max(embed_batch_size, 2048)))

@@ -35,7 +35,7 @@ from . import _lib
 class EncoderConfig:
     """The HF config fields the hot path reads."""
 
-    arch: str = "xlmr"  # "xlmr" | "bert"
+    arch: str = "xlmr"  # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig)
     vocab_size: int = 250002
     hidden: int = 1024
     layers: int = 24
@@ -44,7 +44,7 @@ class EncoderConfig:
     max_pos: int = 8194
     type_vocab: int = 1
     pad_id: int = 1
-    ln_eps: float = 1e-5
+    ln_eps: float = 1e-5     # the RMSNorm epsilon for "qwen3"
     num_labels: int = 0
 
     @property
@@ -116,7 +116,7 @@ class EncoderPath:
     cls_workspace: Optional[str]  # read the full forward's hidden states at the sequence starts
     pool: str                    # CLS and mean pooling
     pool_mean: str
-    head: str                    # classification head; its workspace holds two padded [B, H] tiles of hidden-state elements
+    head: Optional[str]          # classification head; its workspace holds two padded [B, H] tiles of hidden-state elements
     scratch: str                 # _scratch keys of the forward's and the head's workspaces
     head_scratch: str
     hidden: torch.dtype          # element type of the hidden states
@@ -124,6 +124,7 @@ class EncoderPath:
     skinny: bool = False
     pool_writes_bf16: bool = True  # the pooling kernel writes the bf16 copy of an embedding (else it is rounded from fp32 here)
     no_fp8: Optional[str] = None   # why ``calibrate_fp8`` does not apply; None: it does
+    pool_last: Optional[str] = None  # last-token pooling (decoder embedders); None: the path has none
 
 
 BF16_PATH = EncoderPath(forward="tt_encoder_forward", workspace="tt_encoder_workspace_bytes",
@@ -134,6 +135,16 @@ FP16_PATH = EncoderPath(forward="tt_encoder_forward_f16", workspace="tt_encoder_
                         cls_forward="tt_encoder_forward_cls_f16", cls_workspace="tt_encoder_cls_workspace_bytes_f16",
                         pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head="tt_rerank_head_f16",
                         scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False)
+# the decoder embedder (Qwen3Model architecture, decoder.DecoderWeights): full forward, then last-token pooling; its hidden states
+# have the encoder's layout, so first-token and mean pooling read them with the encoder's kernels.  No CLS-only tail, no head.
+DECODER_BF16_PATH = EncoderPath(forward="tt_decoder_forward", workspace="tt_decoder_workspace_bytes", cls_forward=None,
+                                cls_workspace=None, pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None,
+                                scratch="enc", head_scratch="head", hidden=torch.bfloat16, pool_last="tt_embed_pool_last",
+                                no_fp8="the decoder embedder has no fp8 projections")
+DECODER_FP16_PATH = EncoderPath(forward="tt_decoder_forward_f16", workspace="tt_decoder_workspace_bytes_f16", cls_forward=None,
+                                cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
+                                scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
+                                pool_last="tt_embed_pool_last_f16", no_fp8="the decoder embedder has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -706,7 +717,8 @@ class Encoder:
 
     def embed_packed(self, batch: PackedBatch, pooling: str = "cls") -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (embeddings fp32 [B, H] L2-normalised, same rounded to bf16).  ``pooling``: "cls" (the BGE family: the last layer
-        runs for the CLS rows only) or "mean" (sentence-transformers mean pooling over a sequence's tokens: full last layer)."""
+        runs for the CLS rows only), "mean" (sentence-transformers mean pooling over a sequence's tokens: full last layer) or
+        "last" (the last token of every sequence: decoder embedders)."""
         p, dev = self.path, self.device
         B, H = len(batch.seq_len), self.cfg.hidden
         out = torch.empty((B, H), dtype=torch.float32, device=dev)
@@ -716,11 +728,16 @@ class Encoder:
         if pooling == "mean":
             hidden, starts, lens = self.forward_packed(batch, want_lens=True)
             name, rows = p.pool_mean, (starts.data_ptr(), lens.data_ptr())
+        elif pooling == "last":
+            if p.pool_last is None:
+                raise ValueError("last-token pooling needs a decoder path")
+            hidden, starts, lens = self.forward_packed(batch, want_lens=True)
+            name, rows = p.pool_last, (starts.data_ptr(), lens.data_ptr())
         elif pooling == "cls":
             hidden, cls_rows = self.cls_hidden_packed(batch)
             name, rows = p.pool, (cls_rows.data_ptr(),)
         else:
-            raise ValueError(f"pooling '{pooling}' (supported: 'cls', 'mean')")
+            raise ValueError(f"pooling '{pooling}' (supported: 'cls', 'mean', 'last')")
         with torch.cuda.device(dev):
             rc = getattr(self.lib, name)(hidden.data_ptr(), H, *rows, B, H, out.data_ptr(),
                                          out16.data_ptr() if out16 is not None else None, torch.cuda.current_stream(dev).cuda_stream)

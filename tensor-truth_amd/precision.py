@@ -121,6 +121,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
     from .encoder import Encoder
 
     mode = resolve(model_kwargs)
+    if getattr(cfg, "arch", "") == "qwen3":
+        return _build_decoder(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
     make, desc = _implementations()[impl]
     w = make(cfg, state, device)
@@ -134,4 +136,23 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
                        "path (about 1/16 of the bf16 rate; name torch_dtype=bfloat16 / float16 or TT_PRECISION for the "
                        "16-bit modes)", what, getattr(cfg, "hidden", -1), getattr(cfg, "heads", -1))
     logger.info("%s: precision = %s", what, desc)
+    return w, Encoder(w), desc
+
+
+def _build_decoder(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """Decoder embedders (Qwen3-Embedding): bf16 -- what the published checkpoints declare -- or fp16.  The reference precision
+    (fp32 semantics, what no torch_dtype means for the encoder family) has no decoder implementation: refused, never computed in
+    another precision behind the caller's back."""
+    import torch
+
+    from .decoder import DecoderWeights
+    from .encoder import Encoder
+
+    if mode not in ("bf16", "fp16"):
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for decoder embedders (Qwen3-Embedding); pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}} or {{'torch_dtype': 'float16'}}")
+    w = DecoderWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
+    desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
+    logger.info("%s: decoder embedder, precision = %s", what, desc)
     return w, Encoder(w), desc

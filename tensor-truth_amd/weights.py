@@ -21,11 +21,39 @@ import torch
 from .encoder import KNOWN_CONFIGS, EncoderConfig, synthetic_state, synthetic_state_device
 
 
-WEIGHT_FILES = ("model.safetensors", "pytorch_model.bin")
+WEIGHT_FILES = ("model.safetensors", "model.safetensors.index.json", "pytorch_model.bin")
+
+
+def _decoder_config_from_hf(d: dict) -> EncoderConfig:
+    """``model_type == "qwen3"`` (Qwen3-Embedding): every size from config.json, nothing assumed."""
+    from .decoder import DecoderConfig
+
+    # variants the decoder kernels do not compute are refused, never run as plain Qwen3 (no silent wrong vectors)
+    rope = d.get("rope_scaling") or d.get("rope_parameters") or {}     # transformers 4.x / 5.x spelling
+    rope_type = rope.get("rope_type", rope.get("type", "default"))
+    layer_types = sorted(set(d.get("layer_types") or ["full_attention"]))
+    bad = [f"{n}={v!r}" for n, v, ok in (
+        ("attention_bias", d.get("attention_bias", False), not d.get("attention_bias", False)),
+        ("rope_type", rope_type, rope_type == "default"),
+        ("use_sliding_window", d.get("use_sliding_window", False), not d.get("use_sliding_window", False)),
+        ("layer_types", layer_types, layer_types == ["full_attention"]),
+        ("hidden_act", d.get("hidden_act", "silu"), d.get("hidden_act", "silu") == "silu")) if not ok]
+    if bad:
+        raise NotImplementedError(f"qwen3 checkpoint with {', '.join(bad)}: the decoder embedder computes bias-free full causal "
+                                  "attention with default RoPE and SiLU only")
+    heads = d["num_attention_heads"]
+    return DecoderConfig(
+        arch="qwen3", vocab_size=d["vocab_size"], hidden=d["hidden_size"], layers=d["num_hidden_layers"], heads=heads,
+        ffn=d["intermediate_size"], max_pos=d["max_position_embeddings"], type_vocab=1, pad_id=0,
+        ln_eps=d.get("rms_norm_eps", 1e-6), num_labels=0, kv_heads=d.get("num_key_value_heads") or heads,
+        head_dim=d.get("head_dim") or 128,   # Qwen3Config's default (not hidden // heads)
+        rope_theta=float(d.get("rope_theta") or (d.get("rope_parameters") or {}).get("rope_theta") or 10000.0))
 
 
 def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
     mt = d.get("model_type", "xlm-roberta")
+    if mt == "qwen3":
+        return _decoder_config_from_hf(d)
     arch = "bert" if mt == "bert" else "xlmr"
     archs = " ".join(d.get("architectures", []))
     num_labels = 1 if "SequenceClassification" in archs else num_labels_default
@@ -65,19 +93,23 @@ def head_activation(model_name: str, model_dir: Optional[str], model_kwargs: Opt
     raise ValueError(f"cross-encoder activation '{name}' is not supported (Sigmoid or Identity)")
 
 
-def pooling_mode(model_dir: Optional[str]) -> str:
-    """The sentence-transformers pooling a checkpoint directory declares (``1_Pooling/config.json``): "cls", "mean", ... ;
-    "cls" when the directory declares nothing (the BGE models the reference defaults to are CLS + Normalize)."""
+def pooling_mode(model_dir: Optional[str], default: str = "cls") -> str:
+    """The sentence-transformers pooling a checkpoint directory declares (``1_Pooling/config.json``): "cls", "mean", "last"
+    (``pooling_mode_lasttoken``: the decoder embedders), ... ;
+    ``default`` when the directory declares nothing: "cls" for encoders (the BGE models the reference defaults to are CLS +
+    Normalize), "last" for decoder embedders (their first token has seen only itself)."""
     if not model_dir:
-        return "cls"
+        return default
     pc = os.path.join(model_dir, "1_Pooling", "config.json")
     if not os.path.exists(pc):
-        return "cls"
+        return default
     with open(pc) as f:
         d = json.load(f)
     on = [k[len("pooling_mode_"):] for k, v in d.items() if k.startswith("pooling_mode_") and v is True]
     if on == ["cls_token"]:
         return "cls"
+    if on == ["lasttoken"]:
+        return "last"
     return "+".join(sorted(on)) or "none"
 
 
@@ -107,12 +139,23 @@ def find_model_dir(model_name: str, model_kwargs: Optional[dict]) -> Optional[st
 
 
 def load_state(model_dir: str) -> Dict[str, torch.Tensor]:
-    """``model.safetensors`` if present, else the older ``pytorch_model.bin`` (tensors only, ``weights_only=True``)."""
+    """``model.safetensors`` if present, else the shards ``model.safetensors.index.json`` names, else the older
+    ``pytorch_model.bin`` (tensors only, ``weights_only=True``)."""
     st = os.path.join(model_dir, "model.safetensors")
     if os.path.exists(st):
         from safetensors.torch import load_file
 
         return load_file(st)
+    idx = os.path.join(model_dir, "model.safetensors.index.json")
+    if os.path.exists(idx):
+        from safetensors.torch import load_file
+
+        with open(idx) as f:
+            shards = sorted(set(json.load(f)["weight_map"].values()))
+        out: Dict[str, torch.Tensor] = {}
+        for sh in shards:
+            out.update(load_file(os.path.join(model_dir, sh)))
+        return out
     return torch.load(os.path.join(model_dir, "pytorch_model.bin"), map_location="cpu", weights_only=True)
 
 
@@ -134,6 +177,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
         if cfg is None:
             raise ValueError(f"no architecture known for '{model_name}': pass model_kwargs['encoder_config']")
         seed = int(mk["synthetic_seed"])
+        if cfg.arch == "qwen3":
+            from .decoder import synthetic_state as decoder_state
+
+            return cfg, decoder_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
@@ -141,3 +188,16 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
         f"weights for '{model_name}' not found: no model.safetensors under model_kwargs['model_dir'], "
         f"$TT_AMD_MODEL_DIR or the HF cache, and this environment has no network. "
         f"(Benchmarks/tests: pass model_kwargs={{'synthetic_seed': N}}.)")
+
+
+def prompts(model_dir: Optional[str]) -> Dict[str, str]:
+    """The sentence-transformers ``prompts`` a checkpoint directory declares (``config_sentence_transformers.json``), e.g. the
+    Qwen3-Embedding instruction under "query" and "" under "document"; {} when it declares none."""
+    if not model_dir:
+        return {}
+    pc = os.path.join(model_dir, "config_sentence_transformers.json")
+    if not os.path.exists(pc):
+        return {}
+    with open(pc) as f:
+        d = json.load(f)
+    return {str(k): str(v) for k, v in (d.get("prompts") or {}).items()}
