@@ -569,7 +569,8 @@ int tt_attention_x3_hd_f16(const void* qk_planes, int ld_qk, int q_col0, int k_c
                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len,
                            int head_dim, int cls_only, void* stream);
 
-/* ---- decoder embedder: Qwen3Model-architecture checkpoints (Qwen3-Embedding; csrc/decoder.hip) ------------------------------
+/* ---- decoder embedder / reranker: Qwen3Model-architecture checkpoints (Qwen3-Embedding, Qwen3ForSequenceClassification;
+ * csrc/decoder.hip) ------------------------------------------------------------------------------------------------------
  * The reference embeds with whatever Hugging Face model its config names (api/routes/startup.py:108-133,
  * app_utils/config_schema.py:41-61, services/model_manager.py:214-252); the Qwen3-Embedding model card runs it in bf16 with
  * left padding and pools the LAST token.  Pre-norm decoder block, no biases: RMSNorm -> QKV projection -> per-head RMSNorm of
@@ -604,6 +605,24 @@ size_t tt_decoder_workspace_bytes(const tt_decoder_weights* w, int n_rows);   /*
 int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* The pooled-row tail (rerankers, last-token embedders): the same forward, of which only ONE row per sequence is wanted.
+ * pool_row: device [n_seq], the absolute row of the token to keep, seq_start[b] <= pool_row[b] < seq_start[b] + seq_len[b] (a row
+ * outside its sequence gives a zero context for that sequence, never an access outside the batch).  Layers 0 .. layers-2 run as in
+ * tt_decoder_forward.  In the last layer Q, K and V are produced for every row (a pooled query attends to all keys before it), but
+ * attention, output projection + residual, the MLP and the final norm run for the n_seq pooled rows only, on compact buffers of
+ * P rows, P = n_seq rounded up to 64 (n_seq <= 256) or to 256.  hidden_out: [P][H]; row b < n_seq holds the bits row pool_row[b]
+ * of tt_decoder_forward's output holds (the projections give a row the same bits whatever else is in the batch; the attention
+ * evaluates the 16-query tile of pool_row[b] exactly as the full kernel does and stores that one query); rows n_seq .. P-1 are
+ * zero.  layers == 0: embedding -> final norm of the pooled rows.  Same workspace as the full forward (the compact buffers reuse it). */
+size_t tt_decoder_rows_workspace_bytes(const tt_decoder_weights* w, int n_rows, int n_seq);   /* 0 for a refused shape */
+int tt_decoder_forward_rows(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len,
+                            const int32_t* pool_row, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Score head of Qwen3ForSequenceClassification (one label, Linear(H, 1, bias=False)): logits[b] = hidden[b] . score_w in fp32,
+ * scores[b] = sigmoid(logits[b]); hidden [n_seq][ld] in the element type (the tail's output), score_w fp32 [H], both 16-byte
+ * aligned; logits optional. */
+int tt_decoder_score(const void* hidden, int ld, const float* score_w, int n_seq, int hidden_size, float* scores, float* logits,
+                     void* stream);
 /* sentence-transformers Pooling(lasttoken) + Normalize: out[b] = h[r] / ||h[r]||_2 with r = seq_start[b] + seq_len[b] - 1;
  * out_16 (optional) the same vector in the element type (bf16: ready to be a scan query). */
 int tt_embed_pool_last(const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden_size,
@@ -625,6 +644,12 @@ size_t tt_decoder_workspace_bytes_f16(const tt_decoder_weights* w, int n_rows);
 int tt_decoder_forward_f16(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                            void* workspace, size_t workspace_bytes, void* stream);
+size_t tt_decoder_rows_workspace_bytes_f16(const tt_decoder_weights* w, int n_rows, int n_seq);
+int tt_decoder_forward_rows_f16(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                                const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len,
+                                const int32_t* pool_row, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+int tt_decoder_score_f16(const void* hidden, int ld, const float* score_w, int n_seq, int hidden_size, float* scores, float* logits,
+                         void* stream);
 int tt_embed_pool_last_f16(const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden_size,
                            float* out_f32, void* out_16, void* stream);
 int tt_qk_norm_rope_f16(void* qkv, int ld, const int32_t* pos, const float* q_norm, const float* k_norm, int n_rows, int heads,

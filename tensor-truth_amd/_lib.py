@@ -180,6 +180,10 @@ SIGNATURES = {
     "tt_decoder_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "tt_decoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_decoder_rows_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "tt_decoder_forward_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_decoder_score": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_embed_pool_last": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_qk_norm_rope": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
                              c_void_p, c_int, c_void_p]),
@@ -188,6 +192,10 @@ SIGNATURES = {
     "tt_decoder_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
     "tt_decoder_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_decoder_rows_workspace_bytes_f16": (c_size_t, [c_void_p, c_int, c_int]),
+    "tt_decoder_forward_rows_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_decoder_score_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_embed_pool_last_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_qk_norm_rope_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float,
                                  c_void_p, c_int, c_void_p]),

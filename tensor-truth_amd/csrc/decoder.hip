@@ -1,5 +1,6 @@
-// Decoder embedders (Qwen3Model architecture: Qwen3-Embedding): the whole-model forward, last-token pooling and the kernels
-// that only this family needs (include/tt_hip.h, "decoder embedder").  The projections run on the encoder's GEMMs (gemm.hip).
+// Decoder embedders and rerankers (Qwen3Model architecture: Qwen3-Embedding; Qwen3ForSequenceClassification): the whole-model
+// forward, its pooled-row tail (the last layer for one row per sequence), last-token pooling, the score head and the kernels that
+// only this family needs (include/tt_hip.h, "decoder embedder").  The projections run on the encoder's GEMMs (gemm.hip).
 //
 // Layer schedule (pre-norm block, no biases; one rounding to the element type per kernel output):
 //   x    = RMSNorm(h) * g_attn                           [T][H]
@@ -197,11 +198,14 @@ __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __re
 // Softmax in fp32 with a running maximum (log2 domain), P rounded to the element type for the product; the denominator sums the
 // rounded P, so the weights of a row sum to one as they are applied.
 // One (tile t, sequence b, head h) per call; the kernel below walks the sequences (a grid's y extent stops at 65535).
+// keep_row < 0: every query of the tile is stored, at its own row of `out`.  keep_row >= 0 (the pooled-row tail): only the query
+// at absolute row keep_row is stored, at row out_row of `out` -- the same arithmetic, so the same bits as the full tile gives it.
 template <int D>
 __device__ __forceinline__ void dec_attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
                                                    const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out, int ld_out,
                                                    const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len,
-                                                   int n_rows, int group, float scale_log2, int b, int h, int t) {
+                                                   int n_rows, int group, float scale_log2, int b, int h, int t, int keep_row = -1,
+                                                   int out_row = 0) {
     const int s0 = seq_start[b], L = seq_len[b];
     if (s0 < 0 || 16 * t >= L) return;
     const int s_end = min(s0 + L, n_rows);
@@ -275,9 +279,9 @@ __device__ __forceinline__ void dec_attention_tile(const uint16_t* __restrict__ 
     }
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
-    if (qrow < s_end) {   // (the only lane-dependent branch: the wave is whole again for the next sequence's tile)
+    if (qrow < s_end && (keep_row < 0 || qrow == keep_row)) {   // (the only lane-dependent branch: the wave is whole again for the next sequence's tile)
         const float inv = 1.0f / l;
-        uint16_t* dst = out + (size_t)qrow * ld_out + h * D + 4 * g;
+        uint16_t* dst = out + (size_t)(keep_row < 0 ? qrow : out_row) * ld_out + h * D + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < D / 16; ++dt)
             *reinterpret_cast<uint2*>(dst + dt * 16) = uint2{pack_e2(o[dt][0] * inv, o[dt][1] * inv),
@@ -295,6 +299,65 @@ __global__ __launch_bounds__(64) void dec_attention_kernel(const uint16_t* __res
     for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
         dec_attention_tile<D>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, scale_log2, b,
                               blockIdx.z, t);
+}
+
+// The pooled-row tail: per (sequence b, query head) only the 16-query tile that holds pool_row[b], and of it only that query,
+// stored at compact row b of `out` [n_seq][ld_out].  A pool_row outside its sequence stores nothing (the row stays as it was).
+template <int D>
+__global__ __launch_bounds__(64) void dec_attention_rows_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
+                                                                const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
+                                                                int ld_out, const int32_t* __restrict__ seq_start,
+                                                                const int32_t* __restrict__ seq_len,
+                                                                const int32_t* __restrict__ pool_row, int n_seq, int n_rows,
+                                                                int group, float scale_log2) {
+    for (int b = blockIdx.x; b < n_seq; b += gridDim.x) {   // (wave-uniform)
+        const int r = pool_row[b], s0 = seq_start[b], L = seq_len[b];
+        if (s0 < 0 || r < s0 || r - s0 >= L || r >= n_rows) continue;
+        dec_attention_tile<D>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, scale_log2, b,
+                              blockIdx.y, (r - s0) >> 4, r, b);
+    }
+}
+
+// ---- gather of the pooled rows: dst[b] = src[rows[b]] for b < n (a row outside [0, n_rows) gives zeros), zeros up to n_pad ------
+__global__ __launch_bounds__(256) void dec_gather_rows_kernel(const uint16_t* __restrict__ src, int ld, const int32_t* __restrict__ rows,
+                                                              int n, int n_pad, int n_rows, int H, uint16_t* __restrict__ dst) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n_pad) return;
+    const int r = b < n ? rows[b] : -1;
+    const bool ok = r >= 0 && r < n_rows;
+    for (int c = lane; c < H / 8; c += 64)
+        reinterpret_cast<uint4*>(dst + (size_t)b * H)[c] =
+            ok ? reinterpret_cast<const uint4*>(src + (size_t)r * ld)[c] : uint4{0u, 0u, 0u, 0u};
+}
+
+// ---- score head of *ForSequenceClassification (one label, no bias): logit[b] = hidden[b] . w, score[b] = sigmoid(logit[b]) ------
+// fp32 arithmetic, one wave per row; lane l sums the chunks l, l + 64 in ascending order, then the butterfly.
+__global__ __launch_bounds__(256) void dec_score_kernel(const uint16_t* __restrict__ hidden, int ld, const float* __restrict__ w, int n,
+                                                        int H, float* __restrict__ scores, float* __restrict__ logits) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n) return;
+    const uint4* src = reinterpret_cast<const uint4*>(hidden + (size_t)b * ld);
+    float acc = 0.f;
+    for (int c = lane; c < H / 8; c += 64) {
+        const uint4 v = src[c];
+        const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+        const float4 w0 = reinterpret_cast<const float4*>(w)[2 * c], w1 = reinterpret_cast<const float4*>(w)[2 * c + 1];
+        acc += elo(u[0]) * w0.x;
+        acc += ehi(u[0]) * w0.y;
+        acc += elo(u[1]) * w0.z;
+        acc += ehi(u[1]) * w0.w;
+        acc += elo(u[2]) * w1.x;
+        acc += ehi(u[2]) * w1.y;
+        acc += elo(u[3]) * w1.z;
+        acc += ehi(u[3]) * w1.w;
+    }
+    acc = dec_wave_sum(acc);
+    if (lane == 0) {
+        scores[b] = 1.0f / (1.0f + expf(-acc));
+        if (logits) logits[b] = acc;
+    }
 }
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
@@ -381,36 +444,31 @@ int attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, const 
     return TT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t tt_decoder_workspace_bytes(const tt_decoder_weights* w, int n_rows) {
-    if (!w || n_rows <= 0 || check_weights(w) != TT_OK) return 0;
-    return dec_plan(w, n_rows).total;
+int attention_rows_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, const uint16_t* vt, int ldvt, uint16_t* out, int ld_out,
+                          const int32_t* seq_start, const int32_t* seq_len, const int32_t* pool_row, int n_seq, int n_rows, int heads,
+                          int kv_heads, int D, hipStream_t st) {
+    const dim3 grid(std::min(n_seq, 1 << 20), heads);
+    const float scale_log2 = 1.4426950408889634f / sqrtf((float)D);
+    TtProfScope prof(TT_K_ATTENTION, st);
+    if (D == 128)
+        hipLaunchKernelGGL(dec_attention_rows_kernel<128>, grid, dim3(64), 0, st, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out,
+                           seq_start, seq_len, pool_row, n_seq, n_rows, heads / kv_heads, scale_log2);
+    else
+        hipLaunchKernelGGL(dec_attention_rows_kernel<64>, grid, dim3(64), 0, st, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out,
+                           seq_start, seq_len, pool_row, n_seq, n_rows, heads / kv_heads, scale_log2);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
 }
 
-int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
-                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
-                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_weights(w)) return rc;
-    TT_CHECK_ARG(type_ids == nullptr, "a decoder has no token types: type_ids must be NULL");
-    TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
-                 "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
-    TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
-    TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
+// rows of the compact buffers of the pooled-row tail: up to 256 sequences a multiple of 64 (the skinny GEMMs), else of 256
+int rows_pad(int n_seq) { return (n_seq <= 256 && tt_gemm_skinny_enabled()) ? (n_seq + 63) / 64 * 64 : (n_seq + 255) / 256 * 256; }
+
+// The forward behind tt_decoder_forward (pool_row == nullptr: every layer over every row, out [n_rows][H]) and
+// tt_decoder_forward_rows (the last layer's attention, output projection, MLP and the final norm for the rows pool_row names only,
+// out [rows_pad(n_seq)][H]).  Arguments are checked by the callers.
+int dec_run(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
+            const int32_t* pool_row, int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
     const DecWs e = dec_plan(w, n_rows);
-    if (!workspace || workspace_bytes < e.total) {
-        tt_set_error("tt_decoder_forward: workspace %zu < required %zu bytes", workspace_bytes, e.total);
-        return TT_E_WORKSPACE;
-    }
-    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
-    for (int l = 0; l < w->layers; ++l) {
-        const tt_decoder_layer_weights& lw = w->layer[l];
-        TT_CHECK_ARG(lw.qkv_w && lw.q_norm && lw.k_norm && lw.o_w && lw.attn_norm && lw.ffn_norm && lw.gate_up_w && lw.down_w,
-                     "layer %d has a null weight pointer", l);
-    }
-    hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, D = w->head_dim, nq = w->heads, nkv = w->kv_heads, T = n_rows;
     const int nqkv = (nq + 2 * nkv) * D;
@@ -431,6 +489,35 @@ int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const in
         hipLaunchKernelGGL(dec_embed_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, ha);
         TT_CHECK_LAUNCH();
     }
+    // the rows of one layer's second half: M rows of residual `res` and context `c`, through h1 (and x, gu, act) into `out`
+    auto block_tail = [&](const tt_decoder_layer_weights& lw, int M, const uint16_t* c, const uint16_t* res, uint16_t* h1, uint16_t* xn,
+                          uint16_t* out) -> int {
+        GemmParams go{};
+        go.A = c; go.lda = nq * D; go.W = (const uint16_t*)lw.o_w; go.bias = zero;
+        go.residual = res; go.ldr = H; go.C = h1; go.ldc = H; go.M = M; go.N = H; go.K = nq * D;
+        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
+        if (int rc = rmsnorm_launch(h1, xn, lw.ffn_norm, M, H, w->rms_eps, st)) return rc;
+        GemmParams g1{};
+        g1.A = xn; g1.lda = H; g1.W = (const uint16_t*)lw.gate_up_w; g1.bias = zero;
+        g1.C = gu; g1.ldc = 2 * F; g1.M = M; g1.N = 2 * F; g1.K = H;
+        if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
+        {
+            TtProfScope prof(TT_K_ROWOPS, st);
+            const int64_t chunks = (int64_t)M * (F / 8);
+            hipLaunchKernelGGL(dec_swiglu_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, gu, act, chunks, F);
+            TT_CHECK_LAUNCH();
+        }
+        GemmParams g2{};
+        g2.A = act; g2.lda = F; g2.W = (const uint16_t*)lw.down_w; g2.bias = zero;
+        g2.residual = h1; g2.ldr = H; g2.C = out; g2.ldc = H; g2.M = M; g2.N = H; g2.K = F;
+        return tt_gemm_launch(g2, TT_EPI_RESIDUAL, st);
+    };
+    auto gather = [&](uint16_t* dst, int M) -> int {
+        TtProfScope prof(TT_K_ROWOPS, st);
+        hipLaunchKernelGGL(dec_gather_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ha, H, pool_row, n_seq, M, T, H, dst);
+        TT_CHECK_LAUNCH();
+        return TT_OK;
+    };
     for (int l = 0; l < w->layers; ++l) {
         const tt_decoder_layer_weights& lw = w->layer[l];
         if (int rc = rmsnorm_launch(ha, x, lw.attn_norm, T, H, w->rms_eps, st)) return rc;
@@ -441,30 +528,102 @@ int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const in
         if (int rc = qknorm_rope_launch(qkv, nqkv, pos, lw.q_norm, lw.k_norm, T, nq, nkv, D, w->rms_eps, w->rope_theta, vt, 8 * nkv * D,
                                         st))
             return rc;
+        if (pool_row && l == w->layers - 1) {
+            // The last layer for the pooled rows only, on compact [M][...] buffers that reuse the full-size ones this layer no longer
+            // needs (launches of one stream run in order): context -> ctx, residual rows of ha -> hb, h1 -> x, its norm -> ha,
+            // the layer's output -> hb.  Rows n_seq .. M - 1 are zero and stay zero through every step.
+            const int M = rows_pad(n_seq);
+            TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)M * nq * D * 2, st));
+            if (int rc = attention_rows_launch(qkv, nqkv, 0, nq * D, vt, 8 * nkv * D, ctx, nq * D, seq_start, seq_len, pool_row, n_seq, T,
+                                               nq, nkv, D, st))
+                return rc;
+            if (int rc = gather(hb, M)) return rc;
+            if (int rc = block_tail(lw, M, ctx, hb, x, ha, hb)) return rc;
+            return rmsnorm_launch(hb, (uint16_t*)hidden_out, w->final_norm, M, H, w->rms_eps, st);
+        }
         if (int rc = attention_launch(qkv, nqkv, 0, nq * D, vt, 8 * nkv * D, ctx, nq * D, seq_start, seq_len, n_seq, T, nq, nkv, D,
                                       max_len, st))
             return rc;
-        GemmParams go{};
-        go.A = ctx; go.lda = nq * D; go.W = (const uint16_t*)lw.o_w; go.bias = zero;
-        go.residual = ha; go.ldr = H; go.C = hb; go.ldc = H; go.M = T; go.N = H; go.K = nq * D;
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = rmsnorm_launch(hb, x, lw.ffn_norm, T, H, w->rms_eps, st)) return rc;
-        GemmParams g1{};
-        g1.A = x; g1.lda = H; g1.W = (const uint16_t*)lw.gate_up_w; g1.bias = zero;
-        g1.C = gu; g1.ldc = 2 * F; g1.M = T; g1.N = 2 * F; g1.K = H;
-        if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            const int64_t chunks = (int64_t)T * (F / 8);
-            hipLaunchKernelGGL(dec_swiglu_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, gu, act, chunks, F);
-            TT_CHECK_LAUNCH();
-        }
-        GemmParams g2{};
-        g2.A = act; g2.lda = F; g2.W = (const uint16_t*)lw.down_w; g2.bias = zero;
-        g2.residual = hb; g2.ldr = H; g2.C = ha; g2.ldc = H; g2.M = T; g2.N = H; g2.K = F;
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
+        if (int rc = block_tail(lw, T, ctx, ha, hb, x, ha)) return rc;
+    }
+    if (pool_row) {   // a model without layers: embedding -> final norm of the pooled rows
+        const int M = rows_pad(n_seq);
+        if (int rc = gather(hb, M)) return rc;
+        return rmsnorm_launch(hb, (uint16_t*)hidden_out, w->final_norm, M, H, w->rms_eps, st);
     }
     return rmsnorm_launch(ha, (uint16_t*)hidden_out, w->final_norm, T, H, w->rms_eps, st);
+}
+
+int check_forward_args(const char* what, const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, const void* hidden_out,
+                       const void* workspace, size_t workspace_bytes) {
+    if (int rc = check_weights(w)) return rc;
+    TT_CHECK_ARG(type_ids == nullptr, "a decoder has no token types: type_ids must be NULL");
+    TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
+                 "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
+    TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
+    TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
+    const DecWs e = dec_plan(w, n_rows);
+    if (!workspace || workspace_bytes < e.total) {
+        tt_set_error("%s: workspace %zu < required %zu bytes", what, workspace_bytes, e.total);
+        return TT_E_WORKSPACE;
+    }
+    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    for (int l = 0; l < w->layers; ++l) {
+        const tt_decoder_layer_weights& lw = w->layer[l];
+        TT_CHECK_ARG(lw.qkv_w && lw.q_norm && lw.k_norm && lw.o_w && lw.attn_norm && lw.ffn_norm && lw.gate_up_w && lw.down_w,
+                     "layer %d has a null weight pointer", l);
+    }
+    return TT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tt_decoder_workspace_bytes(const tt_decoder_weights* w, int n_rows) {
+    if (!w || n_rows <= 0 || check_weights(w) != TT_OK) return 0;
+    return dec_plan(w, n_rows).total;
+}
+
+int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_forward_args("tt_decoder_forward", w, ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out,
+                                    workspace, workspace_bytes))
+        return rc;
+    return dec_run(w, ids, pos, seq_start, seq_len, nullptr, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+}
+
+size_t tt_decoder_rows_workspace_bytes(const tt_decoder_weights* w, int n_rows, int n_seq) {
+    if (!w || n_rows <= 0 || n_seq <= 0 || n_seq > n_rows || check_weights(w) != TT_OK) return 0;
+    return dec_plan(w, n_rows).total;   // the compact buffers of the tail reuse the full-size ones (rows_pad(n_seq) <= the padded n_rows)
+}
+
+int tt_decoder_forward_rows(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len,
+                            const int32_t* pool_row, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_forward_args("tt_decoder_forward_rows", w, ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len,
+                                    hidden_out, workspace, workspace_bytes))
+        return rc;
+    TT_CHECK_ARG(pool_row != nullptr, "pool_row is NULL (one row per sequence)");
+    TT_CHECK_ARG(n_seq <= n_rows, "n_seq=%d exceeds n_rows=%d", n_seq, n_rows);
+    return dec_run(w, ids, pos, seq_start, seq_len, pool_row, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+}
+
+int tt_decoder_score(const void* hidden, int ld, const float* score_w, int n_seq, int hidden_size, float* scores, float* logits,
+                     void* stream) {
+    TT_CHECK_ARG(n_seq > 0, "n_seq=%d", n_seq);
+    TT_CHECK_ARG(hidden && score_w && scores, "null pointer");
+    TT_CHECK_ARG(hidden_size > 0 && hidden_size % 8 == 0 && hidden_size <= 1024 && ld >= hidden_size && ld % 8 == 0,
+                 "hidden=%d ld=%d", hidden_size, ld);
+    TT_CHECK_ARG(((uintptr_t)hidden % 16) == 0 && ((uintptr_t)score_w % 16) == 0, "hidden and score_w must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(dec_score_kernel, dim3((n_seq + 3) / 4), dim3(256), 0, st, (const uint16_t*)hidden, ld, score_w, n_seq,
+                       hidden_size, scores, logits);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
 }
 
 int tt_embed_pool_last(const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden_size,

@@ -1,5 +1,6 @@
-"""Decoder embedders (``Qwen3Model`` architecture: Qwen3-Embedding) on the HIP path: weights in the layout of
-``tt_decoder_weights`` (include/tt_hip.h), driven by the one host-side ``encoder.Encoder`` through the ``DECODER_*_PATH`` records.
+"""Decoder embedders (``Qwen3Model`` architecture: Qwen3-Embedding) and rerankers (``Qwen3ForSequenceClassification``: the form
+the Qwen3-Reranker checkpoints take for cross-encoder use) on the HIP path: weights in the layout of ``tt_decoder_weights``
+(include/tt_hip.h), driven by the one host-side ``encoder.Encoder`` through the ``DECODER_*_PATH`` records.
 
 The reference embeds with whatever Hugging Face model its config names (``api/routes/startup.py:108-133``,
 ``services/model_manager.py:214-252``); for the Qwen3-Embedding checkpoints sentence-transformers runs ``Qwen3Model`` and pools
@@ -12,7 +13,7 @@ from __future__ import annotations
 import ctypes
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List
+from typing import Dict, Iterable, List, Optional
 
 import torch
 
@@ -22,12 +23,15 @@ from .encoder import DECODER_BF16_PATH, DECODER_FP16_PATH, EncoderConfig, _strip
 @dataclass(frozen=True)
 class DecoderConfig(EncoderConfig):
     """The ``EncoderConfig`` fields (``ln_eps`` = the RMSNorm epsilon) plus grouped-query attention -- ``kv_heads`` KV heads of
-    ``head_dim`` each -- and the RoPE base."""
+    ``head_dim`` each -- and the RoPE base.  ``num_labels == 1``: a ``*ForSequenceClassification`` checkpoint, whose head reads
+    the token ``encoder.pooled_rows`` names: with ``pad_token_id`` set the rightmost token that differs from it, else the last
+    (``pad_id`` is something else: the filler ``pack_tokens`` writes into rows of no sequence)."""
 
     arch: str = "qwen3"
     kv_heads: int = 0
     head_dim: int = 0
     rope_theta: float = 0.0
+    pad_token_id: Optional[int] = None
 
 
 class _DecLayerW(Structure):
@@ -52,7 +56,7 @@ def state_names(cfg: DecoderConfig) -> List[str]:
         names += [p + "self_attn.q_norm.weight", p + "self_attn.k_norm.weight", p + "input_layernorm.weight",
                   p + "post_attention_layernorm.weight"]
         names += [p + f"mlp.{n}_proj.weight" for n in ("gate", "up", "down")]
-    return names + ["norm.weight"]
+    return names + ["norm.weight"] + (["score.weight"] if cfg.num_labels else [])
 
 
 def check_config(cfg: DecoderConfig) -> None:
@@ -71,7 +75,9 @@ def check_config(cfg: DecoderConfig) -> None:
 class DecoderWeights:
     """Device-resident ``Qwen3Model`` weights for ``tt_decoder_forward`` (bf16) or ``tt_decoder_forward_f16`` (fp16): the
     projections in the element type -- q/k/v rows concatenated into one matrix, gate/up into another -- and the RMSNorm weights
-    in fp32."""
+    in fp32.  A ``*ForSequenceClassification`` checkpoint (``cfg.num_labels``) brings ``score.weight``: ``score_w``, fp32 [H], the
+    operand of ``tt_decoder_score`` (transformers' head is ``Linear(H, 1, bias=False)``: a ``score.bias`` is refused like any
+    other tensor the forward would not read)."""
 
     def __init__(self, cfg: DecoderConfig, state: Dict[str, torch.Tensor], device: torch.device,
                  dtype: torch.dtype = torch.bfloat16):
@@ -80,6 +86,8 @@ class DecoderWeights:
         if device.type != "cuda":
             raise RuntimeError("DecoderWeights need a HIP device; tensor_truth_amd has no CPU path")
         check_config(cfg)
+        if cfg.num_labels not in (0, 1):
+            raise ValueError("only single-label (sigmoid) cross-encoder heads are supported")
         self.cfg, self.device, self.dtype = cfg, device, dtype
         self.path = DECODER_FP16_PATH if dtype == torch.float16 else DECODER_BF16_PATH
         self.gemm_dtype = dtype
@@ -90,8 +98,9 @@ class DecoderWeights:
         if missing:
             raise ValueError(f"checkpoint is not a Qwen3Model of {cfg}: missing {missing[:4]}")
         # tensors this forward would not read (q/k/v biases, ...) mean another architecture variant: refused, not ignored.  A
-        # *ForCausalLM export's lm_head is the only extra that plays no part in the embedding.
-        extra = sorted(set(sd) - set(names) - {"lm_head.weight"})
+        # *ForCausalLM export's lm_head, and a *ForSequenceClassification export's score head under an embedder's config, are the
+        # only extras that play no part in the embedding.
+        extra = sorted(set(sd) - set(names) - {"lm_head.weight", "score.weight"})
         if extra:
             raise NotImplementedError(f"checkpoint carries tensors the decoder embedder does not compute: {extra[:4]}")
 
@@ -123,6 +132,11 @@ class DecoderWeights:
         self.struct = _DecW(hidden=H, layers=cfg.layers, heads=nq, kv_heads=nkv, head_dim=D, ffn=F, vocab=cfg.vocab_size,
                             rms_eps=cfg.ln_eps, rope_theta=cfg.rope_theta, embed=emb.data_ptr(),
                             layer=ctypes.cast(self._layers, POINTER(_DecLayerW)), final_norm=vec("norm.weight").data_ptr())
+        self.score_w: Optional[torch.Tensor] = None
+        if cfg.num_labels:
+            if tuple(sd["score.weight"].shape) != (1, H):
+                raise ValueError(f"score.weight {tuple(sd['score.weight'].shape)} does not match {cfg} (expected (1, {H}))")
+            self.score_w = self._kept(sd["score.weight"].reshape(H).to(device=device, dtype=torch.float32).contiguous())
 
     def _kept(self, t: torch.Tensor) -> torch.Tensor:
         self._keep.append(t)
@@ -159,6 +173,8 @@ def synthetic_state(cfg: DecoderConfig, seed: int = 0) -> Dict[str, torch.Tensor
         sd[p + "mlp.gate_proj.weight"] = rnd(F, H)
         sd[p + "mlp.up_proj.weight"] = rnd(F, H)
         sd[p + "mlp.down_proj.weight"] = rnd(H, F)
+    if cfg.num_labels:
+        sd["score.weight"] = rnd(cfg.num_labels, H, std=0.15)
     return sd
 
 

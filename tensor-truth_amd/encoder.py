@@ -125,6 +125,9 @@ class EncoderPath:
     pool_writes_bf16: bool = True  # the pooling kernel writes the bf16 copy of an embedding (else it is rounded from fp32 here)
     no_fp8: Optional[str] = None   # why ``calibrate_fp8`` does not apply; None: it does
     pool_last: Optional[str] = None  # last-token pooling (decoder embedders); None: the path has none
+    rows_forward: Optional[str] = None    # decoder paths: the forward whose last layer runs for ONE row per sequence only
+    rows_workspace: Optional[str] = None  # (``pooled_rows``), and its workspace size
+    score: Optional[str] = None      # decoder paths: the *ForSequenceClassification score head over those rows
 
 
 BF16_PATH = EncoderPath(forward="tt_encoder_forward", workspace="tt_encoder_workspace_bytes",
@@ -136,15 +139,19 @@ FP16_PATH = EncoderPath(forward="tt_encoder_forward_f16", workspace="tt_encoder_
                         pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head="tt_rerank_head_f16",
                         scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False)
 # the decoder embedder (Qwen3Model architecture, decoder.DecoderWeights): full forward, then last-token pooling; its hidden states
-# have the encoder's layout, so first-token and mean pooling read them with the encoder's kernels.  No CLS-only tail, no head.
+# have the encoder's layout, so first-token and mean pooling read them with the encoder's kernels.  Its one-row-per-sequence tail
+# (``rows_forward``: last-token pooling, and the classification checkpoints' score head) keeps whichever row ``pooled_rows`` names.
 DECODER_BF16_PATH = EncoderPath(forward="tt_decoder_forward", workspace="tt_decoder_workspace_bytes", cls_forward=None,
                                 cls_workspace=None, pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None,
                                 scratch="enc", head_scratch="head", hidden=torch.bfloat16, pool_last="tt_embed_pool_last",
-                                no_fp8="the decoder embedder has no fp8 projections")
+                                rows_forward="tt_decoder_forward_rows", rows_workspace="tt_decoder_rows_workspace_bytes",
+                                score="tt_decoder_score", no_fp8="the decoder embedder has no fp8 projections")
 DECODER_FP16_PATH = EncoderPath(forward="tt_decoder_forward_f16", workspace="tt_decoder_workspace_bytes_f16", cls_forward=None,
                                 cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
                                 scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
-                                pool_last="tt_embed_pool_last_f16", no_fp8="the decoder embedder has no fp8 projections")
+                                pool_last="tt_embed_pool_last_f16", rows_forward="tt_decoder_forward_rows_f16",
+                                rows_workspace="tt_decoder_rows_workspace_bytes_f16", score="tt_decoder_score_f16",
+                                no_fp8="the decoder embedder has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -536,6 +543,22 @@ def pack_token_matrix(ids2d: np.ndarray, cfg: EncoderConfig, type_ids2d: Optiona
     return PackedBatch(ids, pos, types, starts, lens, int(n_rows), int(length), int(n * length))
 
 
+def pooled_rows(batch: PackedBatch, pad_token_id: Optional[int] = None) -> np.ndarray:
+    """-> int32 [B]: the absolute row of the token a decoder's one-row-per-sequence tail keeps for each sequence of ``batch``.
+    transformers' rule for ``*ForSequenceClassification`` decoders, restated: with ``pad_token_id`` set, the RIGHTMOST token whose
+    id differs from it -- position 0 if the sequence holds nothing else -- and with ``pad_token_id`` None the last token (what
+    last-token pooling reads too).  Causal attention makes the tokens behind the pooled one irrelevant to it.  One vectorised
+    pass over the ids of the batch as packed (i.e. after truncation)."""
+    starts, lens = batch.seq_start.astype(np.int64), batch.seq_len.astype(np.int64)
+    if pad_token_id is None:
+        return (starts + lens - 1).astype(np.int32)
+    first = np.zeros(len(lens), dtype=np.int64)
+    np.cumsum(lens[:-1], out=first[1:])
+    within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(first, lens)
+    keep = batch.ids[np.repeat(starts, lens) + within] != pad_token_id
+    return (starts + np.maximum.reduceat(np.where(keep, within, 0), first)).astype(np.int32)
+
+
 class _Scratch:
     """Workspace buffers keyed by (kind, device, HIP stream): launches on one stream execute in order, so every
     forward enqueued on that stream can reuse ONE buffer -- whichever host thread enqueues it -- as long as a whole
@@ -633,10 +656,11 @@ class Encoder:
         # one forward (scratch lookup + every launch of it) is enqueued atomically: the workspace is shared per stream
         self._enqueue_lock = _ENQUEUE_LOCKS.setdefault((self.device.type, self.device.index), threading.Lock())
 
-    def _upload(self, batch: PackedBatch):
-        """Token arrays of a batch -> device int32 views (ids, pos, types | None, seq_start, seq_len): one pinned
-        staging buffer, one asynchronous host-to-device copy on the current stream."""
-        parts = [batch.ids, batch.pos, batch.types, batch.seq_start, batch.seq_len]
+    def _upload(self, batch: PackedBatch, *more: np.ndarray):
+        """Token arrays of a batch -> device int32 views (ids, pos, types | None, seq_start, seq_len, and one per int32 array of
+        ``more``: the pooled rows of a decoder's tail): one pinned staging buffer, one asynchronous host-to-device copy on the
+        current stream."""
+        parts = [batch.ids, batch.pos, batch.types, batch.seq_start, batch.seq_len, *more]
         offs, total = [], 0
         for a in parts:
             offs.append(total)
@@ -715,6 +739,42 @@ class Encoder:
         cls, _, _ = self._run(p.cls_forward, p.cls_workspace, self._padded(batch), b_pad, B)
         return cls, torch.arange(B, dtype=torch.int32, device=self.device)
 
+    def rows_hidden_packed(self, batch: PackedBatch, rows: np.ndarray) -> torch.Tensor:
+        """Decoder paths: -> [pad(B), H], row b = the final hidden state of row ``rows[b]`` of ``batch`` (``pooled_rows``), the
+        bits the full forward gives that row.  The last layer's attention, output projection and MLP run for those rows only
+        (``tt_decoder_forward_rows``); pad(B) as ``cls_hidden_packed`` pads, rows B.. zero."""
+        p, dev, w = self.path, self.device, ctypes.byref(self.w.struct)
+        if p.rows_forward is None:
+            raise RuntimeError("this path has no one-row-per-sequence forward")
+        B = len(batch.seq_len)
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.shape != (B,) or (rows < batch.seq_start).any() or (rows >= batch.seq_start + batch.seq_len).any():
+            raise ValueError("pooled rows: one row inside each sequence is needed")
+        batch = self._padded(batch)
+        ids, pos, types, starts, lens, pool = self._upload(batch, rows)
+        if types is not None:
+            raise ValueError("a decoder has no token types")
+        out = torch.empty((_round_rows(B), self.cfg.hidden), dtype=p.hidden, device=dev)
+        need = getattr(self.lib, p.rows_workspace)(w, batch.n_rows, B)
+        with self._enqueue_lock, torch.cuda.device(dev):
+            ws, base = _scratch.get(p.scratch, dev, need)
+            rc = getattr(self.lib, p.rows_forward)(w, ids.data_ptr(), pos.data_ptr(), None, starts.data_ptr(), lens.data_ptr(), B,
+                                                   batch.n_rows, batch.max_len, pool.data_ptr(), out.data_ptr(), base, need,
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, p.rows_forward)
+        return out
+
+    def _compact_rows(self, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(0 .. n-1, ones) as int32 device tensors: the ``seq_start`` / ``seq_len`` under which the pooling kernels read row b of a
+        compact [B, H] buffer for sequence b.  Built once per size class, on the stream that first asks."""
+        have = getattr(self, "_compact", None)
+        if have is None or have[0].numel() < n:
+            cap = max(1024, 1 << (n - 1).bit_length())
+            have = (torch.arange(cap, dtype=torch.int32, device=self.device), torch.ones(cap, dtype=torch.int32, device=self.device))
+            torch.cuda.current_stream(self.device).synchronize()      # (once per size class: other streams read them later)
+            self._compact = have
+        return have[0][:n], have[1][:n]
+
     def embed_packed(self, batch: PackedBatch, pooling: str = "cls") -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (embeddings fp32 [B, H] L2-normalised, same rounded to bf16).  ``pooling``: "cls" (the BGE family: the last layer
         runs for the CLS rows only), "mean" (sentence-transformers mean pooling over a sequence's tokens: full last layer) or
@@ -731,7 +791,9 @@ class Encoder:
         elif pooling == "last":
             if p.pool_last is None:
                 raise ValueError("last-token pooling needs a decoder path")
-            hidden, starts, lens = self.forward_packed(batch, want_lens=True)
+            # the last layer for the last tokens only: the same bits as the full forward's rows, pooled from compact row b
+            hidden = self.rows_hidden_packed(batch, pooled_rows(batch))
+            starts, lens = self._compact_rows(B)
             name, rows = p.pool_last, (starts.data_ptr(), lens.data_ptr())
         elif pooling == "cls":
             hidden, cls_rows = self.cls_hidden_packed(batch)
@@ -749,10 +811,18 @@ class Encoder:
         if not self.cfg.num_labels:
             raise RuntimeError("these weights carry no classification head")
         p, dev = self.path, self.device
-        hidden, cls_rows = self.cls_hidden_packed(batch)
         B, H = len(batch.seq_len), self.cfg.hidden
         scores = torch.empty(B, dtype=torch.float32, device=dev)
         logits = torch.empty(B, dtype=torch.float32, device=dev) if want_logits else None
+        if p.score is not None:
+            # decoder reranker: the score head reads the pooled token's row of the one-row-per-sequence tail
+            hidden = self.rows_hidden_packed(batch, pooled_rows(batch, self.cfg.pad_token_id))
+            with torch.cuda.device(dev):
+                rc = getattr(self.lib, p.score)(hidden.data_ptr(), H, self.w.score_w.data_ptr(), B, H, scores.data_ptr(),
+                                                logits.data_ptr() if want_logits else None, torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(rc, p.score)
+            return (scores, logits) if want_logits else scores
+        hidden, cls_rows = self.cls_hidden_packed(batch)
         n_pad = (B + 127) // 128 * 128
         need = 2 * ((n_pad * H * hidden.element_size() + 255) // 256 * 256)
         with self._enqueue_lock, torch.cuda.device(dev):

@@ -6,6 +6,13 @@ called at ``services/rag_service.py:343-346,617-620`` (keyword ``query_bundle``)
 sentence-transformers: pairs ``(query_str, node.get_content(EMBED))``,
 truncation to 512, sigmoid scores, ``node.score = float(score)``, sort desc, ``[:top_n]``;
 empty input -> ``[]``; missing query -> ``ValueError``.
+
+Decoder rerankers (a ``Qwen3ForSequenceClassification`` checkpoint directory, e.g. a Qwen3-Reranker converted for cross-encoder
+use; bf16 or fp16, named in ``model_kwargs["torch_dtype"]``): pairs are tokenised by the checkpoint's own ``tokenizer.json``, whose
+pair template decides the special tokens, and scored at the token transformers pools (``encoder.pooled_rows``).  Optional
+``model_kwargs["query_template"]`` / ``["document_template"]`` (``str.format`` with ``{query}`` / ``{document}``) wrap the two
+sides before tokenisation -- the chat-style prompt of the Qwen3-Reranker model card, which ``SentenceTransformerRerank`` does not
+apply by itself; default: none, the strings as the reference passes them.
 """
 from __future__ import annotations
 
@@ -55,6 +62,8 @@ class HipSentenceTransformerRerank:
         # (`.model` is what the reference's memory accounting reads)
         self.model, self._encoder, self.precision = _precision.build_encoder(cfg, state, dev, model_kwargs, f"reranker {model}")
         self._tokenizer = (model_kwargs or {}).get("tokenizer") or load_tokenizer(mdir, cfg.arch, cfg.vocab_size)
+        self.query_template, self.document_template = (self._template(model_kwargs, k, f) for k, f in
+                                                       (("query_template", "query"), ("document_template", "document")))
         # concurrent predict() / postprocess_nodes() calls (one per request thread in the reference,
         # rag_service.py:343-346,617-620) share ONE tokenizer call and ONE encoder batch; scores do not depend on the
         # batch a pair travels in (tests/test_configs_gpu.py), so callers see exactly their serial results
@@ -77,6 +86,33 @@ class HipSentenceTransformerRerank:
         # (profiles/r05_surface_busy.log: 97.6 -> 102.3 q/s from 32 threads); TT_COALESCE_DEPTH overrides
         self._front = (Coalescer(self._prepare_many, max_coalesced_calls, coalesce_wait_s, execute=self._enqueue_many,
                                  finish=self._collect_many, depth=3) if coalesce else None)
+
+    @staticmethod
+    def _template(model_kwargs, key: str, field: str) -> Optional[str]:
+        t = (model_kwargs or {}).get(key)
+        if t is None:
+            return None
+        if not isinstance(t, str) or "{" + field + "}" not in t:
+            raise ValueError(f"model_kwargs['{key}'] must be a str.format template holding {{{field}}}")
+        try:
+            t.format(**{field: ""})      # any other field, or a stray brace, fails here and not inside a request
+        except (KeyError, IndexError, ValueError) as exc:
+            raise ValueError(f"model_kwargs['{key}'] is not a str.format template of {{{field}}} alone: {exc!r}") from exc
+        return t
+
+    def format_pair(self, query: str, document):
+        """The (query, document) strings as they are tokenised: wrapped in ``query_template`` / ``document_template`` where given
+        (a passage handed over as stored ids is left as it is)."""
+        if self.query_template is not None:
+            query = self.query_template.format(query=query)
+        if self.document_template is not None and isinstance(document, str):
+            document = self.document_template.format(document=document)
+        return query, document
+
+    def _formatted(self, pairs):
+        if self.query_template is None and self.document_template is None:
+            return pairs
+        return [self.format_pair(q, p) for q, p in pairs]
 
     # ---- token-id level ---------------------------------------------------------------------------
     def _pack(self, pair_ids: Sequence[Sequence[int]], type_ids: Optional[Sequence[Sequence[int]]] = None):
@@ -154,11 +190,11 @@ class HipSentenceTransformerRerank:
         return ids, [e[1] for e in enc]
 
     def _predict_flat(self, pairs: Sequence[Sequence[str]]) -> List[float]:
-        return self.score_token_pairs(*self._tokenize_pairs(pairs)).cpu().tolist()
+        return self.score_token_pairs(*self._tokenize_pairs(self._formatted(pairs))).cpu().tolist()
 
     def _prepare_many(self, calls: List[Sequence[Sequence[str]]]):
         """Host phase of a coalesced batch: the pair lists of several concurrent callers, tokenised and packed."""
-        flat = [p for c in calls for p in c]
+        flat = self._formatted([p for c in calls for p in c])
         return [len(c) for c in calls], self._pack(*self._tokenize_pairs(flat)) if flat else []
 
     def _enqueue_many(self, prepared):
@@ -202,6 +238,10 @@ class HipSentenceTransformerRerank:
         """Would ids made by the tokenizer ``signature`` (with ``instruction`` prepended to the text) be THIS model's ids?"""
         from .tokenization import tokenizer_signature
 
+        if self.config.arch == "qwen3" or self.query_template is not None or self.document_template is not None:
+            # stored ids are laid out by tokenization.SpecialTokens, which knows the XLM-R and BERT pair layouts only: a decoder
+            # reranker's layout is its tokenizer's template (and a text template changes the passage's tokens): pairs come from text
+            return False
         return not self._use_types and not instruction and signature == tokenizer_signature(self._tokenizer)
 
     def attach_token_source(self, source, signature: str, instruction: str = "") -> bool:

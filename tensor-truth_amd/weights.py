@@ -25,7 +25,9 @@ WEIGHT_FILES = ("model.safetensors", "model.safetensors.index.json", "pytorch_mo
 
 
 def _decoder_config_from_hf(d: dict) -> EncoderConfig:
-    """``model_type == "qwen3"`` (Qwen3-Embedding): every size from config.json, nothing assumed."""
+    """``model_type == "qwen3"`` (Qwen3-Embedding; a ``Qwen3ForSequenceClassification`` reranker): every size from config.json,
+    nothing assumed.  A head exists iff ``architectures`` names a ``*ForSequenceClassification`` (what the reference's loader,
+    ``AutoModelForSequenceClassification``, instantiates with trained weights); ``pad_token_id`` decides which token it reads."""
     from .decoder import DecoderConfig
 
     # variants the decoder kernels do not compute are refused, never run as plain Qwen3 (no silent wrong vectors)
@@ -42,10 +44,18 @@ def _decoder_config_from_hf(d: dict) -> EncoderConfig:
         raise NotImplementedError(f"qwen3 checkpoint with {', '.join(bad)}: the decoder embedder computes bias-free full causal "
                                   "attention with default RoPE and SiLU only")
     heads = d["num_attention_heads"]
+    num_labels = 0
+    if "ForSequenceClassification" in " ".join(d.get("architectures") or []):
+        n = d.get("num_labels") or (len(d["id2label"]) if d.get("id2label") else 1)
+        if n != 1:
+            raise ValueError(f"qwen3 classification checkpoint with {n} labels: only single-label (sigmoid) cross-encoder heads "
+                             "are supported")
+        num_labels = 1
+    pad = d.get("pad_token_id")
     return DecoderConfig(
         arch="qwen3", vocab_size=d["vocab_size"], hidden=d["hidden_size"], layers=d["num_hidden_layers"], heads=heads,
         ffn=d["intermediate_size"], max_pos=d["max_position_embeddings"], type_vocab=1, pad_id=0,
-        ln_eps=d.get("rms_norm_eps", 1e-6), num_labels=0, kv_heads=d.get("num_key_value_heads") or heads,
+        ln_eps=d.get("rms_norm_eps", 1e-6), num_labels=num_labels, pad_token_id=None if pad is None else int(pad), kv_heads=d.get("num_key_value_heads") or heads,
         head_dim=d.get("head_dim") or 128,   # Qwen3Config's default (not hidden // heads)
         rope_theta=float(d.get("rope_theta") or (d.get("rope_parameters") or {}).get("rope_theta") or 10000.0))
 
