@@ -116,6 +116,41 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
+// sum over the 64 lanes of a wave (butterfly: every lane ends with the same bits)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// LDS reads hidden from the compiler's LDS-DMA tracking (it would put s_waitcnt vmcnt(0) in front of every ds_read while the
+// next tile's copies are in flight), and the matching counted wait that names every destination register (x3_path.hip,
+// f16c_path.hip; attention.hip and gemm.hip keep their own forms)
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <int OFF>
+__device__ __forceinline__ u32x4 lds_read128(uint32_t addr) {
+    u32x4 r;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
+    return r;
+}
+template <int N>
+__device__ __forceinline__ void lds_wait8(u32x4& a, u32x4& b, u32x4& c, u32x4& d, u32x4& e, u32x4& f, u32x4& g, u32x4& h) {
+    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "n"(N));
+}
+template <int N>
+__device__ __forceinline__ void lds_wait4(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+
+// the embedding kernels' row indices: token id, position and type clamped into their tables (type == NULL: type 0)
+__device__ __forceinline__ void embed_rows_clamped(const int32_t* ids, const int32_t* pos, const int32_t* type, int row, int vocab,
+                                                   int max_pos, int type_vocab, int& id, int& p, int& t) {
+    id = ids[row]; p = pos[row]; t = type ? type[row] : 0;
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
+    t = t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t);
+}
+
 // ---- the element helpers the twice-compiled files use (see TT_F16 above) ---------------------------------------------------
 constexpr bool kF16 = TT_F16 != 0;
 #if TT_F16

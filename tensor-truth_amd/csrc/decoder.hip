@@ -397,18 +397,17 @@ DecWs dec_plan(const tt_decoder_weights* w, int n_rows) {
     DecWs e{};
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, D = (size_t)w->head_dim, T = ((size_t)n_rows + 255) / 256 * 256;
     const size_t nqkv = (size_t)(w->heads + 2 * w->kv_heads) * D;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += tt_align_up(bytes, 256); return o; };
-    e.off_ha = take(T * H * 2);
-    e.off_hb = take(T * H * 2);
-    e.off_x = take(T * H * 2);
-    e.off_qkv = take(T * nqkv * 2);
-    e.off_vt = take(T * w->kv_heads * D * 2);
-    e.off_ctx = take(T * w->heads * D * 2);
-    e.off_gu = take(T * 2 * F * 2);
-    e.off_act = take(T * F * 2);
-    e.off_zero = take(std::max(nqkv, std::max(2 * F, H)) * 4);   // the GEMMs' bias operand: the model has none
-    e.total = off;
+    WsPlanner ws;
+    e.off_ha = ws.take(T * H * 2);
+    e.off_hb = ws.take(T * H * 2);
+    e.off_x = ws.take(T * H * 2);
+    e.off_qkv = ws.take(T * nqkv * 2);
+    e.off_vt = ws.take(T * w->kv_heads * D * 2);
+    e.off_ctx = ws.take(T * w->heads * D * 2);
+    e.off_gu = ws.take(T * 2 * F * 2);
+    e.off_act = ws.take(T * F * 2);
+    e.off_zero = ws.take(std::max(nqkv, std::max(2 * F, H)) * 4);   // the GEMMs' bias operand: the model has none
+    e.total = ws.off;
     return e;
 }
 
@@ -461,7 +460,7 @@ int attention_rows_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, c
 }
 
 // rows of the compact buffers of the pooled-row tail: up to 256 sequences a multiple of 64 (the skinny GEMMs), else of 256
-int rows_pad(int n_seq) { return (n_seq <= 256 && tt_gemm_skinny_enabled()) ? (n_seq + 63) / 64 * 64 : (n_seq + 255) / 256 * 256; }
+int rows_pad(int n_seq) { return pooled_rows_pad(n_seq, tt_gemm_skinny_enabled()); }
 
 // The forward behind tt_decoder_forward (pool_row == nullptr: every layer over every row, out [n_rows][H]) and
 // tt_decoder_forward_rows (the last layer's attention, output projection, MLP and the final norm for the rows pool_row names only,
@@ -563,12 +562,7 @@ int check_forward_args(const char* what, const tt_decoder_weights* w, const int3
                  "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
     TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
     TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
-    const DecWs e = dec_plan(w, n_rows);
-    if (!workspace || workspace_bytes < e.total) {
-        tt_set_error("%s: workspace %zu < required %zu bytes", what, workspace_bytes, e.total);
-        return TT_E_WORKSPACE;
-    }
-    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    if (int rc = tt_check_workspace(what, workspace, workspace_bytes, dec_plan(w, n_rows).total)) return rc;
     for (int l = 0; l < w->layers; ++l) {
         const tt_decoder_layer_weights& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.q_norm && lw.k_norm && lw.o_w && lw.attn_norm && lw.ffn_norm && lw.gate_up_w && lw.down_w,

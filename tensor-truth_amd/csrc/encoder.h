@@ -164,3 +164,54 @@ int tt_head_out_sigmoid_launch(const uint16_t* t, int ld, const uint16_t* w, con
 
 // dist[i] = 1 - cos(e[i], e[i+1]), e fp32 [n][H]
 int tt_adjacent_cosine_launch(const float* e, int n, int H, float* dist, hipStream_t st);
+
+// fp32 rows: dst[b][0..H) = src[rows[b]][0..H) for b < n, zeros up to n_pad (f32_path.hip; the CLS tails of the split-plane
+// and f16c forwards).  H a multiple of 4, both matrices [.][H].
+int tt_gather_rows_f32_launch(const float* src, const int32_t* rows, int n, int n_pad, int H, float* dst, hipStream_t st);
+
+// ---- host helpers of the forwards (encoder_api.hip, x3_path.hip, f16c_path.hip, f32_path.hip, decoder.hip) -------------------
+// workspace layout: consecutive buffers, each starting on a 256-byte boundary
+struct WsPlanner {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += tt_align_up(bytes, 256); return o; }
+};
+
+// the workspace of entry point `what` is present, holds `need` bytes and is 256-byte aligned
+inline int tt_check_workspace(const char* what, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (!workspace || workspace_bytes < need) {
+        tt_set_error("%s: workspace %zu < required %zu bytes", what, workspace_bytes, need);
+        return TT_E_WORKSPACE;
+    }
+    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    return TT_OK;
+}
+
+// Rows of the compact buffers a forward's last layer runs on when only one row per sequence is wanted (CLS tail, pooled rows):
+// up to 256 sequences a multiple of 64 where the skinny GEMMs take them, else a multiple of 256 (the 256-row tile kernels).
+// What the callers pass for skinny_allowed, and why:
+//   bf16 / fp16 encoder, decoder: tt_gemm_skinny_enabled() -- with the diagnostic A/B switch off, the tile kernels need 256 rows;
+//   split planes (x3):            true -- it has never consulted the switch (always on in the product library; with it off in the
+//                                 diagnostic one, a tail of <= 192 rows is refused by the x3 GEMM launcher);
+//   f16c:                         false -- the c-planes GEMM has no skinny kernel and its block scales are tiled per 256 rows.
+inline int pooled_rows_pad(int n_seq, bool skinny_allowed) {
+    return (n_seq <= 256 && skinny_allowed) ? (n_seq + 63) / 64 * 64 : (n_seq + 255) / 256 * 256;
+}
+
+// the classification head of the fp32-residual paths (x3, f16c) is a [n_seq x H x H] product: it runs on the fp32 kernels
+// (tt_rerank_head_f32) through this view of the fp32 head weights
+template <class Weights>
+inline tt_encoder_weights_f32 head_weights_f32(const Weights* w) {
+    tt_encoder_weights_f32 h{};
+    h.hidden = w->hidden; h.layers = 0; h.heads = w->heads; h.ffn = w->ffn; h.vocab = w->vocab; h.max_pos = w->max_pos;
+    h.type_vocab = w->type_vocab; h.ln_eps = w->ln_eps;
+    h.word_emb = w->word_emb; h.pos_emb = w->pos_emb; h.type_emb = w->type_emb; h.emb_ln_g = w->emb_ln_g; h.emb_ln_b = w->emb_ln_b;
+    h.cls_dense_w = w->cls_dense_w; h.cls_dense_b = w->cls_dense_b; h.cls_out_w = w->cls_out_w; h.cls_out_b = w->cls_out_b;
+    return h;
+}
+
+// one projection on plain 16-bit operands: A [M][K], W [N][K] (the caller adds the epilogue's output and residual)
+inline GemmParams gemm_16(const uint16_t* a, const void* w, const float* bias, int M, int N, int K) {
+    GemmParams g{};
+    g.A = a; g.lda = K; g.W = (const uint16_t*)w; g.bias = bias; g.M = M; g.N = N; g.K = K;
+    return g;
+}

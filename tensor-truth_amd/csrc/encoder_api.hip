@@ -39,32 +39,30 @@ EncWs enc_plan(const tt_encoder_weights* w, int n_rows, int n_seq = 0) {
     EncWs e{};
     // buffers are sized for a multiple of 256 rows: the attention kernels read whole key tiles
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += tt_align_up(bytes, 256); return o; };
-    e.off_xa = take(T * H * 2);
-    e.off_xb = take(T * H * 2);
-    e.off_y = take(T * H * 2);
-    e.off_qk = take(T * 2 * H * 2);
-    e.off_vt = take(H * T * 2);
-    e.off_ctx = take(T * H * 2);
-    e.off_ffn = take(T * F * 2);
-    e.n_cls_pad = (n_seq <= 256 && tt_gemm_skinny_enabled()) ? (n_seq + 63) / 64 * 64      // <= 256 rows: skinny GEMMs
-                                                             : (n_seq + 255) / 256 * 256;
+    WsPlanner ws;
+    e.off_xa = ws.take(T * H * 2);
+    e.off_xb = ws.take(T * H * 2);
+    e.off_y = ws.take(T * H * 2);
+    e.off_qk = ws.take(T * 2 * H * 2);
+    e.off_vt = ws.take(H * T * 2);
+    e.off_ctx = ws.take(T * H * 2);
+    e.off_ffn = ws.take(T * F * 2);
+    e.n_cls_pad = pooled_rows_pad(n_seq, tt_gemm_skinny_enabled());
     if (n_seq > 0) {
         const size_t B = (size_t)e.n_cls_pad;
-        e.off_cctx = take(B * H * 2);
-        e.off_cx = take(B * H * 2);
-        e.off_cy = take(B * H * 2);
-        e.off_cx1 = take(B * H * 2);
-        e.off_cffn = take(B * F * 2);
+        e.off_cctx = ws.take(B * H * 2);
+        e.off_cx = ws.take(B * H * 2);
+        e.off_cy = ws.take(B * H * 2);
+        e.off_cx1 = ws.take(B * H * 2);
+        e.off_cffn = ws.take(B * F * 2);
     }
     e.fp8 = fp8_ready(w, n_rows);
     if (e.fp8) {
-        e.off_q8 = take(T * H);
-        e.off_q8s = take(T * 4);
-        e.off_q8c = take(T * 4);   // constant row scales (the FFN intermediate's static scale)
+        e.off_q8 = ws.take(T * H);
+        e.off_q8s = ws.take(T * 4);
+        e.off_q8c = ws.take(T * 4);   // constant row scales (the FFN intermediate's static scale)
     }
-    e.total = off;
+    e.total = ws.off;
     return e;
 }
 
@@ -100,11 +98,7 @@ static int forward_impl(const tt_encoder_weights* w, const int32_t* ids, const i
     TT_CHECK_ARG(ids && pos && seq_start && seq_len && (hidden_out || cls_out), "null pointer");
     const bool cls_tail = cls_out != nullptr && w->layers > 0;
     const EncWs e = enc_plan(w, n_rows, cls_tail ? n_seq : 0);
-    if (!workspace || workspace_bytes < e.total) {
-        tt_set_error("tt_encoder_forward: workspace %zu < required %zu bytes", workspace_bytes, e.total);
-        return TT_E_WORKSPACE;
-    }
-    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    if (int rc = tt_check_workspace("tt_encoder_forward", workspace, workspace_bytes, e.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, T = n_rows;
@@ -142,18 +136,69 @@ static int forward_impl(const tt_encoder_weights* w, const int32_t* ids, const i
     // altogether (tools/probes/fp8_sensitivity.py: rank agreement with the fp32 path per setting).
     const int f8mask_all = TT_DIAG_ENV_INT("TT_FP8_MASK", 0xF), f8first = TT_DIAG_ENV_INT("TT_FP8_SKIP_FIRST", 0),
               f8last = TT_DIAG_ENV_INT("TT_FP8_SKIP_LAST", 0);
+    // The post-attention half of a layer on M rows: y = GEMM(c, Wo) + bo + res, x1 = LayerNorm(y), f = GELU(GEMM(x1, W1) + b1),
+    // y = GEMM(f, W2) + b2 + x1, out = LayerNorm(y).  `f8` names what an fp8 forward adds on its full pass; the CLS tail passes
+    // Fp8Ops{}: plain 16-bit weights, no e4m3 copies, no calibration hook.
+    struct Fp8Ops {
+        uint8_t* q8;      // e4m3 copy of the current GEMM A operand (written by the LayerNorms and by tt_quantize_rows_launch)
+        float* q8s;       // its per-row scales
+        float* q8c;       // constant row scales of the e4m3 FFN intermediate
+        int mask;         // which projections run in e4m3 (TT_FP8_MASK bits; 0 = none)
+        float* absmax;    // the layer's entry of ffn_absmax_out, or NULL
+    };
+    auto half_layer = [&](const tt_layer_weights& lw, int M, uint16_t* c, const uint16_t* res, uint16_t* y, uint16_t* x1, uint16_t* f,
+                          uint16_t* out, const Fp8Ops& f8) -> int {
+        // attention output projection + residual, LayerNorm
+        GemmParams go = gemm_16(c, lw.o_w, lw.o_b, M, H, H);
+        go.residual = res; go.ldr = H; go.C = y; go.ldc = H;
+        if ((f8.mask & 2) && lw.o_w8 && lw.o_wscale) {   // the QKV GEMM is done with q8: reuse it for the context's e4m3 copy
+            {
+                TtProfScope prof(TT_K_ROWOPS, st);
+                if (int rc = tt_quantize_rows_launch(c, H, M, H, f8.q8, f8.q8s, st)) return rc;
+            }
+            go.A = (const uint16_t*)f8.q8; go.W = (const uint16_t*)lw.o_w8; go.a_scale = f8.q8s; go.w_scale = lw.o_wscale; go.fp8 = 1;
+        }
+        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
+        {
+            TtProfScope prof(TT_K_ROWOPS, st);
+            if (int rc = tt_layernorm_launch(y, x1, lw.ln1_g, lw.ln1_b, M, H, w->ln_eps, st, f8.q8, f8.q8s)) return rc;
+        }
+        // FFN
+        GemmParams g1 = gemm_16(x1, lw.ffn1_w, lw.ffn1_b, M, F, H);
+        g1.C = f; g1.ldc = F;
+        const bool f8down = (f8.mask & 12) == 12 && lw.ffn2_w8 && lw.ffn2_wscale && lw.ffn_act_scale > 0.f;
+        if (f8.mask & 4) {
+            g1.A = (const uint16_t*)f8.q8; g1.W = (const uint16_t*)lw.ffn1_w8; g1.a_scale = f8.q8s; g1.w_scale = lw.ffn1_wscale; g1.fp8 = 1;
+            if (f8down) {   // the intermediate is written as e4m3 (static scale) into the same buffer, half its size
+                g1.C8 = (uint8_t*)f; g1.c8_inv_scale = 1.0f / lw.ffn_act_scale;
+            }
+        }
+        if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
+        if (f8.absmax && !f8down) {
+            TtProfScope prof(TT_K_ROWOPS, st);
+            if (int rc = tt_absmax_launch(f, (size_t)M * F, f8.absmax, st)) return rc;
+        }
+        GemmParams g2 = gemm_16(f, lw.ffn2_w, lw.ffn2_b, M, H, F);
+        g2.residual = x1; g2.ldr = H; g2.C = y; g2.ldc = H;
+        if (f8down) {
+            const unsigned bits = __builtin_bit_cast(unsigned, lw.ffn_act_scale);
+            TT_CHECK_HIP(hipMemsetD32Async(f8.q8c, (int)bits, (size_t)M, st));
+            g2.W = (const uint16_t*)lw.ffn2_w8; g2.a_scale = f8.q8c; g2.w_scale = lw.ffn2_wscale; g2.fp8 = 1;
+        }
+        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
+        TtProfScope prof(TT_K_ROWOPS, st);
+        return tt_layernorm_launch(y, out, lw.ln2_g, lw.ln2_b, M, H, w->ln_eps, st, f8.q8, f8.q8s);
+    };
     for (int l = 0; l < w->layers; ++l) {
         const tt_layer_weights& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.qkv_b && lw.o_w && lw.o_b && lw.ln1_g && lw.ln1_b && lw.ffn1_w && lw.ffn1_b &&
                          lw.ffn2_w && lw.ffn2_b && lw.ln2_g && lw.ln2_b,
                      "layer %d has a null weight pointer", l);
         // QKV projection
-        GemmParams g{};
-        g.A = x; g.lda = H; g.W = (const uint16_t*)lw.qkv_w; g.bias = lw.qkv_b;
+        GemmParams g = gemm_16(x, lw.qkv_w, lw.qkv_b, T, 3 * H, H);
         g.C = qk; g.ldc = 2 * H; g.vt = vt; g.ldvt = 8 * H; g.vt_col0 = 2 * H;
-        g.M = T; g.N = 3 * H; g.K = H;
-        const int f8mask = (l < f8first || l >= w->layers - f8last) ? 0 : f8mask_all;
-        if (e.fp8 && (f8mask & 1)) {   // x's e4m3 copy and row scales come from the LayerNorm that produced x
+        const int f8mask = (!e.fp8 || l < f8first || l >= w->layers - f8last) ? 0 : f8mask_all;
+        if (f8mask & 1) {   // x's e4m3 copy and row scales come from the LayerNorm that produced x
             g.A = (const uint16_t*)q8; g.W = (const uint16_t*)lw.qkv_w8; g.a_scale = q8s; g.w_scale = lw.qkv_wscale; g.fp8 = 1;
         }
         // last layer of the CLS tail: only the first row of every sequence needs a QUERY, so the big projection computes K and V alone
@@ -168,9 +213,14 @@ static int forward_impl(const tt_encoder_weights* w, const int32_t* ids, const i
             g.C = qk + H; g.N = 2 * H; g.vt_col0 = H;
         }
         if (int rc = tt_gemm_launch(g, TT_EPI_QKV, st)) return rc;
+        AttnParams a{};
+        a.qk = qk; a.ld_qk = 2 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = vt; a.ldvt = 8 * H;
+        a.ld_out = H; a.seq_start = seq_start; a.seq_len = seq_len;
+        a.n_seq = n_seq; a.heads = w->heads; a.head_dim = dh; a.max_len = max_len;
+        a.scale = 1.0f / sqrtf((float)dh);
         if (cls_tail && l == w->layers - 1) {
             // ---- last layer, CLS rows only: attention of the one query row per sequence, then the
-            //      output projection / LayerNorm / FFN on n_seq (padded to 256) rows instead of n_rows
+            //      second half of the layer on n_seq (padded) rows instead of n_rows
             const int Bp = e.n_cls_pad;
             uint16_t* cctx = (uint16_t*)(ws + e.off_cctx);
             uint16_t* cx = (uint16_t*)(ws + e.off_cx);
@@ -182,96 +232,25 @@ static int forward_impl(const tt_encoder_weights* w, const int32_t* ids, const i
                 TtProfScope prof(TT_K_ROWOPS, st);
                 if (int rc = tt_gather_rows_launch(x, H, seq_start, n_seq, Bp, H, cx, st)) return rc;
             }
-            AttnParams ac{};
             if (kv_only) {   // the first rows' queries (cy is free until the output projection writes it)
-                GemmParams gq{};
-                gq.A = cx; gq.lda = H; gq.W = (const uint16_t*)lw.qkv_w; gq.bias = lw.qkv_b;
-                gq.C = cy; gq.ldc = H; gq.M = Bp; gq.N = H; gq.K = H;
+                GemmParams gq = gemm_16(cx, lw.qkv_w, lw.qkv_b, Bp, H, H);
+                gq.C = cy; gq.ldc = H;
                 if (int rc = tt_gemm_launch(gq, TT_EPI_BIAS, st)) return rc;
-                ac.q_rows = cy; ac.ld_q_rows = H;
+                a.q_rows = cy; a.ld_q_rows = H;
             }
-            ac.qk = qk; ac.ld_qk = 2 * H; ac.q_col0 = 0; ac.k_col0 = H; ac.vt = vt; ac.ldvt = 8 * H;
-            ac.out = cctx; ac.ld_out = H; ac.seq_start = seq_start; ac.seq_len = seq_len;
-            ac.n_seq = n_seq; ac.heads = w->heads; ac.head_dim = dh; ac.max_len = max_len;
-            ac.scale = 1.0f / sqrtf((float)dh);
-            if (int rc = tt_attention_cls_launch(ac, st)) return rc;
-            GemmParams go{};
-            go.A = cctx; go.lda = H; go.W = (const uint16_t*)lw.o_w; go.bias = lw.o_b;
-            go.residual = cx; go.ldr = H; go.C = cy; go.ldc = H; go.M = Bp; go.N = H; go.K = H;
-            if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-            {
-                TtProfScope prof(TT_K_ROWOPS, st);
-                if (int rc = tt_layernorm_launch(cy, cx1, lw.ln1_g, lw.ln1_b, Bp, H, w->ln_eps, st)) return rc;
-            }
-            GemmParams g1{};
-            g1.A = cx1; g1.lda = H; g1.W = (const uint16_t*)lw.ffn1_w; g1.bias = lw.ffn1_b;
-            g1.C = cffn; g1.ldc = F; g1.M = Bp; g1.N = F; g1.K = H;
-            if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-            GemmParams g2{};
-            g2.A = cffn; g2.lda = F; g2.W = (const uint16_t*)lw.ffn2_w; g2.bias = lw.ffn2_b;
-            g2.residual = cx1; g2.ldr = H; g2.C = cy; g2.ldc = H; g2.M = Bp; g2.N = H; g2.K = F;
-            if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-            TtProfScope prof(TT_K_ROWOPS, st);
-            return tt_layernorm_launch(cy, (uint16_t*)cls_out, lw.ln2_g, lw.ln2_b, Bp, H, w->ln_eps, st);
+            a.out = cctx;
+            if (int rc = tt_attention_cls_launch(a, st)) return rc;
+            return half_layer(lw, Bp, cctx, cx, cy, cx1, cffn, (uint16_t*)cls_out, Fp8Ops{});
         }
         // attention
-        AttnParams a{};
-        a.qk = qk; a.ld_qk = 2 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = vt; a.ldvt = 8 * H;
-        a.out = ctx; a.ld_out = H; a.seq_start = seq_start; a.seq_len = seq_len;
-        a.n_seq = n_seq; a.heads = w->heads; a.head_dim = dh; a.max_len = max_len; a.total_rows = n_rows;
-        a.scale = 1.0f / sqrtf((float)dh);
+        a.out = ctx; a.total_rows = n_rows;
         if (int rc = tt_attention_launch(a, st)) return rc;
-        // attention output projection + residual, LayerNorm
-        GemmParams go{};
-        go.A = ctx; go.lda = H; go.W = (const uint16_t*)lw.o_w; go.bias = lw.o_b;
-        go.residual = x; go.ldr = H; go.C = y; go.ldc = H; go.M = T; go.N = H; go.K = H;
-        if (e.fp8 && (f8mask & 2) && lw.o_w8 && lw.o_wscale) {   // the QKV GEMM is done with q8: reuse it for the context's e4m3 copy
-            {
-                TtProfScope prof(TT_K_ROWOPS, st);
-                if (int rc = tt_quantize_rows_launch(ctx, H, T, H, q8, q8s, st)) return rc;
-            }
-            go.A = (const uint16_t*)q8; go.W = (const uint16_t*)lw.o_w8; go.a_scale = q8s; go.w_scale = lw.o_wscale; go.fp8 = 1;
-        }
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-        uint16_t* x1 = (x == xa) ? xb : xa;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            if (int rc = tt_layernorm_launch(y, x1, lw.ln1_g, lw.ln1_b, T, H, w->ln_eps, st, q8, q8s)) return rc;
-        }
-        // FFN
-        GemmParams g1{};
-        g1.A = x1; g1.lda = H; g1.W = (const uint16_t*)lw.ffn1_w; g1.bias = lw.ffn1_b;
-        g1.C = ffn; g1.ldc = F; g1.M = T; g1.N = F; g1.K = H;
-        const bool f8 = e.fp8 && (f8mask & 12) == 12 && lw.ffn2_w8 && lw.ffn2_wscale && lw.ffn_act_scale > 0.f;
-        if (e.fp8 && (f8mask & 4)) {
-            g1.A = (const uint16_t*)q8; g1.W = (const uint16_t*)lw.ffn1_w8; g1.a_scale = q8s; g1.w_scale = lw.ffn1_wscale; g1.fp8 = 1;
-            if (f8) {   // the intermediate is written as e4m3 (static scale) into the same buffer, half its size
-                g1.C8 = (uint8_t*)ffn; g1.c8_inv_scale = 1.0f / lw.ffn_act_scale;
-            }
-        }
-        if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-        if (w->ffn_absmax_out && !f8) {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            if (int rc = tt_absmax_launch(ffn, (size_t)T * F, w->ffn_absmax_out + l, st)) return rc;
-        }
-        GemmParams g2{};
-        g2.A = ffn; g2.lda = F; g2.W = (const uint16_t*)lw.ffn2_w; g2.bias = lw.ffn2_b;
-        g2.residual = x1; g2.ldr = H; g2.C = y; g2.ldc = H; g2.M = T; g2.N = H; g2.K = F;
-        if (f8) {
-            float* q8c = (float*)(ws + e.off_q8c);
-            const float act_scale = lw.ffn_act_scale;
-            const unsigned bits = __builtin_bit_cast(unsigned, act_scale);
-            TT_CHECK_HIP(hipMemsetD32Async(q8c, (int)bits, (size_t)T, st));
-            g2.W = (const uint16_t*)lw.ffn2_w8; g2.a_scale = q8c; g2.w_scale = lw.ffn2_wscale; g2.fp8 = 1;
-        }
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-        // x1 is free again after the FFN-down GEMM has consumed it as residual; the LN output
+        // x1 is free again after the FFN-down GEMM has consumed it as residual; the second LayerNorm's output
         // goes to the other hidden buffer (or straight to hidden_out on the last layer)
+        uint16_t* x1 = (x == xa) ? xb : xa;
         uint16_t* dst = (l == w->layers - 1) ? (uint16_t*)hidden_out : x;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            if (int rc = tt_layernorm_launch(y, dst, lw.ln2_g, lw.ln2_b, T, H, w->ln_eps, st, q8, q8s)) return rc;
-        }
+        const Fp8Ops f8{q8, q8s, e.fp8 ? (float*)(ws + e.off_q8c) : nullptr, f8mask, w->ffn_absmax_out ? w->ffn_absmax_out + l : nullptr};
+        if (int rc = half_layer(lw, T, ctx, x, y, x1, ffn, dst, f8)) return rc;
         x = dst;
     }
     return TT_OK;

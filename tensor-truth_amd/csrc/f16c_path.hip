@@ -32,19 +32,10 @@
 
 #if TT_F16
 
-extern "C" int tt_rerank_head_f32(const tt_encoder_weights_f32* w, const float* hidden_f32, const int32_t* rows, int n_seq,
-                                  float* scores, float* logits, void* workspace, size_t workspace_bytes, void* stream);
-
 namespace {
 
 constexpr int kRowThreadsC = 256;   // four rows per workgroup, one wave per row
 constexpr int kMaxC4c = 4;          // H <= 1024 in the LayerNorm kernels
-
-__device__ __forceinline__ float wave_sum_c(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Four consecutive values of a row (elements e0 .. e0 + 3, e0 = 4 lane (mod 256): a scale block = 8 consecutive lanes) -> the
 // three planes + the block's scale byte.  weight = the W flavour: [hi | lo8 | x8], the lo8 plane carries its OWN block exponent
@@ -97,7 +88,7 @@ __device__ __forceinline__ void ln_row_c(float4 (&x)[kMaxC4c], int nc, int H, co
 #pragma unroll
     for (int c = 0; c < kMaxC4c; ++c)
         if (c < nc) s += (x[c].x + x[c].y) + (x[c].z + x[c].w);
-    const float mean = wave_sum_c(s) / (float)H;
+    const float mean = wave_sum(s) / (float)H;
     float v = 0.f;
 #pragma unroll
     for (int c = 0; c < kMaxC4c; ++c)
@@ -105,7 +96,7 @@ __device__ __forceinline__ void ln_row_c(float4 (&x)[kMaxC4c], int nc, int H, co
             const float a = x[c].x - mean, b = x[c].y - mean, d = x[c].z - mean, e = x[c].w - mean;
             v += (a * a + b * b) + (d * d + e * e);
         }
-    const float rstd = 1.0f / sqrtf(wave_sum_c(v) / (float)H + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)H + eps);
 #pragma unroll
     for (int c = 0; c < kMaxC4c; ++c)
         if (c < nc) {
@@ -127,10 +118,8 @@ __global__ __launch_bounds__(kRowThreadsC) void embed_ln_c_kernel(const int32_t*
                                                                    float eps) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= T) return;
-    int id = ids[row], p = pos[row], t = type ? type[row] : 0;
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    t = t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t);
+    int id, p, t;
+    embed_rows_clamped(ids, pos, type, row, vocab, max_pos, type_vocab, id, p, t);
     const int nc = H / 256;
     float4 x[kMaxC4c];
 #pragma unroll
@@ -169,18 +158,6 @@ __global__ __launch_bounds__(kRowThreadsC) void quantize_c_kernel(const float* i
     }
 }
 
-// rows seq_start[b] of an fp32 [T][H] matrix -> dst [n_pad][H] (rows beyond n: zeros)
-__global__ __launch_bounds__(256) void gather_rows_f32c_kernel(const float* src, const int32_t* rows, int n, int n_pad, int H, float* dst) {
-    const int b = blockIdx.x;
-    if (b >= n_pad) return;
-    for (int c = threadIdx.x * 4; c < H; c += 256 * 4) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (b < n) v = *reinterpret_cast<const float4*>(src + (size_t)rows[b] * H + c);
-        *reinterpret_cast<float4*>(dst + (size_t)b * H + c) = v;
-    }
-}
-
-
 // ---- attention: scores on THREE fp16 products, values on one -------------------------------------------------------------------
 // The score product is the one place of the path where fp16's 2^-11 is not enough by itself: a trained model's peaked heads carry
 // logits of tens to a hundred, and an operand rounding of 2^-11 on q and k moves such a logit by 0.05 -- percents of a
@@ -204,22 +181,6 @@ struct AttnQ2Params {
     float scale, lazy;
     int n_qt;
 };
-
-typedef unsigned int u32x4q __attribute__((ext_vector_type(4)));
-template <int OFF>
-__device__ __forceinline__ u32x4q ldsq_read128(uint32_t addr) {
-    u32x4q r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void ldsq_wait8(u32x4q& a, u32x4q& b, u32x4q& c, u32x4q& d, u32x4q& e, u32x4q& f, u32x4q& g, u32x4q& h) {
-    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "n"(N));
-}
-template <int N>
-__device__ __forceinline__ void ldsq_wait4(u32x4q& a, u32x4q& b, u32x4q& c, u32x4q& d) {
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
 
 constexpr int kQKTile = 64, kQWaves = 4, kQDH = 64;
 constexpr int kQPlane = kQKTile * kQDH * 2;          // 8 KiB: one plane of a K tile (64 rows x 128 B) or the V tile
@@ -349,13 +310,13 @@ __global__ __launch_bounds__(64 * kQWaves, 3) void attention_qk2_kernel(AttnQ2Pa
         f32x16 acc_s[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            u32x4q kh[KS], kl[KS];
+            u32x4 kh[KS], kl[KS];
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                if (j == 0) { kh[s] = ldsq_read128<0>(koff[s] + bufo); kl[s] = ldsq_read128<kQPlane>(koff[s] + bufo); }
-                else { kh[s] = ldsq_read128<32 * RB>(koff[s] + bufo); kl[s] = ldsq_read128<kQPlane + 32 * RB>(koff[s] + bufo); }
+                if (j == 0) { kh[s] = lds_read128<0>(koff[s] + bufo); kl[s] = lds_read128<kQPlane>(koff[s] + bufo); }
+                else { kh[s] = lds_read128<32 * RB>(koff[s] + bufo); kl[s] = lds_read128<kQPlane + 32 * RB>(koff[s] + bufo); }
             }
-            ldsq_wait8<0>(kh[0], kh[1], kh[2], kh[3], kl[0], kl[1], kl[2], kl[3]);
+            lds_wait8<0>(kh[0], kh[1], kh[2], kh[3], kl[0], kl[1], kl[2], kl[3]);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc_s[j][r] = 0.f;
             // small terms first
@@ -367,10 +328,10 @@ __global__ __launch_bounds__(64 * kQWaves, 3) void attention_qk2_kernel(AttnQ2Pa
             for (int s = 0; s < KS; ++s) acc_s[j] = TT_MFMA_32x32x16(__builtin_bit_cast(ex8, kh[s]), qh[s], acc_s[j]);
         }
         // V fragments of the first 32 keys: in flight during the softmax
-        u32x4q vf[2][2];
+        u32x4 vf[2][2];
         const uint32_t vaddr = voff + bufo;
-        vf[0][0] = ldsq_read128<0>(vaddr); vf[0][1] = ldsq_read128<512>(vaddr);
-        vf[1][0] = ldsq_read128<2 * DH * 16>(vaddr); vf[1][1] = ldsq_read128<2 * DH * 16 + 512>(vaddr);
+        vf[0][0] = lds_read128<0>(vaddr); vf[0][1] = lds_read128<512>(vaddr);
+        vf[1][0] = lds_read128<2 * DH * 16>(vaddr); vf[1][1] = lds_read128<2 * DH * 16 + 512>(vaddr);
 
         // ---- mask, running reference, exponentials (fp32).  Register r of sub-tile j is key k0 + 32 j + 16 (r>>3) + 8 hh + (r&7)
         if (kt == 0 && off != 0) {
@@ -418,15 +379,15 @@ __global__ __launch_bounds__(64 * kQWaves, 3) void attention_qk2_kernel(AttnQ2Pa
         // ---- O^T += V^T . P^T, one product
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            ldsq_wait4<0>(vf[0][0], vf[0][1], vf[1][0], vf[1][1]);
+            lds_wait4<0>(vf[0][0], vf[0][1], vf[1][0], vf[1][1]);
             ex8 va[2][2];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
                 for (int d = 0; d < DT; ++d) va[s2][d] = __builtin_bit_cast(ex8, vf[s2][d]);
             if (j == 0) {   // next 32 keys' fragments, in flight during these MFMAs
-                vf[0][0] = ldsq_read128<4 * DH * 16>(vaddr); vf[0][1] = ldsq_read128<4 * DH * 16 + 512>(vaddr);
-                vf[1][0] = ldsq_read128<6 * DH * 16>(vaddr); vf[1][1] = ldsq_read128<6 * DH * 16 + 512>(vaddr);
+                vf[0][0] = lds_read128<4 * DH * 16>(vaddr); vf[0][1] = lds_read128<4 * DH * 16 + 512>(vaddr);
+                vf[1][0] = lds_read128<6 * DH * 16>(vaddr); vf[1][1] = lds_read128<6 * DH * 16 + 512>(vaddr);
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -501,7 +462,7 @@ int attention_qk2_launch(const AttnQ2Params& p, hipStream_t st) {
 
 inline dim3 row_grid_c(int rows) { return dim3((unsigned)((rows + 3) / 4)); }
 inline size_t scale_bytes(size_t rows256, size_t K) { return rows256 / 256 * (K / 128) * 1024; }      // activation scales
-inline int cls_pad_c(int n_seq) { return (n_seq + 255) / 256 * 256; }
+inline int cls_pad_c(int n_seq) { return pooled_rows_pad(n_seq, false); }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 struct XcWs {
@@ -512,32 +473,31 @@ struct XcWs {
 XcWs xc_plan(const tt_encoder_weights_f16c* w, int n_rows, int n_cls = 0) {
     XcWs e{};
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += tt_align_up(bytes, 256); return o; };
-    e.off_xa = take(T * H * 4);
-    e.off_xb = take(T * H * 4);
-    e.off_y = take(T * H * 4);
-    e.off_xc = take(T * 4 * H);
-    e.off_xs = take(scale_bytes(T, H));
-    e.off_qk = take(T * 4 * H * 2);               // Q hi | K hi | Q lo | K lo
-    e.off_vt = take(T * H * 2);
-    e.off_ctx = take(T * 4 * H);
-    e.off_cs = take(scale_bytes(T, H));
-    e.off_ffn = take(T * 4 * F);
-    e.off_fs = take(scale_bytes(T, F));
+    WsPlanner ws;
+    e.off_xa = ws.take(T * H * 4);
+    e.off_xb = ws.take(T * H * 4);
+    e.off_y = ws.take(T * H * 4);
+    e.off_xc = ws.take(T * 4 * H);
+    e.off_xs = ws.take(scale_bytes(T, H));
+    e.off_qk = ws.take(T * 4 * H * 2);               // Q hi | K hi | Q lo | K lo
+    e.off_vt = ws.take(T * H * 2);
+    e.off_ctx = ws.take(T * 4 * H);
+    e.off_cs = ws.take(scale_bytes(T, H));
+    e.off_ffn = ws.take(T * 4 * F);
+    e.off_fs = ws.take(scale_bytes(T, F));
     if (n_cls > 0) {
         const size_t B = (size_t)cls_pad_c(n_cls);
-        e.off_cctx = take(B * 4 * H);
-        e.off_ccs = take(scale_bytes(B, H));
-        e.off_cx = take(B * H * 4);
-        e.off_cy = take(B * H * 4);
-        e.off_cx1 = take(B * H * 4);
-        e.off_cxc = take(B * 4 * H);
-        e.off_cxs = take(scale_bytes(B, H));
-        e.off_cffn = take(B * 4 * F);
-        e.off_cfs = take(scale_bytes(B, F));
+        e.off_cctx = ws.take(B * 4 * H);
+        e.off_ccs = ws.take(scale_bytes(B, H));
+        e.off_cx = ws.take(B * H * 4);
+        e.off_cy = ws.take(B * H * 4);
+        e.off_cx1 = ws.take(B * H * 4);
+        e.off_cxc = ws.take(B * 4 * H);
+        e.off_cxs = ws.take(scale_bytes(B, H));
+        e.off_cffn = ws.take(B * 4 * F);
+        e.off_cfs = ws.take(scale_bytes(B, F));
     }
-    e.total = off;
+    e.total = ws.off;
     return e;
 }
 
@@ -562,6 +522,15 @@ GemmParams gemm_c(const void* a_planes, const uint8_t* a_scales, const void* w_p
     return g;
 }
 
+// LayerNorm of fp32 rows into the fp32 row (out32, may be NULL) and / or its c-planes with their scales (may be NULL)
+int layernorm_c_launch(const float* in, float* out32, char* planes, uint8_t* scales, const float* gamma, const float* beta, int rows, int H,
+                       float eps, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(layernorm_c_kernel, row_grid_c(rows), dim3(kRowThreadsC), 0, st, in, out32, planes, scales, gamma, beta, rows, H, eps);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
 // hidden_out: the last hidden state [n_rows][H]; cls_out (instead): the last hidden state of every sequence's FIRST row only,
 // [cls_pad_c(n_seq)][H] -- the last layer then runs its attention, output projection, LayerNorms and FFN for those rows only
 int forward_c_impl(const tt_encoder_weights_f16c* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
@@ -573,11 +542,7 @@ int forward_c_impl(const tt_encoder_weights_f16c* w, const int32_t* ids, const i
     TT_CHECK_ARG(ids && pos && seq_start && seq_len && (hidden_out || cls_out), "null pointer");
     const bool cls_tail = cls_out != nullptr && w->layers > 0;
     const XcWs e = xc_plan(w, n_rows, cls_tail ? n_seq : 0);
-    if (!workspace || workspace_bytes < e.total) {
-        tt_set_error("tt_encoder_forward_f16c: workspace %zu < required %zu bytes", workspace_bytes, e.total);
-        return TT_E_WORKSPACE;
-    }
-    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    if (int rc = tt_check_workspace("tt_encoder_forward_f16c", workspace, workspace_bytes, e.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, T = n_rows;
@@ -604,6 +569,23 @@ int forward_c_impl(const tt_encoder_weights_f16c* w, const int32_t* ids, const i
                            w->type_emb, w->emb_ln_g, w->emb_ln_b, x, xc, xs, T, H, w->vocab, w->max_pos, w->type_vocab, w->ln_eps);
         TT_CHECK_LAUNCH();
     }
+    // The post-attention half of a layer on M rows; every c-planes buffer comes with its scale array: y = GEMMc(c, Wo) + bo + res,
+    // x1 = LayerNorm(y) (fp32 + c-planes xp), f = GELU_erf(GEMMc(xp, W1) + b1), y = GEMMc(f, W2) + b2 + x1,
+    // LayerNorm(y) -> out32 and, unless NULL, its c-planes out_planes / out_s
+    auto half_layer = [&](const tt_layer_weights_f16c& lw, int M, const char* c, const uint8_t* c_s, const float* res, float* y, float* x1,
+                          char* xp, uint8_t* xp_s, char* f, uint8_t* f_s, float* out32, char* out_planes, uint8_t* out_s) -> int {
+        GemmParams go = gemm_c(c, c_s, lw.o_w, (const uint8_t*)lw.o_s, lw.o_b, M, H, H);
+        go.res32 = res; go.ldr = H; go.C32 = y; go.ldc = H;
+        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
+        if (int rc = layernorm_c_launch(y, x1, xp, xp_s, lw.ln1_g, lw.ln1_b, M, H, w->ln_eps, st)) return rc;
+        GemmParams g1 = gemm_c(xp, xp_s, lw.ffn1_w, (const uint8_t*)lw.ffn1_s, lw.ffn1_b, M, F, H);
+        g1.C = (uint16_t*)f; g1.ldc = 2 * F; g1.c_scales = f_s;
+        if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
+        GemmParams g2 = gemm_c(f, f_s, lw.ffn2_w, (const uint8_t*)lw.ffn2_s, lw.ffn2_b, M, H, F);
+        g2.res32 = x1; g2.ldr = H; g2.C32 = y; g2.ldc = H;
+        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
+        return layernorm_c_launch(y, out32, out_planes, out_s, lw.ln2_g, lw.ln2_b, M, H, w->ln_eps, st);
+    };
     for (int l = 0; l < w->layers; ++l) {
         const tt_layer_weights_f16c& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.qkv_s && lw.qkv_b && lw.o_w && lw.o_s && lw.o_b && lw.ln1_g && lw.ln1_b && lw.ffn1_w && lw.ffn1_s &&
@@ -616,13 +598,9 @@ int forward_c_impl(const tt_encoder_weights_f16c* w, const int32_t* ids, const i
                                lw.qkv_b + 2 * H, T, H, H);
         gv.vt = vt; gv.ldvt = 8 * H; gv.vt_col0 = 0;
         if (int rc = tt_gemm_launch(gv, TT_EPI_VT, st)) return rc;
-        AttnParams a{};                 // (the CLS tail's one-query kernel: attention.hip, Q / K as hi + lo planes)
-        a.qk = qk; a.ld_qk = 4 * H; a.q_col0 = 0; a.k_col0 = H; a.qk_lo_off = 2 * H; a.vt = vt; a.ldvt = 8 * H;
-        a.seq_start = seq_start; a.seq_len = seq_len; a.n_seq = n_seq; a.heads = w->heads; a.head_dim = 64; a.max_len = max_len;
-        a.scale = 0.125f; a.out_width = H; a.ld_out = 2 * H;
         if (cls_tail && l == w->layers - 1) {
-            // ---- last layer, first rows only: one-query attention per (sequence, head), then the output projection, the
-            //      LayerNorms and the FFN on n_seq (padded to 256) rows instead of n_rows
+            // ---- last layer, first rows only: one-query attention per (sequence, head), then the second half of the layer
+            //      on n_seq (padded to 256) rows instead of n_rows
             const int Bp = cls_pad_c(n_seq);
             char* cctx = ws + e.off_cctx;
             uint8_t* ccs = (uint8_t*)(ws + e.off_ccs);
@@ -635,70 +613,28 @@ int forward_c_impl(const tt_encoder_weights_f16c* w, const int32_t* ids, const i
             uint8_t* cfs = (uint8_t*)(ws + e.off_cfs);
             TT_CHECK_HIP(hipMemsetAsync(cctx, 0, (size_t)Bp * 4 * H, st));
             TT_CHECK_HIP(hipMemsetAsync(ccs, 0, scale_bytes(Bp, H), st));
+            AttnParams a{};                 // (the one-query kernel: attention.hip, Q / K as hi + lo planes)
+            a.qk = qk; a.ld_qk = 4 * H; a.q_col0 = 0; a.k_col0 = H; a.qk_lo_off = 2 * H; a.vt = vt; a.ldvt = 8 * H;
+            a.seq_start = seq_start; a.seq_len = seq_len; a.n_seq = n_seq; a.heads = w->heads; a.head_dim = 64; a.max_len = max_len;
+            a.scale = 0.125f; a.out_width = H; a.ld_out = 2 * H;
             a.out = (uint16_t*)cctx; a.out_scales = ccs;
             if (int rc = tt_attention_cls_launch(a, st)) return rc;
-            {
-                TtProfScope prof(TT_K_ROWOPS, st);
-                hipLaunchKernelGGL(gather_rows_f32c_kernel, dim3(Bp), dim3(256), 0, st, x, seq_start, n_seq, Bp, H, cx);
-                TT_CHECK_LAUNCH();
-            }
-            GemmParams go = gemm_c(cctx, ccs, lw.o_w, (const uint8_t*)lw.o_s, lw.o_b, Bp, H, H);
-            go.res32 = cx; go.ldr = H; go.C32 = cy; go.ldc = H;
-            if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-            {
-                TtProfScope prof(TT_K_ROWOPS, st);
-                hipLaunchKernelGGL(layernorm_c_kernel, row_grid_c(Bp), dim3(kRowThreadsC), 0, st, cy, cx1, cxc, cxs, lw.ln1_g, lw.ln1_b, Bp, H,
-                                   w->ln_eps);
-                TT_CHECK_LAUNCH();
-            }
-            GemmParams g1 = gemm_c(cxc, cxs, lw.ffn1_w, (const uint8_t*)lw.ffn1_s, lw.ffn1_b, Bp, F, H);
-            g1.C = (uint16_t*)cffn; g1.ldc = 2 * F; g1.c_scales = cfs;
-            if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-            GemmParams g2 = gemm_c(cffn, cfs, lw.ffn2_w, (const uint8_t*)lw.ffn2_s, lw.ffn2_b, Bp, H, F);
-            g2.res32 = cx1; g2.ldr = H; g2.C32 = cy; g2.ldc = H;
-            if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-            TtProfScope prof(TT_K_ROWOPS, st);
-            hipLaunchKernelGGL(layernorm_c_kernel, row_grid_c(Bp), dim3(kRowThreadsC), 0, st, cy, cls_out, (char*)nullptr, (uint8_t*)nullptr,
-                               lw.ln2_g, lw.ln2_b, Bp, H, w->ln_eps);
-            TT_CHECK_LAUNCH();
-            return TT_OK;
+            if (int rc = tt_gather_rows_f32_launch(x, seq_start, n_seq, Bp, H, cx, st)) return rc;
+            return half_layer(lw, Bp, cctx, ccs, cx, cy, cx1, cxc, cxs, cffn, cfs, cls_out, nullptr, nullptr);
         }
         AttnQ2Params a2{};
         a2.qk = qk; a2.ld_qk = 4 * H; a2.q_col0 = 0; a2.k_col0 = H; a2.lo_off = 2 * H; a2.vt = vt; a2.ldvt = 8 * H;
         a2.out = ctx; a2.out_scales = cs; a2.out_width = H; a2.seq_start = seq_start; a2.seq_len = seq_len;
         a2.n_seq = n_seq; a2.heads = w->heads; a2.max_len = max_len; a2.scale = 0.125f;
         if (int rc = attention_qk2_launch(a2, st)) return rc;
-        GemmParams go = gemm_c(ctx, cs, lw.o_w, (const uint8_t*)lw.o_s, lw.o_b, T, H, H);
-        go.res32 = x; go.ldr = H; go.C32 = y; go.ldc = H;
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
         float* x1 = (x == xa) ? xb : xa;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            hipLaunchKernelGGL(layernorm_c_kernel, row_grid_c(T), dim3(kRowThreadsC), 0, st, y, x1, xc, xs, lw.ln1_g, lw.ln1_b, T, H, w->ln_eps);
-            TT_CHECK_LAUNCH();
-        }
-        GemmParams g1 = gemm_c(xc, xs, lw.ffn1_w, (const uint8_t*)lw.ffn1_s, lw.ffn1_b, T, F, H);
-        g1.C = (uint16_t*)ffn; g1.ldc = 2 * F; g1.c_scales = fs;
-        if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-        GemmParams g2 = gemm_c(ffn, fs, lw.ffn2_w, (const uint8_t*)lw.ffn2_s, lw.ffn2_b, T, H, F);
-        g2.res32 = x1; g2.ldr = H; g2.C32 = y; g2.ldc = H;
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
         const bool last = l == w->layers - 1;
         float* dst = last ? hidden_out : x;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            hipLaunchKernelGGL(layernorm_c_kernel, row_grid_c(T), dim3(kRowThreadsC), 0, st, y, dst, last ? (char*)nullptr : xc,
-                               last ? (uint8_t*)nullptr : xs, lw.ln2_g, lw.ln2_b, T, H, w->ln_eps);
-            TT_CHECK_LAUNCH();
-        }
+        if (int rc = half_layer(lw, T, ctx, cs, x, y, x1, xc, xs, ffn, fs, dst, last ? nullptr : xc, last ? nullptr : xs)) return rc;
         x = dst;
     }
-    if (cls_out) {     // no layers: the "last hidden state" is the embedding LayerNorm's output -- gather the first rows
-        TtProfScope prof(TT_K_ROWOPS, st);
-        const int Bp = cls_pad_c(n_seq);
-        hipLaunchKernelGGL(gather_rows_f32c_kernel, dim3(Bp), dim3(256), 0, st, x, seq_start, n_seq, Bp, H, cls_out);
-        TT_CHECK_LAUNCH();
-    }
+    if (cls_out)       // no layers: the "last hidden state" is the embedding LayerNorm's output -- gather the first rows
+        return tt_gather_rows_f32_launch(x, seq_start, n_seq, cls_pad_c(n_seq), H, cls_out, st);
     return TT_OK;
 }
 }  // namespace
@@ -777,11 +713,7 @@ int tt_encoder_forward_f16c_cls(const tt_encoder_weights_f16c* w, const int32_t*
 int tt_rerank_head_f16c(const tt_encoder_weights_f16c* w, const float* hidden_f32, const int32_t* rows, int n_seq, float* scores,
                         float* logits, void* workspace, size_t workspace_bytes, void* stream) {
     TT_CHECK_ARG(w != nullptr, "null weights");
-    tt_encoder_weights_f32 h{};     // the head is a [n_seq x H x H] product: the fp32 kernels (f32_path.hip) on fp32 head weights
-    h.hidden = w->hidden; h.layers = 0; h.heads = w->heads; h.ffn = w->ffn; h.vocab = w->vocab; h.max_pos = w->max_pos;
-    h.type_vocab = w->type_vocab; h.ln_eps = w->ln_eps;
-    h.word_emb = w->word_emb; h.pos_emb = w->pos_emb; h.type_emb = w->type_emb; h.emb_ln_g = w->emb_ln_g; h.emb_ln_b = w->emb_ln_b;
-    h.cls_dense_w = w->cls_dense_w; h.cls_dense_b = w->cls_dense_b; h.cls_out_w = w->cls_out_w; h.cls_out_b = w->cls_out_b;
+    const tt_encoder_weights_f32 h = head_weights_f32(w);
     return tt_rerank_head_f32(&h, hidden_f32, rows, n_seq, scores, logits, workspace, workspace_bytes, stream);
 }
 

@@ -18,16 +18,11 @@
 //   layernorm_f32, cls_pool_f32, head_out_f32
 // Roofline: gemm_f32 is MFMA-bound at the fp32 matrix rate (157 TF/s peak); the rest is bandwidth- or VALU-bound and small.
 #include "common.h"
+#include "encoder.h"
 
 namespace {
 
 constexpr int kRowThreadsF = 256;   // 4 waves, one row per wave
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- LayerNorm of one row held as x[H/64] per lane (element e = lane + 64 * c) -------------------------------
 template <int MAXC>
@@ -59,10 +54,8 @@ __global__ __launch_bounds__(kRowThreadsF) void embed_ln_f32_kernel(const int32_
                                                                      int vocab, int max_pos, int type_vocab, float eps) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= T) return;
-    int id = ids[row], p = pos[row], t = type ? type[row] : 0;
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    t = t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t);
+    int id, p, t;
+    embed_rows_clamped(ids, pos, type, row, vocab, max_pos, type_vocab, id, p, t);
     const int nc = H / 64;
     float x[kMaxC];
 #pragma unroll
@@ -328,6 +321,18 @@ __global__ __launch_bounds__(kRowThreadsF) void gather_rows_f32_kernel(const flo
     for (int e = lane; e < H; e += 64) dst[(size_t)b * H + e] = b < n ? src[(size_t)rows[b] * ld + e] : 0.f;
 }
 
+// the same gather, one workgroup per row in float4 pieces, both matrices [.][H] (tt_gather_rows_f32_launch: the CLS tails of the
+// split-plane and f16c forwards)
+__global__ __launch_bounds__(256) void gather_rows_f32x4_kernel(const float* src, const int32_t* rows, int n, int n_pad, int H, float* dst) {
+    const int b = blockIdx.x;
+    if (b >= n_pad) return;
+    for (int c = threadIdx.x * 4; c < H; c += 256 * 4) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (b < n) v = *reinterpret_cast<const float4*>(src + (size_t)rows[b] * H + c);
+        *reinterpret_cast<float4*>(dst + (size_t)b * H + c) = v;
+    }
+}
+
 __global__ __launch_bounds__(kRowThreadsF) void head_out_f32_kernel(const float* t, int ld, const float* w, const float* bias, int n, int H,
                                                                      float* scores, float* logits) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -348,15 +353,14 @@ struct F32Ws {
 F32Ws f32_plan(const tt_encoder_weights_f32* w, int n_rows) {
     F32Ws e{};
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = (size_t)n_rows;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += tt_align_up(bytes, 256); return o; };
-    e.off_xa = take(T * H * 4);
-    e.off_xb = take(T * H * 4);
-    e.off_y = take(T * H * 4);
-    e.off_qkv = take(T * 3 * H * 4);
-    e.off_ctx = take(T * H * 4);
-    e.off_ffn = take(T * F * 4);
-    e.total = off;
+    WsPlanner ws;
+    e.off_xa = ws.take(T * H * 4);
+    e.off_xb = ws.take(T * H * 4);
+    e.off_y = ws.take(T * H * 4);
+    e.off_qkv = ws.take(T * 3 * H * 4);
+    e.off_ctx = ws.take(T * H * 4);
+    e.off_ffn = ws.take(T * F * 4);
+    e.total = ws.off;
     return e;
 }
 
@@ -376,6 +380,13 @@ inline dim3 row_grid_f(int rows) { return dim3((unsigned)((rows + 3) / 4)); }
 
 }  // namespace
 
+int tt_gather_rows_f32_launch(const float* src, const int32_t* rows, int n, int n_pad, int H, float* dst, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(gather_rows_f32x4_kernel, dim3(n_pad), dim3(256), 0, st, src, rows, n, n_pad, H, dst);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
 extern "C" {
 
 size_t tt_encoder_f32_workspace_bytes(const tt_encoder_weights_f32* w, int n_rows) {
@@ -390,11 +401,7 @@ int tt_encoder_forward_f32(const tt_encoder_weights_f32* w, const int32_t* ids, 
     TT_CHECK_ARG(n_rows > 0 && n_seq > 0 && max_len > 0, "n_rows=%d n_seq=%d max_len=%d", n_rows, n_seq, max_len);
     TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
     const F32Ws e = f32_plan(w, n_rows);
-    if (!workspace || workspace_bytes < e.total) {
-        tt_set_error("tt_encoder_forward_f32: workspace %zu < required %zu bytes", workspace_bytes, e.total);
-        return TT_E_WORKSPACE;
-    }
-    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    if (int rc = tt_check_workspace("tt_encoder_forward_f32", workspace, workspace_bytes, e.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, T = n_rows, dh = H / w->heads;

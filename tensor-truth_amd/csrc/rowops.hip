@@ -14,12 +14,6 @@ namespace {
 constexpr int kRowThreads = 256;  // 4 rows per block
 constexpr int kMaxChunks = 2;     // H <= 1024: at most 2 x (8 bf16) per lane
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
     f[0] = elo(u.x); f[1] = ehi(u.x);
     f[2] = elo(u.y); f[3] = ehi(u.y);

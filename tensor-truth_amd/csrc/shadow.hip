@@ -32,11 +32,6 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr float kShadowScale = 256.0f;
 constexpr int kSWaves = 8, kSThreads = 64 * kSWaves;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ float bf16_to_f32(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
 // e4m3 byte of x (saturating at +-448; NaN stays NaN) and its value back in fp32
 __device__ __forceinline__ uint32_t to_e4m3(float x) {

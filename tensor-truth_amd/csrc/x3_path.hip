@@ -26,20 +26,11 @@
 
 #define TT_MFMA_32x32x16Z(a, b, c, x, y, z) TT_MFMA_32x32x16((a), (b), (c))
 
-extern "C" int tt_rerank_head_f32(const tt_encoder_weights_f32* w, const float* hidden_f32, const int32_t* rows, int n_seq,
-                                  float* scores, float* logits, void* workspace, size_t workspace_bytes, void* stream);
-
 namespace {
 
 // ---- row kernels: one wave per row, lane owns 4 consecutive elements per 256-element chunk ---------------------------
 constexpr int kRowThreadsX = 256;
 constexpr int kMaxC4 = 4;   // H <= 1024
-
-__device__ __forceinline__ float wave_sum_x(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // LayerNorm of a row held as x[c] (float4 = elements 256 c + 4 lane ...), two-pass fp32 statistics; writes the fp32 row
 // (out32, may be NULL) and its two bf16 planes (planes[0..H) = hi, planes[H..2H) = lo; may be NULL)
@@ -60,7 +51,7 @@ __device__ __forceinline__ void ln_row_x3(float4 (&x)[kMaxC4], int nc, int H, co
 #pragma unroll
     for (int c = 0; c < kMaxC4; ++c)
         if (c < nc && lane_has(c, lane, H)) s += (x[c].x + x[c].y) + (x[c].z + x[c].w);
-    const float mean = wave_sum_x(s) / (float)H;
+    const float mean = wave_sum(s) / (float)H;
     float v = 0.f;
 #pragma unroll
     for (int c = 0; c < kMaxC4; ++c)
@@ -68,7 +59,7 @@ __device__ __forceinline__ void ln_row_x3(float4 (&x)[kMaxC4], int nc, int H, co
             const float a = x[c].x - mean, b = x[c].y - mean, d = x[c].z - mean, e = x[c].w - mean;
             v += (a * a + b * b) + (d * d + e * e);
         }
-    const float rstd = 1.0f / sqrtf(wave_sum_x(v) / (float)H + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)H + eps);
 #pragma unroll
     for (int c = 0; c < kMaxC4; ++c)
         if (c < nc && lane_has(c, lane, H)) {
@@ -98,10 +89,8 @@ __global__ __launch_bounds__(kRowThreadsX) void embed_ln_x3_kernel(const int32_t
                                                                     int type_vocab, float eps, int flags) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= T) return;
-    int id = ids[row], p = pos[row], t = type ? type[row] : 0;
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    p = p < 0 ? 0 : (p >= max_pos ? max_pos - 1 : p);
-    t = t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t);
+    int id, p, t;
+    embed_rows_clamped(ids, pos, type, row, vocab, max_pos, type_vocab, id, p, t);
     const int nc = (H + 255) / 256;
     float4 x[kMaxC4];
 #pragma unroll
@@ -168,22 +157,6 @@ struct AttnX3Params {
     int round_flags;          // diagnostic (TT_X3_ROUND_MASK): 1 = probabilities rounded to bf16 (P lo = 0), 2 = context rounded (lo = 0)
     int head_dim;             // 64 (bge-m3, bge-reranker-v2-m3 / -base) or 32 (bge-small-en-v1.5, ms-marco-MiniLM: round 6); 0 = 64
 };
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-template <int OFF>
-__device__ __forceinline__ u32x4 ldsx_read128(uint32_t addr) {
-    u32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void ldsx_wait8(u32x4& a, u32x4& b, u32x4& c, u32x4& d, u32x4& e, u32x4& f, u32x4& g, u32x4& h) {
-    asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "n"(N));
-}
-template <int N>
-__device__ __forceinline__ void ldsx_wait4(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
 
 constexpr int kXKTile = 64, kXWaves = 4;
 // DH = head width: 64, or 32 (round 6: the 384-wide BERT models' 12 x 32 heads -- half the bytes per row and tile, two MFMA K-steps
@@ -324,11 +297,11 @@ __global__ __launch_bounds__(64 * kXWaves, 2) void attention_x3_kernel(AttnX3Par
             u32x4 kh[KS], kl[KS];
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                if (j == 0) { kh[s] = ldsx_read128<0>(koff[s] + bufo); kl[s] = ldsx_read128<kXPlane>(koff[s] + bufo); }
-                else { kh[s] = ldsx_read128<32 * RB>(koff[s] + bufo); kl[s] = ldsx_read128<kXPlane + 32 * RB>(koff[s] + bufo); }
+                if (j == 0) { kh[s] = lds_read128<0>(koff[s] + bufo); kl[s] = lds_read128<kXPlane>(koff[s] + bufo); }
+                else { kh[s] = lds_read128<32 * RB>(koff[s] + bufo); kl[s] = lds_read128<kXPlane + 32 * RB>(koff[s] + bufo); }
             }
-            if constexpr (KS == 4) ldsx_wait8<0>(kh[0], kh[1], kh[2], kh[3], kl[0], kl[1], kl[2], kl[3]);
-            else ldsx_wait4<0>(kh[0], kh[1], kl[0], kl[1]);
+            if constexpr (KS == 4) lds_wait8<0>(kh[0], kh[1], kh[2], kh[3], kl[0], kl[1], kl[2], kl[3]);
+            else lds_wait4<0>(kh[0], kh[1], kl[0], kl[1]);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc_s[j][r] = 0.f;
             // small terms first
@@ -401,29 +374,29 @@ __global__ __launch_bounds__(64 * kXWaves, 2) void attention_x3_kernel(AttnX3Par
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     if (j == 0 && s2 == 0) {
-                        vh[0][0] = ldsx_read128<0>(va); vh[0][1] = ldsx_read128<512>(va);
-                        vl[0][0] = ldsx_read128<kXPlane>(va); vl[0][1] = ldsx_read128<kXPlane + 512>(va);
+                        vh[0][0] = lds_read128<0>(va); vh[0][1] = lds_read128<512>(va);
+                        vl[0][0] = lds_read128<kXPlane>(va); vl[0][1] = lds_read128<kXPlane + 512>(va);
                     } else if (j == 0) {
-                        vh[1][0] = ldsx_read128<2 * DH * 16>(va); vh[1][1] = ldsx_read128<2 * DH * 16 + 512>(va);
-                        vl[1][0] = ldsx_read128<kXPlane + 2 * DH * 16>(va); vl[1][1] = ldsx_read128<kXPlane + 2 * DH * 16 + 512>(va);
+                        vh[1][0] = lds_read128<2 * DH * 16>(va); vh[1][1] = lds_read128<2 * DH * 16 + 512>(va);
+                        vl[1][0] = lds_read128<kXPlane + 2 * DH * 16>(va); vl[1][1] = lds_read128<kXPlane + 2 * DH * 16 + 512>(va);
                     } else if (s2 == 0) {
-                        vh[0][0] = ldsx_read128<4 * DH * 16>(va); vh[0][1] = ldsx_read128<4 * DH * 16 + 512>(va);
-                        vl[0][0] = ldsx_read128<kXPlane + 4 * DH * 16>(va); vl[0][1] = ldsx_read128<kXPlane + 4 * DH * 16 + 512>(va);
+                        vh[0][0] = lds_read128<4 * DH * 16>(va); vh[0][1] = lds_read128<4 * DH * 16 + 512>(va);
+                        vl[0][0] = lds_read128<kXPlane + 4 * DH * 16>(va); vl[0][1] = lds_read128<kXPlane + 4 * DH * 16 + 512>(va);
                     } else {
-                        vh[1][0] = ldsx_read128<6 * DH * 16>(va); vh[1][1] = ldsx_read128<6 * DH * 16 + 512>(va);
-                        vl[1][0] = ldsx_read128<kXPlane + 6 * DH * 16>(va); vl[1][1] = ldsx_read128<kXPlane + 6 * DH * 16 + 512>(va);
+                        vh[1][0] = lds_read128<6 * DH * 16>(va); vh[1][1] = lds_read128<6 * DH * 16 + 512>(va);
+                        vl[1][0] = lds_read128<kXPlane + 6 * DH * 16>(va); vl[1][1] = lds_read128<kXPlane + 6 * DH * 16 + 512>(va);
                     }
                 }
-                ldsx_wait8<0>(vh[0][0], vh[0][1], vh[1][0], vh[1][1], vl[0][0], vl[0][1], vl[1][0], vl[1][1]);
+                lds_wait8<0>(vh[0][0], vh[0][1], vh[1][0], vh[1][1], vl[0][0], vl[0][1], vl[1][0], vl[1][1]);
             } else {          // one 32-feature tile: the fragment of token group 4 j + 2 s2 + hh
                 if (j == 0) {
-                    vh[0][0] = ldsx_read128<0>(va); vl[0][0] = ldsx_read128<kXPlane>(va);
-                    vh[1][0] = ldsx_read128<2 * DH * 16>(va); vl[1][0] = ldsx_read128<kXPlane + 2 * DH * 16>(va);
+                    vh[0][0] = lds_read128<0>(va); vl[0][0] = lds_read128<kXPlane>(va);
+                    vh[1][0] = lds_read128<2 * DH * 16>(va); vl[1][0] = lds_read128<kXPlane + 2 * DH * 16>(va);
                 } else {
-                    vh[0][0] = ldsx_read128<4 * DH * 16>(va); vl[0][0] = ldsx_read128<kXPlane + 4 * DH * 16>(va);
-                    vh[1][0] = ldsx_read128<6 * DH * 16>(va); vl[1][0] = ldsx_read128<kXPlane + 6 * DH * 16>(va);
+                    vh[0][0] = lds_read128<4 * DH * 16>(va); vl[0][0] = lds_read128<kXPlane + 4 * DH * 16>(va);
+                    vh[1][0] = lds_read128<6 * DH * 16>(va); vl[1][0] = lds_read128<kXPlane + 6 * DH * 16>(va);
                 }
-                ldsx_wait4<0>(vh[0][0], vh[1][0], vl[0][0], vl[1][0]);
+                lds_wait4<0>(vh[0][0], vh[1][0], vl[0][0], vl[1][0]);
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -557,7 +530,7 @@ __global__ __launch_bounds__(64) void attention_cls_x3_kernel(AttnX3Params p) {
         probs_x[j] = e;
         sum += e;
     }
-    sum = wave_sum_x(sum);
+    sum = wave_sum(sum);
     __syncthreads();
     const int d = lane;        // one feature per lane (DH = 32: the upper half of the wave has none)
     if (d >= DH) return;
@@ -576,17 +549,6 @@ __global__ __launch_bounds__(64) void attention_cls_x3_kernel(AttnX3Params p) {
     uint16_t* op = p.out + (size_t)seq * p.ld_out + head * DH + d;
     op[0] = (uint16_t)(pack_e2(hi, 0.f) & 0xFFFFu);
     op[p.out_lo_off] = (uint16_t)(pack_e2(o - hi, 0.f) & 0xFFFFu);
-}
-
-// rows seq_start[b] of an fp32 [T][H] matrix -> dst [n_pad][H] (rows beyond n: zeros)
-__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* src, const int32_t* rows, int n, int n_pad, int H, float* dst) {
-    const int b = blockIdx.x;
-    if (b >= n_pad) return;
-    for (int c = threadIdx.x * 4; c < H; c += 256 * 4) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (b < n) v = *reinterpret_cast<const float4*>(src + (size_t)rows[b] * H + c);
-        *reinterpret_cast<float4*>(dst + (size_t)b * H + c) = v;
-    }
 }
 
 int attention_cls_x3_launch(const AttnX3Params& p, hipStream_t st) {
@@ -613,7 +575,7 @@ int attention_cls_x3_launch(const AttnX3Params& p, hipStream_t st) {
     return TT_OK;
 }
 
-inline int x3_cls_pad(int n_seq) { return n_seq <= 256 ? (n_seq + 63) / 64 * 64 : (n_seq + 255) / 256 * 256; }
+inline int x3_cls_pad(int n_seq) { return pooled_rows_pad(n_seq, true); }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 struct X3Ws {
@@ -624,27 +586,26 @@ struct X3Ws {
 X3Ws x3_plan(const tt_encoder_weights_x3* w, int n_rows, int n_cls = 0) {
     X3Ws e{};
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += tt_align_up(bytes, 256); return o; };
-    e.off_xa = take(T * H * 4);
-    e.off_xb = take(T * H * 4);
-    e.off_y = take(T * H * 4);
-    e.off_xpl = take(T * 2 * H * 2);
-    e.off_qk = take(T * 4 * H * 2);
-    e.off_vt = take(T * H * 2);
-    e.off_vtlo = take(T * H * 2);
-    e.off_ctx = take(T * 2 * H * 2);
-    e.off_ffn = take(T * 2 * F * 2);
+    WsPlanner ws;
+    e.off_xa = ws.take(T * H * 4);
+    e.off_xb = ws.take(T * H * 4);
+    e.off_y = ws.take(T * H * 4);
+    e.off_xpl = ws.take(T * 2 * H * 2);
+    e.off_qk = ws.take(T * 4 * H * 2);
+    e.off_vt = ws.take(T * H * 2);
+    e.off_vtlo = ws.take(T * H * 2);
+    e.off_ctx = ws.take(T * 2 * H * 2);
+    e.off_ffn = ws.take(T * 2 * F * 2);
     if (n_cls > 0) {
         const size_t B = (size_t)x3_cls_pad(n_cls);
-        e.off_cctx = take(B * 2 * H * 2);
-        e.off_cx = take(B * H * 4);
-        e.off_cy = take(B * H * 4);
-        e.off_cx1 = take(B * H * 4);
-        e.off_cxpl = take(B * 2 * H * 2);
-        e.off_cffn = take(B * 2 * F * 2);
+        e.off_cctx = ws.take(B * 2 * H * 2);
+        e.off_cx = ws.take(B * H * 4);
+        e.off_cy = ws.take(B * H * 4);
+        e.off_cx1 = ws.take(B * H * 4);
+        e.off_cxpl = ws.take(B * 2 * H * 2);
+        e.off_cffn = ws.take(B * 2 * F * 2);
     }
-    e.total = off;
+    e.total = ws.off;
     return e;
 }
 
@@ -662,6 +623,24 @@ int check_weights_x3(const tt_encoder_weights_x3* w) {
 }
 
 inline dim3 row_grid_x(int rows) { return dim3((unsigned)((rows + 3) / 4)); }
+
+// one projection on split-plane operands: A [M][2K], W [N][2K] (the caller adds the epilogue's output and residual)
+GemmParams gemm_x3(const void* a_planes, const void* w_planes, const float* bias, int M, int N, int K) {
+    GemmParams g{};
+    g.x3 = 1;
+    g.A = (const uint16_t*)a_planes; g.lda = 2 * K; g.W = (const uint16_t*)w_planes; g.ldw = 2 * K;
+    g.bias = bias; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
+// LayerNorm of fp32 rows into the fp32 row (out32, may be NULL) and / or its planes (may be NULL)
+int layernorm_x3_launch(const float* in, float* out32, uint16_t* planes, const float* gamma, const float* beta, int rows, int H, float eps,
+                        int flags, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(layernorm_x3_kernel, row_grid_x(rows), dim3(kRowThreadsX), 0, st, in, out32, planes, gamma, beta, rows, H, eps, flags);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
 
 }  // namespace
 
@@ -687,11 +666,7 @@ int forward_x3_impl(const tt_encoder_weights_x3* w, const int32_t* ids, const in
     TT_CHECK_ARG(ids && pos && seq_start && seq_len && (hidden_out || cls_out), "null pointer");
     const bool cls_tail = cls_out != nullptr && w->layers > 0;
     const X3Ws e = x3_plan(w, n_rows, cls_tail ? n_seq : 0);
-    if (!workspace || workspace_bytes < e.total) {
-        tt_set_error("tt_encoder_forward_x3: workspace %zu < required %zu bytes", workspace_bytes, e.total);
-        return TT_E_WORKSPACE;
-    }
-    TT_CHECK_ARG(((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
+    if (int rc = tt_check_workspace("tt_encoder_forward_x3", workspace, workspace_bytes, e.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, T = n_rows;
@@ -727,15 +702,34 @@ int forward_x3_impl(const tt_encoder_weights_x3* w, const int32_t* ids, const in
                            w->type_emb, w->emb_ln_g, w->emb_ln_b, x, xpl, T, H, w->vocab, w->max_pos, w->type_vocab, w->ln_eps, ln_out);
         TT_CHECK_LAUNCH();
     }
+    // The post-attention half of a layer on M rows: y = GEMMx3(c, Wo) + bo + residual, x1 = LayerNorm(y) (fp32 + planes xp),
+    // f = GELU_erf(GEMMx3(xp, W1) + b1), y = GEMMx3(f, W2) + b2 + x1, LayerNorm(y) -> out32 and / or out_planes (either may be NULL).
+    // res_pl: both residuals are rebuilt from the planes xp (xp holds the layer input's planes on entry) and no fp32 copy of x1
+    // is written; otherwise the residuals are the fp32 rows res and x1.  The CLS tail passes res_pl = false.
+    auto half_layer = [&](const tt_layer_weights_x3& lw, int M, const uint16_t* c, const float* res, float* y, float* x1, uint16_t* xp,
+                          uint16_t* f, float* out32, uint16_t* out_planes, bool res_pl) -> int {
+        GemmParams go = gemm_x3(c, lw.o_w, lw.o_b, M, H, H);
+        go.res32 = res; go.ldr = H; go.C32 = y; go.ldc = H;
+        if (res_pl) { go.res32 = nullptr; go.res_planes = xp; go.res_lo_off = H; go.ldr = 2 * H; }
+        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
+        if (int rc = layernorm_x3_launch(y, res_pl ? nullptr : x1, xp, lw.ln1_g, lw.ln1_b, M, H, w->ln_eps, ln_in | ln_out, st)) return rc;
+        GemmParams g1 = gemm_x3(xp, lw.ffn1_w, lw.ffn1_b, M, F, H);
+        g1.C = f; g1.ldc = 2 * F; g1.c_lo_off = F;
+        g1.x3_zero_lo = (rmask & 64) ? 1 : 0;
+        if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
+        GemmParams g2 = gemm_x3(f, lw.ffn2_w, lw.ffn2_b, M, H, F);
+        g2.res32 = x1; g2.ldr = H; g2.C32 = y; g2.ldc = H;
+        if (res_pl) { g2.res32 = nullptr; g2.res_planes = xp; g2.res_lo_off = H; g2.ldr = 2 * H; }
+        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
+        return layernorm_x3_launch(y, out32, out_planes, lw.ln2_g, lw.ln2_b, M, H, w->ln_eps, ln_in | ln_out, st);
+    };
     for (int l = 0; l < w->layers; ++l) {
         const tt_layer_weights_x3& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.qkv_b && lw.o_w && lw.o_b && lw.ln1_g && lw.ln1_b && lw.ffn1_w && lw.ffn1_b && lw.ffn2_w &&
                          lw.ffn2_b && lw.ln2_g && lw.ln2_b, "layer %d has a null weight pointer", l);
         // Q, K columns -> planes [T][4H] (hi at [0, 2H), lo at [2H, 4H)); V columns -> V8 hi / lo
-        GemmParams g{};
-        g.x3 = 1;
-        g.A = xpl; g.lda = 2 * H; g.W = (const uint16_t*)lw.qkv_w; g.ldw = 2 * H; g.bias = lw.qkv_b;
-        g.C = qk; g.ldc = 4 * H; g.c_lo_off = 2 * H; g.M = T; g.N = 2 * H; g.K = H;
+        GemmParams g = gemm_x3(xpl, lw.qkv_w, lw.qkv_b, T, 2 * H, H);
+        g.C = qk; g.ldc = 4 * H; g.c_lo_off = 2 * H;
         g.x3_zero_lo = (rmask & 2) ? 1 : 0;
         if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
         GemmParams gv = g;
@@ -743,9 +737,14 @@ int forward_x3_impl(const tt_encoder_weights_x3* w, const int32_t* ids, const in
         gv.bias = lw.qkv_b + 2 * H;
         gv.N = H; gv.vt = vt; gv.vt_lo = vtlo; gv.ldvt = 8 * H; gv.vt_col0 = 0;
         if (int rc = tt_gemm_launch(gv, TT_EPI_VT, st)) return rc;
+        AttnX3Params a{};
+        a.qk = qk; a.ld_qk = 4 * H; a.q_col0 = 0; a.k_col0 = H; a.lo_off = 2 * H; a.vt = vt; a.vt_lo = vtlo; a.ldvt = 8 * H;
+        a.ld_out = 2 * H; a.out_lo_off = H; a.seq_start = seq_start; a.seq_len = seq_len;
+        a.n_seq = n_seq; a.heads = w->heads; a.max_len = max_len; a.head_dim = H / w->heads;
+        a.scale = 1.0f / sqrtf((float)a.head_dim);
         if (cls_tail && l == w->layers - 1) {
-            // ---- last layer, first rows only: one-query attention per (sequence, head), then the output projection, the
-            //      LayerNorms and the FFN on n_seq (padded) rows instead of n_rows
+            // ---- last layer, first rows only: one-query attention per (sequence, head), then the second half of the layer
+            //      on n_seq (padded) rows instead of n_rows
             const int Bp = x3_cls_pad(n_seq);
             uint16_t* cctx = (uint16_t*)(ws + e.off_cctx);
             float* cx = (float*)(ws + e.off_cx);
@@ -754,95 +753,24 @@ int forward_x3_impl(const tt_encoder_weights_x3* w, const int32_t* ids, const in
             uint16_t* cxpl = (uint16_t*)(ws + e.off_cxpl);
             uint16_t* cffn = (uint16_t*)(ws + e.off_cffn);
             TT_CHECK_HIP(hipMemsetAsync(cctx, 0, (size_t)Bp * 2 * H * 2, st));
-            AttnX3Params ac{};
-            ac.qk = qk; ac.ld_qk = 4 * H; ac.q_col0 = 0; ac.k_col0 = H; ac.lo_off = 2 * H; ac.vt = vt; ac.vt_lo = vtlo; ac.ldvt = 8 * H;
-            ac.out = cctx; ac.ld_out = 2 * H; ac.out_lo_off = H; ac.seq_start = seq_start; ac.seq_len = seq_len;
-            ac.n_seq = n_seq; ac.heads = w->heads; ac.max_len = max_len; ac.head_dim = H / w->heads;
-            ac.scale = 1.0f / sqrtf((float)ac.head_dim);
-            if (int rc = attention_cls_x3_launch(ac, st)) return rc;
-            {
-                TtProfScope prof(TT_K_ROWOPS, st);
-                hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(Bp), dim3(256), 0, st, x, seq_start, n_seq, Bp, H, cx);
-                TT_CHECK_LAUNCH();
-            }
-            GemmParams go{};
-            go.x3 = 1;
-            go.A = cctx; go.lda = 2 * H; go.W = (const uint16_t*)lw.o_w; go.ldw = 2 * H; go.bias = lw.o_b;
-            go.res32 = cx; go.ldr = H; go.C32 = cy; go.ldc = H; go.M = Bp; go.N = H; go.K = H;
-            if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-            {
-                TtProfScope prof(TT_K_ROWOPS, st);
-                hipLaunchKernelGGL(layernorm_x3_kernel, row_grid_x(Bp), dim3(kRowThreadsX), 0, st, cy, cx1, cxpl, lw.ln1_g, lw.ln1_b, Bp, H,
-                                   w->ln_eps, ln_in | ln_out);
-                TT_CHECK_LAUNCH();
-            }
-            GemmParams g1{};
-            g1.x3 = 1;
-            g1.A = cxpl; g1.lda = 2 * H; g1.W = (const uint16_t*)lw.ffn1_w; g1.ldw = 2 * H; g1.bias = lw.ffn1_b;
-            g1.C = cffn; g1.ldc = 2 * F; g1.c_lo_off = F; g1.M = Bp; g1.N = F; g1.K = H;
-            g1.x3_zero_lo = (rmask & 64) ? 1 : 0;
-            if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-            GemmParams g2{};
-            g2.x3 = 1;
-            g2.A = cffn; g2.lda = 2 * F; g2.W = (const uint16_t*)lw.ffn2_w; g2.ldw = 2 * F; g2.bias = lw.ffn2_b;
-            g2.res32 = cx1; g2.ldr = H; g2.C32 = cy; g2.ldc = H; g2.M = Bp; g2.N = H; g2.K = F;
-            if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-            TtProfScope prof(TT_K_ROWOPS, st);
-            hipLaunchKernelGGL(layernorm_x3_kernel, row_grid_x(Bp), dim3(kRowThreadsX), 0, st, cy, cls_out, (uint16_t*)nullptr, lw.ln2_g,
-                               lw.ln2_b, Bp, H, w->ln_eps, ln_in | ln_out);
-            TT_CHECK_LAUNCH();
-            return TT_OK;
+            a.out = cctx;
+            if (int rc = attention_cls_x3_launch(a, st)) return rc;
+            if (int rc = tt_gather_rows_f32_launch(x, seq_start, n_seq, Bp, H, cx, st)) return rc;
+            return half_layer(lw, Bp, cctx, cx, cy, cx1, cxpl, cffn, cls_out, nullptr, false);
         }
-        AttnX3Params a{};
-        a.qk = qk; a.ld_qk = 4 * H; a.q_col0 = 0; a.k_col0 = H; a.lo_off = 2 * H; a.vt = vt; a.vt_lo = vtlo; a.ldvt = 8 * H;
-        a.out = ctx; a.ld_out = 2 * H; a.out_lo_off = H; a.seq_start = seq_start; a.seq_len = seq_len;
-        a.n_seq = n_seq; a.heads = w->heads; a.max_len = max_len; a.head_dim = H / w->heads;
-        a.scale = 1.0f / sqrtf((float)a.head_dim);
+        a.out = ctx;
         a.round_flags = ((rmask & 4) ? 1 : 0) | ((rmask & 8) ? 2 : 0);
         if (int rc = attention_x3_launch(a, st)) return rc;
-        GemmParams go{};
-        go.x3 = 1;
-        go.A = ctx; go.lda = 2 * H; go.W = (const uint16_t*)lw.o_w; go.ldw = 2 * H; go.bias = lw.o_b;
-        go.res32 = x; go.ldr = H; go.C32 = y; go.ldc = H; go.M = T; go.N = H; go.K = H;
-        if (res_planes) { go.res32 = nullptr; go.res_planes = xpl; go.res_lo_off = H; go.ldr = 2 * H; }
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
         float* x1 = (x == xa) ? xb : xa;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            hipLaunchKernelGGL(layernorm_x3_kernel, row_grid_x(T), dim3(kRowThreadsX), 0, st, y, res_planes ? (float*)nullptr : x1, xpl, lw.ln1_g,
-                               lw.ln1_b, T, H, w->ln_eps, ln_in | ln_out);
-            TT_CHECK_LAUNCH();
-        }
-        GemmParams g1{};
-        g1.x3 = 1;
-        g1.A = xpl; g1.lda = 2 * H; g1.W = (const uint16_t*)lw.ffn1_w; g1.ldw = 2 * H; g1.bias = lw.ffn1_b;
-        g1.C = ffn; g1.ldc = 2 * F; g1.c_lo_off = F; g1.M = T; g1.N = F; g1.K = H;
-        g1.x3_zero_lo = (rmask & 64) ? 1 : 0;
-        if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-        GemmParams g2{};
-        g2.x3 = 1;
-        g2.A = ffn; g2.lda = 2 * F; g2.W = (const uint16_t*)lw.ffn2_w; g2.ldw = 2 * F; g2.bias = lw.ffn2_b;
-        g2.res32 = x1; g2.ldr = H; g2.C32 = y; g2.ldc = H; g2.M = T; g2.N = H; g2.K = F;
-        if (res_planes) { g2.res32 = nullptr; g2.res_planes = xpl; g2.res_lo_off = H; g2.ldr = 2 * H; }
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
         const bool last = l == w->layers - 1;
         float* dst = last ? hidden_out : x;
         // (the fp32 copy is still written where something reads it: the forward's output, and the input of a first-rows-only last layer)
         const bool want32 = !res_planes || last || (cls_tail && l == w->layers - 2);
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            hipLaunchKernelGGL(layernorm_x3_kernel, row_grid_x(T), dim3(kRowThreadsX), 0, st, y, want32 ? dst : (float*)nullptr,
-                               last ? (uint16_t*)nullptr : xpl, lw.ln2_g, lw.ln2_b, T, H, w->ln_eps, ln_in | ln_out);
-            TT_CHECK_LAUNCH();
-        }
+        if (int rc = half_layer(lw, T, ctx, x, y, x1, xpl, ffn, want32 ? dst : nullptr, last ? nullptr : xpl, res_planes)) return rc;
         x = dst;
     }
-    if (cls_out) {     // no layers: the "last hidden state" is the embedding LayerNorm's output -- gather the first rows
-        TtProfScope prof(TT_K_ROWOPS, st);
-        const int Bp = x3_cls_pad(n_seq);
-        hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(Bp), dim3(256), 0, st, x, seq_start, n_seq, Bp, H, cls_out);
-        TT_CHECK_LAUNCH();
-    }
+    if (cls_out)       // no layers: the "last hidden state" is the embedding LayerNorm's output -- gather the first rows
+        return tt_gather_rows_f32_launch(x, seq_start, n_seq, x3_cls_pad(n_seq), H, cls_out, st);
     return TT_OK;
 }
 }  // namespace
@@ -873,11 +801,7 @@ int tt_encoder_forward_x3_cls(const tt_encoder_weights_x3* w, const int32_t* ids
 int tt_rerank_head_x3(const tt_encoder_weights_x3* w, const float* hidden_f32, const int32_t* rows, int n_seq, float* scores,
                       float* logits, void* workspace, size_t workspace_bytes, void* stream) {
     TT_CHECK_ARG(w != nullptr, "null weights");
-    tt_encoder_weights_f32 h{};     // the head is a [n_seq x H x H] product: the fp32 kernels (f32_path.hip) on fp32 head weights
-    h.hidden = w->hidden; h.layers = 0; h.heads = w->heads; h.ffn = w->ffn; h.vocab = w->vocab; h.max_pos = w->max_pos;
-    h.type_vocab = w->type_vocab; h.ln_eps = w->ln_eps;
-    h.word_emb = w->word_emb; h.pos_emb = w->pos_emb; h.type_emb = w->type_emb; h.emb_ln_g = w->emb_ln_g; h.emb_ln_b = w->emb_ln_b;
-    h.cls_dense_w = w->cls_dense_w; h.cls_dense_b = w->cls_dense_b; h.cls_out_w = w->cls_out_w; h.cls_out_b = w->cls_out_b;
+    const tt_encoder_weights_f32 h = head_weights_f32(w);
     return tt_rerank_head_f32(&h, hidden_f32, rows, n_seq, scores, logits, workspace, workspace_bytes, stream);
 }
 
@@ -896,10 +820,7 @@ int tt_gemm_x3(const void* a_planes, const void* w_planes, const float* bias, co
                float* c_f32, int m, int n, int k, int epilogue, void* stream) {
     TT_CHECK_ARG(a_planes && w_planes && bias, "null pointer");
     TT_CHECK_ARG(epilogue == TT_EPI_BIAS || epilogue == TT_EPI_GELU || epilogue == TT_EPI_RESIDUAL, "epilogue %d", epilogue);
-    GemmParams g{};
-    g.x3 = 1;
-    g.A = (const uint16_t*)a_planes; g.lda = 2 * k; g.W = (const uint16_t*)w_planes; g.ldw = 2 * k; g.bias = bias;
-    g.M = m; g.N = n; g.K = k;
+    GemmParams g = gemm_x3(a_planes, w_planes, bias, m, n, k);
     if (epilogue == TT_EPI_RESIDUAL) {
         TT_CHECK_ARG(residual_f32 && c_f32, "residual epilogue: fp32 residual and fp32 output");
         g.res32 = residual_f32; g.ldr = n; g.C32 = c_f32; g.ldc = n;
