@@ -658,6 +658,76 @@ int tt_attention_causal_gqa_f16(const void* qkv, int ld, int q_col0, int k_col0,
                                 const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads,
                                 int head_dim, int max_len, void* stream);
 
+/* ---- ModernBERT encoders: embedders and ModernBertForSequenceClassification cross-encoders (csrc/modernbert.hip) -----------
+ * gte-modernbert, gte-reranker-modernbert, nomic modernbert-embed and the answerdotai/ModernBERT fine-tunes.  Pre-norm encoder
+ * block without biases: h = LayerNorm(tok_embeddings[ids]) (weight only; no position table, no token types); per layer
+ *   x = attn_norm(h) (layer 0: none) -> Wqkv -> rotate-half RoPE of q and k with the layer's base (positions 0-based within each
+ *   sequence) -> bidirectional attention over the sequence's own tokens, on a "sliding" layer restricted to keys with
+ *   |q - k| <= local_attention / 2 -> Wo + residual -> mlp_norm -> Wi ([2F][H]: "input" rows, then "gate" rows) ->
+ *   GELU_erf(input) * gate -> mlp.Wo + residual;
+ * a final LayerNorm.  Same packed token layout as tt_encoder_forward (`pos` = position within the sequence, type_ids must be
+ * NULL), same projections (the 16-bit GEMMs), bf16 -- or fp16 for the `_f16` twins.  Matrices [out][in] in the element type, norm
+ * weights fp32.  hidden a multiple of 128 and <= 1024, hidden = 64 * heads (head_dim 64), ffn a multiple of 64; anything else is
+ * refused before a launch. */
+typedef struct tt_modernbert_layer_weights {
+    const void* qkv_w;        /* [3H][H] attn.Wqkv: q rows, k rows, v rows */
+    const void* o_w;          /* [H][H] attn.Wo */
+    const float* attn_norm;   /* [H], NULL for a layer without one (layer 0) */
+    const float* mlp_norm;    /* [H] */
+    const void* wi_w;         /* [2F][H] mlp.Wi */
+    const void* wo_w;         /* [H][F] mlp.Wo */
+    int32_t sliding;          /* 1: a sliding_attention layer (window, local RoPE base); 0: full_attention (global base) */
+} tt_modernbert_layer_weights;
+
+typedef struct tt_modernbert_weights {
+    int32_t hidden, layers, heads, ffn, vocab, local_attention;
+    float norm_eps, global_rope_theta, local_rope_theta;
+    const void* embed;        /* [vocab][H] embeddings.tok_embeddings */
+    const float* emb_norm;    /* [H] embeddings.norm */
+    const tt_modernbert_layer_weights* layer; /* host array [layers] */
+    const float* final_norm;  /* [H] */
+    /* classification head (tt_modernbert_head; NULL for an embedder), all fp32 */
+    const float* head_dense_wt; /* [H][H] head.dense.weight TRANSPOSED: [in][out] */
+    const float* head_norm;     /* [H] head.norm */
+    const float* cls_w;         /* [H] classifier.weight (one label) */
+    const float* cls_b;         /* [1] classifier.bias */
+} tt_modernbert_weights;
+
+size_t tt_modernbert_workspace_bytes(const tt_modernbert_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state (after the final norm) */
+int tt_modernbert_forward(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                          const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* Head of ModernBertForSequenceClassification, one label, fp32 arithmetic: p = hidden[seq_start[b]] (pooling 0, "cls") or the mean
+ * of the sequence's rows (pooling 1, "mean"); logits[b] = classifier(LayerNorm(GELU_erf(head.dense(p)))), scores[b] =
+ * sigmoid(logits[b]); hidden [.][ld] in the element type (tt_modernbert_forward's output); logits optional. */
+int tt_modernbert_head(const tt_modernbert_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
+                       int n_seq, int pooling, float* scores, float* logits, void* stream);
+/* building blocks (parity tests; the forward's own kernels).
+ * tt_rope_v8: rows of qkv [n_rows][ld] (q heads at column h * 64, k heads behind them, v heads behind those; n_rows a multiple of
+ *   8): q and k heads rotated by rotate-half RoPE of base rope_theta at pos[row] in place (angles in fp32); the v heads copied to
+ *   the V8 layout of tt_attention_varlen, vt[(row / 8) * ldvt + feature * 8 + row % 8].
+ * tt_attention_window: out[q][h * 64 ...] = softmax over the keys k of q's own sequence with |q - k| <= window of
+ *   (Q_h . K_h) / 8, applied to V_h (window < 0: every key of the sequence); Q at q_col0 + h * 64, K at k_col0 + h * 64 of rows of
+ *   ld elements, V in the V8 layout; any sequence start; rows of no sequence are not written.  head_dim must be 64. */
+int tt_rope_v8(void* qkv, int ld, const int32_t* pos, int n_rows, int heads, int head_dim, float rope_theta, void* vt, int ldvt,
+               void* stream);
+int tt_attention_window(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                        int max_len, int window, void* stream);
+/* the fp16 twins (modernbert.hip compiled a second time) */
+size_t tt_modernbert_workspace_bytes_f16(const tt_modernbert_weights* w, int n_rows);
+int tt_modernbert_forward_f16(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                              const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int tt_modernbert_head_f16(const tt_modernbert_weights* w, const void* hidden, int ld, const int32_t* seq_start,
+                           const int32_t* seq_len, int n_seq, int pooling, float* scores, float* logits, void* stream);
+int tt_rope_v8_f16(void* qkv, int ld, const int32_t* pos, int n_rows, int heads, int head_dim, float rope_theta, void* vt, int ldvt,
+                   void* stream);
+int tt_attention_window_f16(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                            int max_len, int window, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

@@ -201,6 +201,21 @@ SIGNATURES = {
                                  c_void_p, c_int, c_void_p]),
     "tt_attention_causal_gqa_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # ModernBERT encoders (csrc/modernbert.hip) and their fp16 twins (same signatures)
+    "tt_modernbert_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "tt_modernbert_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_modernbert_head": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tt_rope_v8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    "tt_attention_window": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "tt_modernbert_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
+    "tt_modernbert_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_modernbert_head_f16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "tt_rope_v8_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    "tt_attention_window_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

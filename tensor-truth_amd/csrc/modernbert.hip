@@ -1,0 +1,538 @@
+// ModernBERT encoders (ModernBertModel embedders, ModernBertForSequenceClassification cross-encoders): the whole-model forward, the
+// classification head and the kernels that only this family needs (include/tt_hip.h, "ModernBERT encoders").  The projections run
+// on the encoder's GEMMs (gemm.hip), the LayerNorms on the encoder's row op (rowops.hip) with a zero beta, and the global layers'
+// attention on the encoder's bidirectional kernel (attention.hip).
+//
+// Layer schedule (pre-norm block, no biases; one rounding to the element type per kernel output):
+//   x    = LayerNorm(h) * g_attn                         [T][H]   (layer 0 has no attn_norm: x = h)
+//   qkv  = GEMM(x, Wqkv)                                 [T][3H]  Q | K | V, heads of 64
+//   qkv  = RoPE(q), RoPE(k) with the layer's base        in place; V copied to the V8 layout vt
+//   ctx  = attention(qkv, vt)                            [T][H]   bidirectional; a sliding layer keeps |q - k| <= local_attention / 2
+//   h1   = GEMM(ctx, Wo) + h                             residual fused in the epilogue
+//   x    = LayerNorm(h1) * g_mlp
+//   gu   = GEMM(x, Wi)                                   [T][2F]  "input" columns, then "gate" columns
+//   a    = GELU_erf(gu[:, :F]) * gu[:, F:]               [T][F]
+//   h    = GEMM(a, Wo_mlp) + h1
+// with h = LayerNorm(tok_embeddings[ids]) * g_emb before the first layer and out = LayerNorm(h) * g_final after the last.  Every
+// row op reads one token row only, so a token's result does not depend on how the batch is packed; the attention mixes the rows of
+// one sequence only.
+//
+// Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
+#include "common.h"
+#include "encoder.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+__device__ __forceinline__ float mb_wave_sum(float v) {
+    // butterfly: every lane ends with the same bits (a + b == b + a)
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ float mb_wave_max16(float v) {
+    // maximum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (one query column of an MFMA 16x16 result)
+    v = fmaxf(v, __shfl_xor(v, 16, 64));
+    return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+
+// GELU(x) = 0.5 x (1 + erf(x / sqrt 2)), the exact-erf form of the encoder's GEMM epilogue (gemm.hip gelu_erf2, one value at a
+// time): gelu(x) = max(x, 0) - |x| 2^Q(|x|), Q the degree-7 fit of log2 Phi(-u) on [0, 9]; abs error <= 1e-5.
+__device__ __forceinline__ float mb_gelu_erf(float x) {
+    const float u = fabsf(x);
+    float q = u * -9.697845371e-07f + 4.016999810e-05f;
+    q = q * u + -7.211678312e-04f;
+    q = q * u + 7.490924560e-03f;
+    q = q * u + -5.142170191e-02f;
+    q = q * u + -4.614778757e-01f;
+    q = q * u + -1.149914980e+00f;
+    q = q * u + -1.000091195e+00f;
+    return fmaxf(x, 0.f) - u * __builtin_amdgcn_exp2f(q);
+}
+
+// ---- embedding gather: out[r] = table[ids[r]] (an id outside [0, vocab) gives a zero row) ------------------------------------
+__global__ __launch_bounds__(128) void mb_embed_kernel(const int32_t* __restrict__ ids, const uint16_t* __restrict__ table, int vocab,
+                                                       int H, uint16_t* __restrict__ out) {
+    const int row = blockIdx.x;
+    const int id = ids[row];
+    const bool ok = id >= 0 && id < vocab;
+    const uint4* src = reinterpret_cast<const uint4*>(table + (size_t)(ok ? id : 0) * H);
+    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)row * H);
+    for (int c = threadIdx.x; c < H / 8; c += blockDim.x) dst[c] = ok ? src[c] : uint4{0u, 0u, 0u, 0u};
+}
+
+// ---- rotate-half RoPE of the q and k heads with base theta, in place; V heads copied to the V8 layout ------------------------
+// One block per token row, one wave per head at a time; heads of 64: lane i < 32 holds the pair (i, i + 32).
+//   inv_freq[i] = theta^(-2 i / 64), angle = pos * inv_freq[i] (fp32, as transformers' default rotary embedding)
+//   out[i] = x[i] cos - x[i + 32] sin,  out[i + 32] = x[i + 32] cos + x[i] sin
+// inv_freq comes from the host, rounded once from double (a kernel argument: 32 floats): at position 8191 an error of a few ulp in
+// it, as a device powf may leave, is an angle error of 1e-3 rad -- more than fp16's unit roundoff.
+// Lane i reads inv[i] with one global_load_dword from the kernel-argument segment (no scratch copy: checked in the disassembly).
+struct MbRopeFreq {
+    float inv[32];
+};
+__global__ __launch_bounds__(256) void mb_rope_kernel(uint16_t* __restrict__ qkv, int ld, const int32_t* __restrict__ pos, int heads,
+                                                      MbRopeFreq freq, uint16_t* __restrict__ vt, int ldvt) {
+    constexpr int D = 64, half = 32;
+    const int row = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float p = (float)pos[row];
+    uint16_t* r = qkv + (size_t)row * ld;
+    float c = 1.f, s = 0.f;
+    if (lane < half) sincosf(p * freq.inv[lane], &s, &c);
+    for (int h = wave; h < 3 * heads; h += 4) {
+        uint16_t* x = r + (size_t)h * D;
+        if (h >= 2 * heads) {   // V head: vt[(row / 8) * ldvt + feature * 8 + row % 8]
+            const size_t f0 = (size_t)(h - 2 * heads) * D;
+            vt[(size_t)(row >> 3) * ldvt + (f0 + lane) * 8 + (row & 7)] = x[lane];
+            continue;
+        }
+        if (lane < half) {
+            const float a = ebits_to_f32(x[lane]), b = ebits_to_f32(x[lane + half]);
+            x[lane] = f32_to_ebits(a * c - b * s);
+            x[lane + half] = f32_to_ebits(b * c + a * s);
+        }
+    }
+}
+
+// ---- GELU_erf(input) * gate: gu [T][2F] (input columns, then gate columns) -> out [T][F] -------------------------------------
+__global__ __launch_bounds__(256) void mb_geglu_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
+                                                       int F) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_chunks) return;
+    const int64_t row = i / (F / 8), c = i % (F / 8);
+    const uint4 iv = reinterpret_cast<const uint4*>(gu + row * 2 * F)[c];
+    const uint4 gv = reinterpret_cast<const uint4*>(gu + row * 2 * F + F)[c];
+    const uint32_t i4[4] = {iv.x, iv.y, iv.z, iv.w}, g4[4] = {gv.x, gv.y, gv.z, gv.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = pack_e2(mb_gelu_erf(elo(i4[k])) * elo(g4[k]), mb_gelu_erf(ehi(i4[k])) * ehi(g4[k]));
+    reinterpret_cast<uint4*>(out + row * F)[c] = uint4{o[0], o[1], o[2], o[3]};
+}
+
+// ---- bidirectional attention with a sliding window over packed varlen sequences, head_dim 64 ---------------------------------
+// One wave per (16-query tile, sequence, head), on the decoder's tile routine (decoder.hip dec_attention_tile) with another key
+// range and mask.  Tile q0 .. q0 + 15 of a sequence s0 .. s_end - 1 visits the key blocks of 32, on the absolute 8-row grid, that
+// intersect [max(s0, q0 - w), min(s_end - 1, q0 + 15 + w)]; key k is live for query q iff s0 <= k < s_end && |q - k| <= w (the mask
+// also removes the neighbouring sequences' rows of shared 8-row groups).  w >= the batch's longest sequence: every key of the
+// sequence, the walk and the bits of a layer without a window.
+//   S^T = K Q^T  (mfma 16x16x32, two tiles per key block).  The K rows each lane loads are permuted so that, for query c = lane & 15,
+//                lane l ends up holding the scores of keys kb + 8 (l >> 4) + j, j = 0..7 -- exactly the B operand of
+//   O^T += V^T P^T  (mfma 16x16x32 per 16 features), whose A operand is one 16-byte read of the V8 layout per lane.
+// Softmax in fp32 with a running maximum (log2 domain), P rounded to the element type for the product; the denominator sums the
+// rounded P, so the weights of a row sum to one as they are applied.  A block may hold no live key for some query of the tile (the
+// window's edge): its P is zero and its running maximum stays where it was (-1e30 before the query's first live key).
+__device__ __forceinline__ void mb_attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
+                                                  const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out, int ld_out,
+                                                  const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len,
+                                                  int n_rows, int w, float scale_log2, int b, int h, int t) {
+    constexpr int D = 64;
+    const int s0 = seq_start[b], L = seq_len[b];
+    if (s0 < 0 || 16 * t >= L) return;
+    const int s_end = min(s0 + L, n_rows);
+    const int q0 = s0 + 16 * t;
+    if (q0 >= s_end) return;
+    const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
+    const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
+
+    // Q fragment, the B operand of S^T: lane holds Q[q0 + c][32 kk + 8 g + j]
+    ex8 qf[D / 32];
+    const int qrow = q0 + c;
+    const int q_ref = min(qrow, s_end - 1);      // rows past the sequence: computed against its keys, never stored
+#pragma unroll
+    for (int kk = 0; kk < D / 32; ++kk) {
+        const uint4 u = qrow < s_end ? *reinterpret_cast<const uint4*>(qkv + (size_t)qrow * ld + q_col0 + h * D + kk * 32 + 8 * g)
+                                     : zero4;
+        qf[kk] = __builtin_bit_cast(ex8, u);
+    }
+    f32x4 o[D / 16];
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -1e30f, l = 0.f;   // running maximum (log2 units) of query c, and this lane's share of the denominator
+
+    const int q_last = min(q0 + 15, s_end - 1);
+    const int k_first = max(s0, q0 - w), k_last = min(s_end - 1, q_last + w);     // (w <= n_rows: no overflow)
+    const int k_lo = max(s0, q_ref - w), k_hi = min(s_end - 1, q_ref + w);        // this lane's query
+    const uint16_t* kbase = qkv + k_col0 + (size_t)h * D + 8 * g;
+    const uint16_t* vbase = vt + ((size_t)h * D + c) * 8;
+    for (int kb = k_first & ~7; kb <= k_last; kb += 32) {
+        f32x4 s[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            // A row c of tile tt is key kb + 8 (c >> 2) + 4 tt + (c & 3): result row 4 g + i is then key kb + 8 g + 4 tt + i
+            const int krow = kb + 8 * (c >> 2) + 4 * tt + (c & 3);
+            s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < D / 32; ++kk) {
+                const uint4 u = krow < n_rows ? *reinterpret_cast<const uint4*>(kbase + (size_t)krow * ld + kk * 32) : zero4;
+                s[tt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), qf[kk], s[tt]);
+            }
+        }
+        float x[8];
+        float bm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int key = kb + 8 * g + j;
+            const float v = s[j >> 2][j & 3] * scale_log2;
+            x[j] = (key >= k_lo && key <= k_hi) ? v : -INFINITY;
+            bm = fmaxf(bm, x[j]);
+        }
+        const float m_new = fmaxf(m, mb_wave_max16(bm));
+        const float alpha = exp2f(m - m_new);
+        m = m_new;
+        uint32_t pk[4];
+        float ps = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            pk[j >> 1] = pack_e2_inrange(exp2f(x[j] - m_new), exp2f(x[j + 1] - m_new));
+            ps += elo(pk[j >> 1]);
+            ps += ehi(pk[j >> 1]);
+        }
+        l = l * alpha + ps;
+        const ex8 pf = __builtin_bit_cast(ex8, uint4{pk[0], pk[1], pk[2], pk[3]});
+        // V^T fragment: feature 16 dt + c, keys kb + 8 g .. + 7 (one 8-row group of the V8 layout)
+        const int grp = (kb >> 3) + g;
+        const bool vok = 8 * grp < n_rows;
+#pragma unroll
+        for (int dt = 0; dt < D / 16; ++dt) {
+            const uint4 u = vok ? *reinterpret_cast<const uint4*>(vbase + (size_t)grp * ldvt + (size_t)dt * 16 * 8) : zero4;
+            o[dt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), pf, o[dt] * alpha);
+        }
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (qrow < s_end) {   // (the only lane-dependent branch: the wave is whole again for the next sequence's tile)
+        const float inv = 1.0f / l;
+        uint16_t* dst = out + (size_t)qrow * ld_out + h * D + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < D / 16; ++dt)
+            *reinterpret_cast<uint2*>(dst + dt * 16) = uint2{pack_e2(o[dt][0] * inv, o[dt][1] * inv),
+                                                             pack_e2(o[dt][2] * inv, o[dt][3] * inv)};
+    }
+}
+
+__global__ __launch_bounds__(64) void mb_attention_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
+                                                          const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
+                                                          int ld_out, const int32_t* __restrict__ seq_start,
+                                                          const int32_t* __restrict__ seq_len, int n_seq, int n_rows, int w,
+                                                          float scale_log2) {
+    const int t = blockIdx.x;
+    for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
+        mb_attention_tile(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, w, scale_log2, b, blockIdx.z, t);
+}
+
+// ---- classification head: pooling -> head.dense -> GELU -> head.norm -> classifier -> sigmoid, fp32 ---------------------------
+// One wave (one block) per sequence.  The pooled row (the first token's, or the mean over the sequence's tokens summed in ascending
+// order) goes to LDS; lane l owns the dense outputs l, l + 64, ... and walks the inputs in ascending order over the TRANSPOSED
+// matrix (coalesced rows), so a sequence's logit does not depend on the batch it travels in.
+__global__ __launch_bounds__(64) void mb_head_kernel(const uint16_t* __restrict__ hidden, int ld, const int32_t* __restrict__ seq_start,
+                                                     const int32_t* __restrict__ seq_len, int H, int pooling,
+                                                     const float* __restrict__ dense_wt, const float* __restrict__ norm_g,
+                                                     const float* __restrict__ cls_w, const float* __restrict__ cls_b, float eps,
+                                                     float* __restrict__ scores, float* __restrict__ logits) {
+    __shared__ float pooled[1024];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int s0 = seq_start[b];
+    const int n = pooling ? seq_len[b] : 1;
+    const bool ok = s0 >= 0 && n > 0;
+    // pooled row: lane owns the 8-element chunks lane, lane + 64 (H <= 1024)
+    float acc[2][8];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
+    if (ok) {
+        for (int r = 0; r < n; ++r) {
+            const uint4* src = reinterpret_cast<const uint4*>(hidden + (size_t)(s0 + r) * ld);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int ch = lane + 64 * j;
+                if (ch >= H / 8) continue;
+                const uint4 v = src[ch];
+                const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    acc[j][2 * k] += elo(u[k]);
+                    acc[j][2 * k + 1] += ehi(u[k]);
+                }
+            }
+        }
+    }
+    const float inv_n = ok ? 1.0f / (float)n : 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int ch = lane + 64 * j;
+        if (ch >= H / 8) continue;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pooled[8 * ch + k] = pooling ? acc[j][k] * inv_n : acc[j][k];
+    }
+    __syncthreads();
+    // dense (no bias): y[o] = sum_i pooled[i] * Wt[i][o], o = lane + 64 jj
+    float y[16];
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) y[jj] = 0.f;
+    const int no = H / 64;   // outputs per lane (H a multiple of 64)
+    for (int i = 0; i < H; ++i) {
+        const float p = pooled[i];
+        const float* wr = dense_wt + (size_t)i * H + lane;
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj)
+            if (jj < no) y[jj] += p * wr[64 * jj];
+    }
+    // GELU (libm erf: a few hundred rows per call), then LayerNorm (weight only) in two passes
+    float sum = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+        if (jj < no) {
+            y[jj] = 0.5f * y[jj] * (1.0f + erff(y[jj] * 0.70710678118654752f));
+            sum += y[jj];
+        }
+    }
+    const float mean = mb_wave_sum(sum) / (float)H;
+    float var = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+        if (jj < no) {
+            const float d = y[jj] - mean;
+            var += d * d;
+        }
+    }
+    const float rstd = rsqrtf(mb_wave_sum(var) / (float)H + eps);
+    float dot = 0.f;
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) {
+        if (jj < no) {
+            const int o = lane + 64 * jj;
+            dot += (y[jj] - mean) * rstd * norm_g[o] * cls_w[o];
+        }
+    }
+    dot = mb_wave_sum(dot) + cls_b[0];
+    if (lane == 0) {
+        scores[b] = 1.0f / (1.0f + expf(-dot));
+        if (logits) logits[b] = dot;
+    }
+}
+
+// ---- argument checks -----------------------------------------------------------------------------------------------------------
+int check_shape(int hidden, int heads, int ffn) {
+    if (hidden <= 0 || hidden % 128 || hidden > 1024) {
+        tt_set_error("modernbert: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", hidden);
+        return TT_E_UNSUPPORTED;
+    }
+    if (heads <= 0 || hidden != 64 * heads) {
+        tt_set_error("modernbert: hidden=%d heads=%d: head_dim must be 64", hidden, heads);
+        return TT_E_UNSUPPORTED;
+    }
+    if (ffn <= 0 || ffn % 64) {
+        tt_set_error("modernbert: ffn=%d must be a multiple of 64", ffn);
+        return TT_E_UNSUPPORTED;
+    }
+    return TT_OK;
+}
+
+int check_weights(const tt_modernbert_weights* w) {
+    TT_CHECK_ARG(w != nullptr, "null weights");
+    if (int rc = check_shape(w->hidden, w->heads, w->ffn)) return rc;
+    TT_CHECK_ARG(w->layers >= 0 && (w->layers == 0 || w->layer != nullptr), "layer array missing");
+    TT_CHECK_ARG(w->embed && w->emb_norm && w->final_norm && w->vocab > 0, "embedding table / embedding norm / final norm missing");
+    TT_CHECK_ARG(w->norm_eps > 0.f && w->global_rope_theta > 0.f && w->local_rope_theta > 0.f && w->local_attention >= 0,
+                 "norm_eps=%g global_rope_theta=%g local_rope_theta=%g local_attention=%d", w->norm_eps, w->global_rope_theta,
+                 w->local_rope_theta, w->local_attention);
+    return TT_OK;
+}
+
+struct MbWs {
+    size_t off_ha, off_hb, off_x, off_qkv, off_vt, off_ctx, off_gu, off_act, off_zero, zero_bytes, total;
+};
+
+MbWs mb_plan(const tt_modernbert_weights* w, int n_rows) {
+    MbWs e{};
+    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
+    WsPlanner ws;
+    e.off_ha = ws.take(T * H * 2);
+    e.off_hb = ws.take(T * H * 2);
+    e.off_x = ws.take(T * H * 2);
+    e.off_qkv = ws.take(T * 3 * H * 2);
+    e.off_vt = ws.take(T * H * 2);
+    e.off_ctx = ws.take(T * H * 2);
+    e.off_gu = ws.take(T * 2 * F * 2);
+    e.off_act = ws.take(T * F * 2);
+    e.zero_bytes = std::max(3 * H, 2 * F) * 4;   // the GEMMs' bias operand and the LayerNorms' beta: the model has neither
+    e.off_zero = ws.take(e.zero_bytes);
+    e.total = ws.off;
+    return e;
+}
+
+int layernorm_launch(const uint16_t* in, uint16_t* out, const float* g, const float* zero, int rows, int H, float eps, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    return tt_layernorm_launch(in, out, g, zero, rows, H, eps, st);
+}
+
+int rope_launch(uint16_t* qkv, int ld, const int32_t* pos, int rows, int heads, float theta, uint16_t* vt, int ldvt, hipStream_t st) {
+    MbRopeFreq freq;
+    for (int i = 0; i < 32; ++i) freq.inv[i] = (float)pow((double)theta, -(double)(2 * i) / 64.0);
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(mb_rope_kernel, dim3(rows), dim3(256), 0, st, qkv, ld, pos, heads, freq, vt, ldvt);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
+// window < 0: no window
+int window_attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, const uint16_t* vt, int ldvt, uint16_t* out, int ld_out,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int max_len, int window,
+                            hipStream_t st) {
+    const int n_qt = (max_len + 15) / 16;
+    const dim3 grid(n_qt, std::min(n_seq, 65535), heads);   // more sequences: each block row takes every 65535th
+    const float scale_log2 = 1.4426950408889634f / 8.0f;    // log2(e) / sqrt(64)
+    const int w = (window < 0 || window > n_rows) ? n_rows : window;   // |q - k| < n_rows within a batch
+    TtProfScope prof(TT_K_ATTENTION, st);
+    hipLaunchKernelGGL(mb_attention_kernel, grid, dim3(64), 0, st, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len,
+                       n_seq, n_rows, w, scale_log2);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
+int mb_run(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
+           int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
+    const MbWs e = mb_plan(w, n_rows);
+    char* ws = (char*)workspace;
+    const int H = w->hidden, F = w->ffn, nh = w->heads, T = n_rows;
+    uint16_t* ha = (uint16_t*)(ws + e.off_ha);
+    uint16_t* hb = (uint16_t*)(ws + e.off_hb);
+    uint16_t* x = (uint16_t*)(ws + e.off_x);
+    uint16_t* qkv = (uint16_t*)(ws + e.off_qkv);
+    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
+    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
+    uint16_t* gu = (uint16_t*)(ws + e.off_gu);
+    uint16_t* act = (uint16_t*)(ws + e.off_act);
+    const float* zero = (const float*)(ws + e.off_zero);
+    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
+    // rows that belong to no sequence are never written by the attention kernels: keep them finite (their V rows are masked keys)
+    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * H * 2, st));
+    {
+        TtProfScope prof(TT_K_ROWOPS, st);
+        hipLaunchKernelGGL(mb_embed_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, hb);
+        TT_CHECK_LAUNCH();
+    }
+    if (int rc = layernorm_launch(hb, ha, w->emb_norm, zero, T, H, w->norm_eps, st)) return rc;
+    for (int l = 0; l < w->layers; ++l) {
+        const tt_modernbert_layer_weights& lw = w->layer[l];
+        const uint16_t* xin = ha;
+        if (lw.attn_norm) {
+            if (int rc = layernorm_launch(ha, x, lw.attn_norm, zero, T, H, w->norm_eps, st)) return rc;
+            xin = x;
+        }
+        GemmParams g = gemm_16(xin, lw.qkv_w, zero, T, 3 * H, H);
+        g.C = qkv; g.ldc = 3 * H;
+        if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
+        if (int rc = rope_launch(qkv, 3 * H, pos, T, nh, lw.sliding ? w->local_rope_theta : w->global_rope_theta, vt, 8 * H, st)) return rc;
+        if (lw.sliding) {
+            if (int rc = window_attention_launch(qkv, 3 * H, 0, H, vt, 8 * H, ctx, H, seq_start, seq_len, n_seq, T, nh, max_len,
+                                                 w->local_attention / 2, st))
+                return rc;
+        } else {
+            // global layers: the encoder's bidirectional kernel (64-wide heads, the same Q / K rows and V8 layout)
+            AttnParams a{};
+            a.qk = qkv; a.ld_qk = 3 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = vt; a.ldvt = 8 * H;
+            a.out = ctx; a.ld_out = H; a.seq_start = seq_start; a.seq_len = seq_len;
+            a.n_seq = n_seq; a.heads = nh; a.head_dim = 64; a.max_len = max_len; a.total_rows = T;
+            a.scale = 0.125f;
+            if (int rc = tt_attention_launch(a, st)) return rc;
+        }
+        GemmParams go = gemm_16(ctx, lw.o_w, zero, T, H, H);
+        go.residual = ha; go.ldr = H; go.C = hb; go.ldc = H;
+        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
+        if (int rc = layernorm_launch(hb, x, lw.mlp_norm, zero, T, H, w->norm_eps, st)) return rc;
+        GemmParams g1 = gemm_16(x, lw.wi_w, zero, T, 2 * F, H);
+        g1.C = gu; g1.ldc = 2 * F;
+        if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
+        {
+            TtProfScope prof(TT_K_ROWOPS, st);
+            const int64_t chunks = (int64_t)T * (F / 8);
+            hipLaunchKernelGGL(mb_geglu_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, gu, act, chunks, F);
+            TT_CHECK_LAUNCH();
+        }
+        GemmParams g2 = gemm_16(act, lw.wo_w, zero, T, H, F);
+        g2.residual = hb; g2.ldr = H; g2.C = ha; g2.ldc = H;
+        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
+    }
+    return layernorm_launch(ha, (uint16_t*)hidden_out, w->final_norm, zero, T, H, w->norm_eps, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t tt_modernbert_workspace_bytes(const tt_modernbert_weights* w, int n_rows) {
+    if (!w || n_rows <= 0 || check_weights(w) != TT_OK) return 0;
+    return mb_plan(w, n_rows).total;
+}
+
+int tt_modernbert_forward(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                          const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_weights(w)) return rc;
+    TT_CHECK_ARG(type_ids == nullptr, "ModernBERT has no token types: type_ids must be NULL");
+    TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
+                 "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
+    TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
+    TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
+    if (int rc = tt_check_workspace("tt_modernbert_forward", workspace, workspace_bytes, mb_plan(w, n_rows).total)) return rc;
+    for (int l = 0; l < w->layers; ++l) {
+        const tt_modernbert_layer_weights& lw = w->layer[l];
+        TT_CHECK_ARG(lw.qkv_w && lw.o_w && lw.mlp_norm && lw.wi_w && lw.wo_w, "layer %d has a null weight pointer", l);
+    }
+    return mb_run(w, ids, pos, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+}
+
+int tt_modernbert_head(const tt_modernbert_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
+                       int n_seq, int pooling, float* scores, float* logits, void* stream) {
+    TT_CHECK_ARG(w != nullptr, "null weights");
+    if (int rc = check_shape(w->hidden, w->heads, w->ffn)) return rc;
+    TT_CHECK_ARG(n_seq > 0, "n_seq=%d", n_seq);
+    TT_CHECK_ARG(pooling == 0 || pooling == 1, "pooling=%d (0: first token, 1: mean)", pooling);
+    TT_CHECK_ARG(hidden && seq_start && scores && (pooling == 0 || seq_len), "null pointer");
+    TT_CHECK_ARG(w->head_dense_wt && w->head_norm && w->cls_w && w->cls_b, "these weights carry no classification head");
+    TT_CHECK_ARG(ld >= w->hidden && ld % 8 == 0 && ((uintptr_t)hidden % 16) == 0, "hidden=%d ld=%d (16-byte aligned rows)", w->hidden, ld);
+    TT_CHECK_ARG(w->norm_eps > 0.f, "norm_eps=%g", w->norm_eps);
+    hipStream_t st = (hipStream_t)stream;
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(mb_head_kernel, dim3(n_seq), dim3(64), 0, st, (const uint16_t*)hidden, ld, seq_start, seq_len, w->hidden, pooling,
+                       w->head_dense_wt, w->head_norm, w->cls_w, w->cls_b, w->norm_eps, scores, logits);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
+int tt_rope_v8(void* qkv, int ld, const int32_t* pos, int n_rows, int heads, int head_dim, float rope_theta, void* vt, int ldvt,
+               void* stream) {
+    if (head_dim != 64) {
+        tt_set_error("rope: head_dim=%d (supported: 64)", head_dim);
+        return TT_E_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(qkv && pos && vt, "null pointer");
+    TT_CHECK_ARG(heads > 0 && n_rows > 0 && n_rows % 8 == 0 && ld >= 3 * heads * 64 && ldvt >= 8 * heads * 64,
+                 "heads=%d n_rows=%d ld=%d ldvt=%d", heads, n_rows, ld, ldvt);
+    TT_CHECK_ARG(rope_theta > 0.f, "rope_theta=%g", rope_theta);
+    return rope_launch((uint16_t*)qkv, ld, pos, n_rows, heads, rope_theta, (uint16_t*)vt, ldvt, (hipStream_t)stream);
+}
+
+int tt_attention_window(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                        int max_len, int window, void* stream) {
+    if (head_dim != 64) {
+        tt_set_error("windowed attention: head_dim=%d (supported: 64)", head_dim);
+        return TT_E_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(qkv && vt && out && seq_start && seq_len, "null pointer");
+    TT_CHECK_ARG(heads > 0 && n_seq > 0 && max_len > 0 && n_rows > 0 && n_rows % 8 == 0 && max_len <= n_rows,
+                 "heads=%d n_seq=%d n_rows=%d max_len=%d", heads, n_seq, n_rows, max_len);
+    TT_CHECK_ARG(ld % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && q_col0 >= 0 && k_col0 >= 0 && ld_out % 4 == 0 &&
+                     ld >= std::max(q_col0, k_col0) + heads * 64 && ld_out >= heads * 64 && ldvt >= 8 * heads * 64 && ldvt % 8 == 0,
+                 "ld=%d q_col0=%d k_col0=%d ld_out=%d ldvt=%d", ld, q_col0, k_col0, ld_out, ldvt);
+    return window_attention_launch((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out, seq_start,
+                                   seq_len, n_seq, n_rows, heads, max_len, window, (hipStream_t)stream);
+}
+
+}  // extern "C"

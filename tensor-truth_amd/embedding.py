@@ -93,6 +93,14 @@ class HipHuggingFaceEmbedding:
         self.max_length = min(max_length or cfg.max_seq_len, cfg.max_seq_len)
         self.query_instruction = query_instruction_for(model_name) if query_instruction is None else query_instruction
         self.text_instruction = text_instruction or ""
+        if cfg.arch == "modernbert":
+            # sentence-transformers prompts (config_sentence_transformers.json), e.g. nomic's "search_query: " / "search_document: ":
+            # "query" for queries, "document" for texts, where the checkpoint names them
+            pr = _weights.prompts(mdir)
+            if query_instruction is None:
+                self.query_instruction = pr.get("query", "")
+            if text_instruction is None:
+                self.text_instruction = pr.get("document", "")
         if cfg.arch == "qwen3":
             # decoder embedders carry their instructions as sentence-transformers prompts (config_sentence_transformers.json):
             # "query" for queries, "document" for texts -- the prompt_name the reference's stack passes for each

@@ -35,7 +35,7 @@ from . import _lib
 class EncoderConfig:
     """The HF config fields the hot path reads."""
 
-    arch: str = "xlmr"  # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig)
+    arch: str = "xlmr"  # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig) | "modernbert" (modernbert.ModernBertConfig)
     vocab_size: int = 250002
     hidden: int = 1024
     layers: int = 24
@@ -128,6 +128,7 @@ class EncoderPath:
     rows_forward: Optional[str] = None    # decoder paths: the forward whose last layer runs for ONE row per sequence only
     rows_workspace: Optional[str] = None  # (``pooled_rows``), and its workspace size
     score: Optional[str] = None      # decoder paths: the *ForSequenceClassification score head over those rows
+    pooled_head: Optional[str] = None  # ModernBERT paths: pooling ("cls" / "mean") + classification head over the full forward
 
 
 BF16_PATH = EncoderPath(forward="tt_encoder_forward", workspace="tt_encoder_workspace_bytes",
@@ -152,6 +153,17 @@ DECODER_FP16_PATH = EncoderPath(forward="tt_decoder_forward_f16", workspace="tt_
                                 pool_last="tt_embed_pool_last_f16", rows_forward="tt_decoder_forward_rows_f16",
                                 rows_workspace="tt_decoder_rows_workspace_bytes_f16", score="tt_decoder_score_f16",
                                 no_fp8="the decoder embedder has no fp8 projections")
+# ModernBERT encoders (modernbert.ModernBertWeights): full forward; first-token and mean pooling with the encoder's kernels; the
+# classification head pools ("cls" / "mean", the checkpoint's ``classifier_pooling``) the full forward's rows itself.
+MODERNBERT_BF16_PATH = EncoderPath(forward="tt_modernbert_forward", workspace="tt_modernbert_workspace_bytes", cls_forward=None,
+                                   cls_workspace=None, pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None,
+                                   scratch="enc", head_scratch="head", hidden=torch.bfloat16, pooled_head="tt_modernbert_head",
+                                   no_fp8="the ModernBERT path has no fp8 projections")
+MODERNBERT_FP16_PATH = EncoderPath(forward="tt_modernbert_forward_f16", workspace="tt_modernbert_workspace_bytes_f16",
+                                   cls_forward=None, cls_workspace=None, pool="tt_embed_pool_f16",
+                                   pool_mean="tt_embed_pool_mean_f16", head=None, scratch="enc", head_scratch="head",
+                                   hidden=torch.float16, pool_writes_bf16=False, pooled_head="tt_modernbert_head_f16",
+                                   no_fp8="the ModernBERT path has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -821,6 +833,16 @@ class Encoder:
                 rc = getattr(self.lib, p.score)(hidden.data_ptr(), H, self.w.score_w.data_ptr(), B, H, scores.data_ptr(),
                                                 logits.data_ptr() if want_logits else None, torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(rc, p.score)
+            return (scores, logits) if want_logits else scores
+        if p.pooled_head is not None:
+            # ModernBERT cross-encoder: the head pools the full forward's rows as the checkpoint says and scores them
+            hidden, starts, lens = self.forward_packed(batch, want_lens=True)
+            with torch.cuda.device(dev):
+                rc = getattr(self.lib, p.pooled_head)(ctypes.byref(self.w.struct), hidden.data_ptr(), H, starts.data_ptr(),
+                                                      lens.data_ptr(), B, 1 if self.cfg.classifier_pooling == "mean" else 0,
+                                                      scores.data_ptr(), logits.data_ptr() if want_logits else None,
+                                                      torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(rc, p.pooled_head)
             return (scores, logits) if want_logits else scores
         hidden, cls_rows = self.cls_hidden_packed(batch)
         n_pad = (B + 127) // 128 * 128

@@ -123,6 +123,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
     mode = resolve(model_kwargs)
     if getattr(cfg, "arch", "") == "qwen3":
         return _build_decoder(cfg, state, device, mode, what)
+    if getattr(cfg, "arch", "") == "modernbert":
+        return _build_modernbert(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
     make, desc = _implementations()[impl]
     w = make(cfg, state, device)
@@ -155,4 +157,23 @@ def _build_decoder(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, 
     w = DecoderWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
     desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
     logger.info("%s: decoder embedder, precision = %s", what, desc)
+    return w, Encoder(w), desc
+
+
+def _build_modernbert(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """ModernBERT encoders: bf16 or fp16, resolved as for the decoder embedders.  The reference precision (fp32 semantics, what no
+    torch_dtype means for the XLM-R / BERT family) has no ModernBERT implementation: refused, never computed in another precision
+    behind the caller's back."""
+    import torch
+
+    from .encoder import Encoder
+    from .modernbert import ModernBertWeights
+
+    if mode not in ("bf16", "fp16"):
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for ModernBERT encoders; pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}} or {{'torch_dtype': 'float16'}}")
+    w = ModernBertWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
+    desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
+    logger.info("%s: ModernBERT encoder, precision = %s", what, desc)
     return w, Encoder(w), desc

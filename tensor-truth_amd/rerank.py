@@ -238,9 +238,10 @@ class HipSentenceTransformerRerank:
         """Would ids made by the tokenizer ``signature`` (with ``instruction`` prepended to the text) be THIS model's ids?"""
         from .tokenization import tokenizer_signature
 
-        if self.config.arch == "qwen3" or self.query_template is not None or self.document_template is not None:
+        if self.config.arch in ("qwen3", "modernbert") or self.query_template is not None or self.document_template is not None:
             # stored ids are laid out by tokenization.SpecialTokens, which knows the XLM-R and BERT pair layouts only: a decoder
-            # reranker's layout is its tokenizer's template (and a text template changes the passage's tokens): pairs come from text
+            # (or ModernBERT) reranker's layout is its tokenizer's template (and a text template changes the passage's tokens): pairs
+            # come from text
             return False
         return not self._use_types and not instruction and signature == tokenizer_signature(self._tokenizer)
 

@@ -250,8 +250,8 @@ class HFTokenizer:
 
     def encode_pair_batch(self, pairs: Sequence[Tuple[str, str]], max_length: int = 512):
         encs = self._batch(self._pairs(max_length), [(a, b) for a, b in pairs])
-        if self.arch in ("xlmr", "qwen3"):
-            # XLM-R (and a decoder reranker) has ONE token type (type_vocab 1): the segment ids are all zero and no caller reads them -- building 400 x 292
+        if self.arch in ("xlmr", "qwen3", "modernbert"):
+            # XLM-R (and a decoder or ModernBERT reranker) has ONE token type (type_vocab 1): the segment ids are all zero and no caller reads them -- building 400 x 292
             # more Python ints per rerank batch under the GIL is a third of this call
             return [(enc.ids, None) for enc in encs]
         return [(enc.ids, enc.type_ids) for enc in encs]

@@ -60,10 +60,59 @@ def _decoder_config_from_hf(d: dict) -> EncoderConfig:
         rope_theta=float(d.get("rope_theta") or (d.get("rope_parameters") or {}).get("rope_theta") or 10000.0))
 
 
+def _modernbert_config_from_hf(d: dict) -> EncoderConfig:
+    """``model_type == "modernbert"`` (gte-modernbert, nomic modernbert-embed, gte-reranker-modernbert, the answerdotai/ModernBERT
+    fine-tunes): every size from config.json.  ``layer_types`` is read; derived from ``global_attn_every_n_layers`` only where an
+    older export does not carry it, like the two RoPE bases (``rope_parameters``, else ``global_rope_theta`` /
+    ``local_rope_theta``).  A head exists iff ``architectures`` names a ``*ForSequenceClassification``."""
+    from .modernbert import ModernBertConfig, default_layer_types
+
+    layers = d["num_hidden_layers"]
+    layer_types = d.get("layer_types")
+    if not layer_types:
+        layer_types = default_layer_types(layers, int(d.get("global_attn_every_n_layers", 3)))
+    rp = d.get("rope_parameters") or {}
+    g, loc = rp.get("full_attention") or {}, rp.get("sliding_attention") or {}
+    rope_types = sorted({str(x.get("rope_type", x.get("type", "default"))) for x in (g, loc, d.get("rope_scaling") or {})})
+    glu = d.get("hidden_activation", "gelu")
+    cact = d.get("classifier_activation", "gelu")
+    # variants the ModernBERT kernels do not compute are refused by field name, never run as the plain model
+    bad = [f"{n}={v!r}" for n, v, ok in (
+        ("attention_bias", d.get("attention_bias", False), not d.get("attention_bias", False)),
+        ("mlp_bias", d.get("mlp_bias", False), not d.get("mlp_bias", False)),
+        ("norm_bias", d.get("norm_bias", False), not d.get("norm_bias", False)),
+        ("classifier_bias", d.get("classifier_bias", False), not d.get("classifier_bias", False)),
+        ("rope_type", rope_types, rope_types == ["default"]),
+        ("hidden_activation", glu, glu == "gelu"),
+        ("classifier_activation", cact, cact == "gelu")) if not ok]
+    if bad:
+        raise NotImplementedError(f"modernbert checkpoint with {', '.join(bad)}: the ModernBERT path computes bias-free layers "
+                                  "with default RoPE and exact-erf GELU only")
+    num_labels = 0
+    if "ForSequenceClassification" in " ".join(d.get("architectures") or []):
+        n = d.get("num_labels") or (len(d["id2label"]) if d.get("id2label") else 1)
+        if n != 1:
+            raise NotImplementedError(f"modernbert classification checkpoint with num_labels={n}: only single-label (sigmoid) "
+                                      "cross-encoder heads are supported")
+        num_labels = 1
+    pad = d.get("pad_token_id")
+    vocab = d["vocab_size"]
+    return ModernBertConfig(
+        arch="modernbert", vocab_size=vocab, hidden=d["hidden_size"], layers=layers, heads=d["num_attention_heads"],
+        ffn=d["intermediate_size"], max_pos=d["max_position_embeddings"], type_vocab=1,
+        pad_id=int(pad) if pad is not None and 0 <= int(pad) < vocab else 0, ln_eps=d.get("norm_eps", 1e-5), num_labels=num_labels,
+        layer_types=tuple(layer_types),
+        global_rope_theta=float(g.get("rope_theta") or d.get("global_rope_theta") or 160000.0),
+        local_rope_theta=float(loc.get("rope_theta") or d.get("local_rope_theta") or d.get("global_rope_theta") or 10000.0),
+        local_attention=int(d.get("local_attention", 128)), classifier_pooling=str(d.get("classifier_pooling", "cls")))
+
+
 def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
     mt = d.get("model_type", "xlm-roberta")
     if mt == "qwen3":
         return _decoder_config_from_hf(d)
+    if mt == "modernbert":
+        return _modernbert_config_from_hf(d)
     arch = "bert" if mt == "bert" else "xlmr"
     archs = " ".join(d.get("architectures", []))
     num_labels = 1 if "SequenceClassification" in archs else num_labels_default
@@ -191,6 +240,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .decoder import synthetic_state as decoder_state
 
             return cfg, decoder_state(cfg, seed), None
+        if cfg.arch == "modernbert":
+            from .modernbert import synthetic_state as modernbert_state
+
+            return cfg, modernbert_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
