@@ -6,45 +6,20 @@
 //   x    = RMSNorm(h) * g_attn                           [T][H]
 //   qkv  = GEMM(x, Wqkv)                                 [T][(nq + 2 nkv) D]  q_proj | k_proj | v_proj
 //   qkv  = RoPE(RMSNorm_head(q) * g_q), RoPE(RMSNorm_head(k) * g_k)   in place; V copied to the V8 layout vt
-//   ctx  = causal GQA attention(qkv, vt)                 [T][nq D]
+//   ctx  = causal GQA attention(qkv, vt)                 [T][nq D]   the shared tile (varlen.h attention_tile) with the causal mask
 //   h1   = GEMM(ctx, Wo) + h                             residual fused in the epilogue
 //   x    = RMSNorm(h1) * g_ffn
 //   gu   = GEMM(x, [Wgate; Wup])                         [T][2F]
 //   a    = SiLU(gu[:, :F]) * gu[:, F:]                   [T][F]
 //   h    = GEMM(a, Wdown) + h1
 // and after the last layer  out = RMSNorm(h) * g_final.  Every row op reads one token row only, so a token's result does not
-// depend on how the batch is packed; the attention mixes the rows of one sequence only.
+// depend on how the batch is packed; the attention mixes the rows of one sequence only.  The attention tile, the embedding gather,
+// the gated-activation kernel, the workspace plan and the batch-argument checks are the ones ModernBERT uses too (varlen.h).
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "common.h"
-#include "encoder.h"
-
-#include <algorithm>
+#include "varlen.h"
 
 namespace {
-
-__device__ __forceinline__ float dec_wave_sum(float v) {
-    // butterfly: every lane ends with the same bits (a + b == b + a)
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float dec_wave_max16(float v) {
-    // maximum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (one query column of an MFMA 16x16 result)
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-
-// ---- embedding gather: out[r] = table[ids[r]] (an id outside [0, vocab) gives a zero row) ------------------------------------
-__global__ __launch_bounds__(256) void dec_embed_kernel(const int32_t* __restrict__ ids, const uint16_t* __restrict__ table,
-                                                        int vocab, int H, uint16_t* __restrict__ out) {
-    const int row = blockIdx.x;
-    const int id = ids[row];
-    const bool ok = id >= 0 && id < vocab;
-    const uint4* src = reinterpret_cast<const uint4*>(table + (size_t)(ok ? id : 0) * H);
-    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)row * H);
-    for (int c = threadIdx.x; c < H / 8; c += blockDim.x) dst[c] = ok ? src[c] : uint4{0u, 0u, 0u, 0u};
-}
 
 // ---- RMSNorm over rows of H <= 1024 elements: one wave per row, four rows per block ---------------------------------------------
 __global__ __launch_bounds__(256) void dec_rmsnorm_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
@@ -69,7 +44,7 @@ __global__ __launch_bounds__(256) void dec_rmsnorm_kernel(const uint16_t* __rest
             ss += b * b;
         }
     }
-    const float r = rsqrtf(dec_wave_sum(ss) / (float)H + eps);
+    const float r = rsqrtf(wave_sum(ss) / (float)H + eps);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = lane + 64 * j;
@@ -116,7 +91,7 @@ __global__ __launch_bounds__(256) void dec_qknorm_rope_kernel(uint16_t* __restri
             a = ebits_to_f32(x[lane]);
             b = ebits_to_f32(x[lane + half]);
         }
-        const float rs = rsqrtf(dec_wave_sum(a * a + b * b) / (float)D + eps);
+        const float rs = rsqrtf(wave_sum(a * a + b * b) / (float)D + eps);
         if (lane < half) {
             const float xa = a * rs * g[lane], xb = b * rs * g[lane + half];
             x[lane] = f32_to_ebits(xa * c - xb * s);
@@ -125,23 +100,10 @@ __global__ __launch_bounds__(256) void dec_qknorm_rope_kernel(uint16_t* __restri
     }
 }
 
-// ---- SiLU(gate) * up: gu [T][2F] (gate columns, then up columns) -> out [T][F] --------------------------------------------------
-__global__ __launch_bounds__(256) void dec_swiglu_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
-                                                         int F) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_chunks) return;
-    const int64_t row = i / (F / 8), c = i % (F / 8);
-    const uint4 gv = reinterpret_cast<const uint4*>(gu + row * 2 * F)[c];
-    const uint4 uv = reinterpret_cast<const uint4*>(gu + row * 2 * F + F)[c];
-    const uint32_t g4[4] = {gv.x, gv.y, gv.z, gv.w}, u4[4] = {uv.x, uv.y, uv.z, uv.w};
-    uint32_t o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float g0 = elo(g4[k]), g1 = ehi(g4[k]);
-        o[k] = pack_e2(g0 / (1.0f + expf(-g0)) * elo(u4[k]), g1 / (1.0f + expf(-g1)) * ehi(u4[k]));
-    }
-    reinterpret_cast<uint4*>(out + row * F)[c] = uint4{o[0], o[1], o[2], o[3]};
-}
+// ---- SiLU(gate) * up through varlen.h's gated_act_kernel: gu [T][2F] (gate columns, then up columns) -> out [T][F] ------------
+struct Silu {
+    static __device__ __forceinline__ float f(float x) { return x / (1.0f + expf(-x)); }
+};
 
 // ---- last-token pooling + L2 norm: out[b] = h[r] / max(||h[r]||, 1e-12), r = seq_start[b] + seq_len[b] - 1; one wave per sequence
 __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __restrict__ hidden, int ld, const int32_t* __restrict__ seq_start,
@@ -167,7 +129,7 @@ __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __re
             ss += bb * bb;
         }
     }
-    const float inv = 1.0f / fmaxf(sqrtf(dec_wave_sum(ss)), 1e-12f);
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = lane + 64 * j;
@@ -188,107 +150,7 @@ __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __re
     }
 }
 
-// ---- causal GQA attention over packed varlen sequences ---------------------------------------------------------------------------
-// One wave per (16-query tile, sequence, query head); query head h reads KV head h / group.  Keys are visited in blocks of 32 on
-// the absolute 8-row grid from the sequence's first 8-row group up to the tile's last query; a key k is live for query q iff
-// seq_start <= k <= q (the mask also removes the neighbouring sequences' rows of shared 8-row groups).
-//   S^T = K Q^T  (mfma 16x16x32, two tiles per key block).  The K rows each lane loads are permuted so that, for query c = lane & 15,
-//                lane l ends up holding the scores of keys kb + 8 (l >> 4) + j, j = 0..7 -- exactly the B operand of
-//   O^T += V^T P^T  (mfma 16x16x32 per 16 features), whose A operand is one 16-byte read of the V8 layout per lane.
-// Softmax in fp32 with a running maximum (log2 domain), P rounded to the element type for the product; the denominator sums the
-// rounded P, so the weights of a row sum to one as they are applied.
-// One (tile t, sequence b, head h) per call; the kernel below walks the sequences (a grid's y extent stops at 65535).
-// keep_row < 0: every query of the tile is stored, at its own row of `out`.  keep_row >= 0 (the pooled-row tail): only the query
-// at absolute row keep_row is stored, at row out_row of `out` -- the same arithmetic, so the same bits as the full tile gives it.
-template <int D>
-__device__ __forceinline__ void dec_attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
-                                                   const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out, int ld_out,
-                                                   const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len,
-                                                   int n_rows, int group, float scale_log2, int b, int h, int t, int keep_row = -1,
-                                                   int out_row = 0) {
-    const int s0 = seq_start[b], L = seq_len[b];
-    if (s0 < 0 || 16 * t >= L) return;
-    const int s_end = min(s0 + L, n_rows);
-    const int q0 = s0 + 16 * t;
-    if (q0 >= s_end) return;
-    const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
-    const int kvh = h / group;
-    const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
-
-    // Q fragment, the B operand of S^T: lane holds Q[q0 + c][32 kk + 8 g + j]
-    ex8 qf[D / 32];
-    const int qrow = q0 + c;
-    const int q_lim = min(qrow, s_end - 1);      // rows past the sequence: computed against its keys, never stored
-#pragma unroll
-    for (int kk = 0; kk < D / 32; ++kk) {
-        const uint4 u = qrow < s_end ? *reinterpret_cast<const uint4*>(qkv + (size_t)qrow * ld + q_col0 + h * D + kk * 32 + 8 * g)
-                                     : zero4;
-        qf[kk] = __builtin_bit_cast(ex8, u);
-    }
-    f32x4 o[D / 16];
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -1e30f, l = 0.f;   // running maximum (log2 units) of query c, and this lane's share of the denominator
-
-    const int q_last = min(q0 + 15, s_end - 1);
-    const uint16_t* kbase = qkv + k_col0 + (size_t)kvh * D + 8 * g;
-    const uint16_t* vbase = vt + ((size_t)kvh * D + c) * 8;
-    for (int kb = s0 & ~7; kb <= q_last; kb += 32) {
-        f32x4 s[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            // A row c of tile tt is key kb + 8 (c >> 2) + 4 tt + (c & 3): result row 4 g + i is then key kb + 8 g + 4 tt + i
-            const int krow = kb + 8 * (c >> 2) + 4 * tt + (c & 3);
-            s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < D / 32; ++kk) {
-                const uint4 u = krow < n_rows ? *reinterpret_cast<const uint4*>(kbase + (size_t)krow * ld + kk * 32) : zero4;
-                s[tt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), qf[kk], s[tt]);
-            }
-        }
-        float x[8];
-        float bm = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = kb + 8 * g + j;
-            const float v = s[j >> 2][j & 3] * scale_log2;
-            x[j] = (key >= s0 && key <= q_lim) ? v : -INFINITY;
-            bm = fmaxf(bm, x[j]);
-        }
-        const float m_new = fmaxf(m, dec_wave_max16(bm));
-        const float alpha = exp2f(m - m_new);
-        m = m_new;
-        uint32_t pk[4];
-        float ps = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            pk[j >> 1] = pack_e2_inrange(exp2f(x[j] - m_new), exp2f(x[j + 1] - m_new));
-            ps += elo(pk[j >> 1]);
-            ps += ehi(pk[j >> 1]);
-        }
-        l = l * alpha + ps;
-        const ex8 pf = __builtin_bit_cast(ex8, uint4{pk[0], pk[1], pk[2], pk[3]});
-        // V^T fragment: feature 16 dt + c, keys kb + 8 g .. + 7 (one 8-row group of the V8 layout)
-        const int grp = (kb >> 3) + g;
-        const bool vok = 8 * grp < n_rows;
-#pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt) {
-            const uint4 u = vok ? *reinterpret_cast<const uint4*>(vbase + (size_t)grp * ldvt + (size_t)dt * 16 * 8) : zero4;
-            o[dt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), pf, o[dt] * alpha);
-        }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    if (qrow < s_end && (keep_row < 0 || qrow == keep_row)) {   // (the only lane-dependent branch: the wave is whole again for the next sequence's tile)
-        const float inv = 1.0f / l;
-        uint16_t* dst = out + (size_t)(keep_row < 0 ? qrow : out_row) * ld_out + h * D + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt)
-            *reinterpret_cast<uint2*>(dst + dt * 16) = uint2{pack_e2(o[dt][0] * inv, o[dt][1] * inv),
-                                                             pack_e2(o[dt][2] * inv, o[dt][3] * inv)};
-    }
-}
-
+// ---- causal GQA attention over packed varlen sequences: one wave per (16-query tile, sequence, query head) on varlen.h's tile ------
 template <int D>
 __global__ __launch_bounds__(64) void dec_attention_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
                                                            const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
@@ -297,8 +159,8 @@ __global__ __launch_bounds__(64) void dec_attention_kernel(const uint16_t* __res
                                                            int n_qt, float scale_log2) {
     const int t = n_qt - 1 - (int)blockIdx.x;   // the longest tiles (most keys) first
     for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
-        dec_attention_tile<D>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, scale_log2, b,
-                              blockIdx.z, t);
+        attention_tile<D, false>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, 0, scale_log2, b,
+                                 blockIdx.z, t);
 }
 
 // The pooled-row tail: per (sequence b, query head) only the 16-query tile that holds pool_row[b], and of it only that query,
@@ -313,8 +175,8 @@ __global__ __launch_bounds__(64) void dec_attention_rows_kernel(const uint16_t* 
     for (int b = blockIdx.x; b < n_seq; b += gridDim.x) {   // (wave-uniform)
         const int r = pool_row[b], s0 = seq_start[b], L = seq_len[b];
         if (s0 < 0 || r < s0 || r - s0 >= L || r >= n_rows) continue;
-        dec_attention_tile<D>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, scale_log2, b,
-                              blockIdx.y, (r - s0) >> 4, r, b);
+        attention_tile<D, false>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, 0, scale_log2, b,
+                                 blockIdx.y, (r - s0) >> 4, r, b);
     }
 }
 
@@ -353,7 +215,7 @@ __global__ __launch_bounds__(256) void dec_score_kernel(const uint16_t* __restri
         acc += elo(u[3]) * w1.z;
         acc += ehi(u[3]) * w1.w;
     }
-    acc = dec_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) {
         scores[b] = 1.0f / (1.0f + expf(-acc));
         if (logits) logits[b] = acc;
@@ -361,13 +223,18 @@ __global__ __launch_bounds__(256) void dec_score_kernel(const uint16_t* __restri
 }
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
-int check_shape(int hidden, int heads, int kv_heads, int head_dim) {
+int check_heads(int heads, int kv_heads, int head_dim) {
     if (head_dim != 64 && head_dim != 128) {
         tt_set_error("decoder: head_dim=%d not in {64, 128}", head_dim);
         return TT_E_UNSUPPORTED;
     }
     TT_CHECK_ARG(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "decoder: heads=%d is not a multiple of kv_heads=%d", heads,
                  kv_heads);
+    return TT_OK;
+}
+
+int check_shape(int hidden, int heads, int kv_heads, int head_dim) {
+    if (int rc = check_heads(heads, kv_heads, head_dim)) return rc;
     if (hidden <= 0 || hidden % 128 || hidden > 1024) {
         tt_set_error("decoder: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", hidden);
         return TT_E_UNSUPPORTED;
@@ -389,26 +256,11 @@ int check_weights(const tt_decoder_weights* w) {
     return TT_OK;
 }
 
-struct DecWs {
-    size_t off_ha, off_hb, off_x, off_qkv, off_vt, off_ctx, off_gu, off_act, off_zero, total;
-};
-
-DecWs dec_plan(const tt_decoder_weights* w, int n_rows) {
-    DecWs e{};
-    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, D = (size_t)w->head_dim, T = ((size_t)n_rows + 255) / 256 * 256;
+VarlenWs dec_plan(const tt_decoder_weights* w, int n_rows) {
+    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, D = (size_t)w->head_dim;
     const size_t nqkv = (size_t)(w->heads + 2 * w->kv_heads) * D;
-    WsPlanner ws;
-    e.off_ha = ws.take(T * H * 2);
-    e.off_hb = ws.take(T * H * 2);
-    e.off_x = ws.take(T * H * 2);
-    e.off_qkv = ws.take(T * nqkv * 2);
-    e.off_vt = ws.take(T * w->kv_heads * D * 2);
-    e.off_ctx = ws.take(T * w->heads * D * 2);
-    e.off_gu = ws.take(T * 2 * F * 2);
-    e.off_act = ws.take(T * F * 2);
-    e.off_zero = ws.take(std::max(nqkv, std::max(2 * F, H)) * 4);   // the GEMMs' bias operand: the model has none
-    e.total = ws.off;
-    return e;
+    // zeros: the GEMMs' bias operand (the model has none)
+    return varlen_plan(n_rows, H, nqkv, w->kv_heads * D, w->heads * D, F, std::max(nqkv, std::max(2 * F, H)));
 }
 
 int rmsnorm_launch(const uint16_t* in, uint16_t* out, const float* g, int rows, int H, float eps, hipStream_t st) {
@@ -467,7 +319,7 @@ int rows_pad(int n_seq) { return pooled_rows_pad(n_seq, tt_gemm_skinny_enabled()
 // out [rows_pad(n_seq)][H]).  Arguments are checked by the callers.
 int dec_run(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
             const int32_t* pool_row, int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const DecWs e = dec_plan(w, n_rows);
+    const VarlenWs e = dec_plan(w, n_rows);
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, D = w->head_dim, nq = w->heads, nkv = w->kv_heads, T = n_rows;
     const int nqkv = (nq + 2 * nkv) * D;
@@ -480,35 +332,27 @@ int dec_run(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos,
     uint16_t* gu = (uint16_t*)(ws + e.off_gu);
     uint16_t* act = (uint16_t*)(ws + e.off_act);
     const float* zero = (const float*)(ws + e.off_zero);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, (size_t)std::max(nqkv, std::max(2 * F, H)) * 4, st));
+    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
     // rows that belong to no sequence are never written by the attention kernel: keep them finite (their V rows are masked keys)
     TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * nq * D * 2, st));
     {
         TtProfScope prof(TT_K_ROWOPS, st);
-        hipLaunchKernelGGL(dec_embed_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, ha);
+        hipLaunchKernelGGL(embed_gather_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, ha);
         TT_CHECK_LAUNCH();
     }
     // the rows of one layer's second half: M rows of residual `res` and context `c`, through h1 (and x, gu, act) into `out`
     auto block_tail = [&](const tt_decoder_layer_weights& lw, int M, const uint16_t* c, const uint16_t* res, uint16_t* h1, uint16_t* xn,
                           uint16_t* out) -> int {
-        GemmParams go{};
-        go.A = c; go.lda = nq * D; go.W = (const uint16_t*)lw.o_w; go.bias = zero;
-        go.residual = res; go.ldr = H; go.C = h1; go.ldc = H; go.M = M; go.N = H; go.K = nq * D;
+        GemmParams go = gemm_16(c, lw.o_w, zero, M, H, nq * D);
+        go.residual = res; go.ldr = H; go.C = h1; go.ldc = H;
         if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
         if (int rc = rmsnorm_launch(h1, xn, lw.ffn_norm, M, H, w->rms_eps, st)) return rc;
-        GemmParams g1{};
-        g1.A = xn; g1.lda = H; g1.W = (const uint16_t*)lw.gate_up_w; g1.bias = zero;
-        g1.C = gu; g1.ldc = 2 * F; g1.M = M; g1.N = 2 * F; g1.K = H;
+        GemmParams g1 = gemm_16(xn, lw.gate_up_w, zero, M, 2 * F, H);
+        g1.C = gu; g1.ldc = 2 * F;
         if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            const int64_t chunks = (int64_t)M * (F / 8);
-            hipLaunchKernelGGL(dec_swiglu_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, gu, act, chunks, F);
-            TT_CHECK_LAUNCH();
-        }
-        GemmParams g2{};
-        g2.A = act; g2.lda = F; g2.W = (const uint16_t*)lw.down_w; g2.bias = zero;
-        g2.residual = h1; g2.ldr = H; g2.C = out; g2.ldc = H; g2.M = M; g2.N = H; g2.K = F;
+        if (int rc = gated_act_launch<Silu>(gu, act, M, F, st)) return rc;
+        GemmParams g2 = gemm_16(act, lw.down_w, zero, M, H, F);
+        g2.residual = h1; g2.ldr = H; g2.C = out; g2.ldc = H;
         return tt_gemm_launch(g2, TT_EPI_RESIDUAL, st);
     };
     auto gather = [&](uint16_t* dst, int M) -> int {
@@ -520,9 +364,8 @@ int dec_run(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos,
     for (int l = 0; l < w->layers; ++l) {
         const tt_decoder_layer_weights& lw = w->layer[l];
         if (int rc = rmsnorm_launch(ha, x, lw.attn_norm, T, H, w->rms_eps, st)) return rc;
-        GemmParams g{};
-        g.A = x; g.lda = H; g.W = (const uint16_t*)lw.qkv_w; g.bias = zero;
-        g.C = qkv; g.ldc = nqkv; g.M = T; g.N = nqkv; g.K = H;
+        GemmParams g = gemm_16(x, lw.qkv_w, zero, T, nqkv, H);
+        g.C = qkv; g.ldc = nqkv;
         if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
         if (int rc = qknorm_rope_launch(qkv, nqkv, pos, lw.q_norm, lw.k_norm, T, nq, nkv, D, w->rms_eps, w->rope_theta, vt, 8 * nkv * D,
                                         st))
@@ -557,12 +400,9 @@ int check_forward_args(const char* what, const tt_decoder_weights* w, const int3
                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, const void* hidden_out,
                        const void* workspace, size_t workspace_bytes) {
     if (int rc = check_weights(w)) return rc;
-    TT_CHECK_ARG(type_ids == nullptr, "a decoder has no token types: type_ids must be NULL");
-    TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
-                 "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
-    TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
-    TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
-    if (int rc = tt_check_workspace(what, workspace, workspace_bytes, dec_plan(w, n_rows).total)) return rc;
+    if (int rc = check_packed_forward_args(what, "a decoder", ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out,
+                                           workspace, workspace_bytes, dec_plan(w, n_rows).total))
+        return rc;
     for (int l = 0; l < w->layers; ++l) {
         const tt_decoder_layer_weights& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.q_norm && lw.k_norm && lw.o_w && lw.attn_norm && lw.ffn_norm && lw.gate_up_w && lw.down_w,
@@ -638,7 +478,7 @@ int tt_embed_pool_last(const void* hidden, int ld, const int32_t* seq_start, con
 int tt_attention_causal_gqa(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
                             const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads,
                             int head_dim, int max_len, void* stream) {
-    if (int rc = check_shape(1024, heads, kv_heads, head_dim)) return rc;
+    if (int rc = check_heads(heads, kv_heads, head_dim)) return rc;
     TT_CHECK_ARG(qkv && vt && out && seq_start && seq_len, "null pointer");
     TT_CHECK_ARG(n_seq > 0 && max_len > 0 && n_rows > 0 && n_rows % 8 == 0 && max_len <= n_rows,
                  "n_seq=%d n_rows=%d max_len=%d", n_seq, n_rows, max_len);
@@ -650,7 +490,7 @@ int tt_attention_causal_gqa(const void* qkv, int ld, int q_col0, int k_col0, con
 
 int tt_qk_norm_rope(void* qkv, int ld, const int32_t* pos, const float* q_norm, const float* k_norm, int n_rows, int heads,
                     int kv_heads, int head_dim, float eps, float rope_theta, void* vt, int ldvt, void* stream) {
-    if (int rc = check_shape(1024, heads, kv_heads, head_dim)) return rc;
+    if (int rc = check_heads(heads, kv_heads, head_dim)) return rc;
     TT_CHECK_ARG(qkv && pos && q_norm && k_norm && vt, "null pointer");
     TT_CHECK_ARG(n_rows > 0 && n_rows % 8 == 0 && ld >= (heads + 2 * kv_heads) * head_dim && ldvt >= 8 * kv_heads * head_dim,
                  "n_rows=%d ld=%d ldvt=%d", n_rows, ld, ldvt);

@@ -8,6 +8,7 @@
 //   qkv  = GEMM(x, Wqkv)                                 [T][3H]  Q | K | V, heads of 64
 //   qkv  = RoPE(q), RoPE(k) with the layer's base        in place; V copied to the V8 layout vt
 //   ctx  = attention(qkv, vt)                            [T][H]   bidirectional; a sliding layer keeps |q - k| <= local_attention / 2
+//                                                                 (the shared tile, varlen.h attention_tile, with the window mask)
 //   h1   = GEMM(ctx, Wo) + h                             residual fused in the epilogue
 //   x    = LayerNorm(h1) * g_mlp
 //   gu   = GEMM(x, Wi)                                   [T][2F]  "input" columns, then "gate" columns
@@ -15,28 +16,15 @@
 //   h    = GEMM(a, Wo_mlp) + h1
 // with h = LayerNorm(tok_embeddings[ids]) * g_emb before the first layer and out = LayerNorm(h) * g_final after the last.  Every
 // row op reads one token row only, so a token's result does not depend on how the batch is packed; the attention mixes the rows of
-// one sequence only.
+// one sequence only.  The attention tile, the embedding gather, the gated-activation kernel, the workspace plan and the
+// batch-argument checks are the ones the decoder path uses too (varlen.h).
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "common.h"
-#include "encoder.h"
+#include "varlen.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace {
-
-__device__ __forceinline__ float mb_wave_sum(float v) {
-    // butterfly: every lane ends with the same bits (a + b == b + a)
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float mb_wave_max16(float v) {
-    // maximum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (one query column of an MFMA 16x16 result)
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
 
 // GELU(x) = 0.5 x (1 + erf(x / sqrt 2)), the exact-erf form of the encoder's GEMM epilogue (gemm.hip gelu_erf2, one value at a
 // time): gelu(x) = max(x, 0) - |x| 2^Q(|x|), Q the degree-7 fit of log2 Phi(-u) on [0, 9]; abs error <= 1e-5.
@@ -51,17 +39,10 @@ __device__ __forceinline__ float mb_gelu_erf(float x) {
     q = q * u + -1.000091195e+00f;
     return fmaxf(x, 0.f) - u * __builtin_amdgcn_exp2f(q);
 }
-
-// ---- embedding gather: out[r] = table[ids[r]] (an id outside [0, vocab) gives a zero row) ------------------------------------
-__global__ __launch_bounds__(128) void mb_embed_kernel(const int32_t* __restrict__ ids, const uint16_t* __restrict__ table, int vocab,
-                                                       int H, uint16_t* __restrict__ out) {
-    const int row = blockIdx.x;
-    const int id = ids[row];
-    const bool ok = id >= 0 && id < vocab;
-    const uint4* src = reinterpret_cast<const uint4*>(table + (size_t)(ok ? id : 0) * H);
-    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)row * H);
-    for (int c = threadIdx.x; c < H / 8; c += blockDim.x) dst[c] = ok ? src[c] : uint4{0u, 0u, 0u, 0u};
-}
+// GELU_erf(input) * gate through varlen.h's gated_act_kernel: gu [T][2F] (input columns, then gate columns) -> out [T][F]
+struct GeluErf {
+    static __device__ __forceinline__ float f(float x) { return mb_gelu_erf(x); }
+};
 
 // ---- rotate-half RoPE of the q and k heads with base theta, in place; V heads copied to the V8 layout ------------------------
 // One block per token row, one wave per head at a time; heads of 64: lane i < 32 holds the pair (i, i + 32).
@@ -97,122 +78,8 @@ __global__ __launch_bounds__(256) void mb_rope_kernel(uint16_t* __restrict__ qkv
     }
 }
 
-// ---- GELU_erf(input) * gate: gu [T][2F] (input columns, then gate columns) -> out [T][F] -------------------------------------
-__global__ __launch_bounds__(256) void mb_geglu_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
-                                                       int F) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_chunks) return;
-    const int64_t row = i / (F / 8), c = i % (F / 8);
-    const uint4 iv = reinterpret_cast<const uint4*>(gu + row * 2 * F)[c];
-    const uint4 gv = reinterpret_cast<const uint4*>(gu + row * 2 * F + F)[c];
-    const uint32_t i4[4] = {iv.x, iv.y, iv.z, iv.w}, g4[4] = {gv.x, gv.y, gv.z, gv.w};
-    uint32_t o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = pack_e2(mb_gelu_erf(elo(i4[k])) * elo(g4[k]), mb_gelu_erf(ehi(i4[k])) * ehi(g4[k]));
-    reinterpret_cast<uint4*>(out + row * F)[c] = uint4{o[0], o[1], o[2], o[3]};
-}
-
 // ---- bidirectional attention with a sliding window over packed varlen sequences, head_dim 64 ---------------------------------
-// One wave per (16-query tile, sequence, head), on the decoder's tile routine (decoder.hip dec_attention_tile) with another key
-// range and mask.  Tile q0 .. q0 + 15 of a sequence s0 .. s_end - 1 visits the key blocks of 32, on the absolute 8-row grid, that
-// intersect [max(s0, q0 - w), min(s_end - 1, q0 + 15 + w)]; key k is live for query q iff s0 <= k < s_end && |q - k| <= w (the mask
-// also removes the neighbouring sequences' rows of shared 8-row groups).  w >= the batch's longest sequence: every key of the
-// sequence, the walk and the bits of a layer without a window.
-//   S^T = K Q^T  (mfma 16x16x32, two tiles per key block).  The K rows each lane loads are permuted so that, for query c = lane & 15,
-//                lane l ends up holding the scores of keys kb + 8 (l >> 4) + j, j = 0..7 -- exactly the B operand of
-//   O^T += V^T P^T  (mfma 16x16x32 per 16 features), whose A operand is one 16-byte read of the V8 layout per lane.
-// Softmax in fp32 with a running maximum (log2 domain), P rounded to the element type for the product; the denominator sums the
-// rounded P, so the weights of a row sum to one as they are applied.  A block may hold no live key for some query of the tile (the
-// window's edge): its P is zero and its running maximum stays where it was (-1e30 before the query's first live key).
-__device__ __forceinline__ void mb_attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
-                                                  const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out, int ld_out,
-                                                  const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len,
-                                                  int n_rows, int w, float scale_log2, int b, int h, int t) {
-    constexpr int D = 64;
-    const int s0 = seq_start[b], L = seq_len[b];
-    if (s0 < 0 || 16 * t >= L) return;
-    const int s_end = min(s0 + L, n_rows);
-    const int q0 = s0 + 16 * t;
-    if (q0 >= s_end) return;
-    const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
-    const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
-
-    // Q fragment, the B operand of S^T: lane holds Q[q0 + c][32 kk + 8 g + j]
-    ex8 qf[D / 32];
-    const int qrow = q0 + c;
-    const int q_ref = min(qrow, s_end - 1);      // rows past the sequence: computed against its keys, never stored
-#pragma unroll
-    for (int kk = 0; kk < D / 32; ++kk) {
-        const uint4 u = qrow < s_end ? *reinterpret_cast<const uint4*>(qkv + (size_t)qrow * ld + q_col0 + h * D + kk * 32 + 8 * g)
-                                     : zero4;
-        qf[kk] = __builtin_bit_cast(ex8, u);
-    }
-    f32x4 o[D / 16];
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -1e30f, l = 0.f;   // running maximum (log2 units) of query c, and this lane's share of the denominator
-
-    const int q_last = min(q0 + 15, s_end - 1);
-    const int k_first = max(s0, q0 - w), k_last = min(s_end - 1, q_last + w);     // (w <= n_rows: no overflow)
-    const int k_lo = max(s0, q_ref - w), k_hi = min(s_end - 1, q_ref + w);        // this lane's query
-    const uint16_t* kbase = qkv + k_col0 + (size_t)h * D + 8 * g;
-    const uint16_t* vbase = vt + ((size_t)h * D + c) * 8;
-    for (int kb = k_first & ~7; kb <= k_last; kb += 32) {
-        f32x4 s[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            // A row c of tile tt is key kb + 8 (c >> 2) + 4 tt + (c & 3): result row 4 g + i is then key kb + 8 g + 4 tt + i
-            const int krow = kb + 8 * (c >> 2) + 4 * tt + (c & 3);
-            s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < D / 32; ++kk) {
-                const uint4 u = krow < n_rows ? *reinterpret_cast<const uint4*>(kbase + (size_t)krow * ld + kk * 32) : zero4;
-                s[tt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), qf[kk], s[tt]);
-            }
-        }
-        float x[8];
-        float bm = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = kb + 8 * g + j;
-            const float v = s[j >> 2][j & 3] * scale_log2;
-            x[j] = (key >= k_lo && key <= k_hi) ? v : -INFINITY;
-            bm = fmaxf(bm, x[j]);
-        }
-        const float m_new = fmaxf(m, mb_wave_max16(bm));
-        const float alpha = exp2f(m - m_new);
-        m = m_new;
-        uint32_t pk[4];
-        float ps = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            pk[j >> 1] = pack_e2_inrange(exp2f(x[j] - m_new), exp2f(x[j + 1] - m_new));
-            ps += elo(pk[j >> 1]);
-            ps += ehi(pk[j >> 1]);
-        }
-        l = l * alpha + ps;
-        const ex8 pf = __builtin_bit_cast(ex8, uint4{pk[0], pk[1], pk[2], pk[3]});
-        // V^T fragment: feature 16 dt + c, keys kb + 8 g .. + 7 (one 8-row group of the V8 layout)
-        const int grp = (kb >> 3) + g;
-        const bool vok = 8 * grp < n_rows;
-#pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt) {
-            const uint4 u = vok ? *reinterpret_cast<const uint4*>(vbase + (size_t)grp * ldvt + (size_t)dt * 16 * 8) : zero4;
-            o[dt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), pf, o[dt] * alpha);
-        }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    if (qrow < s_end) {   // (the only lane-dependent branch: the wave is whole again for the next sequence's tile)
-        const float inv = 1.0f / l;
-        uint16_t* dst = out + (size_t)qrow * ld_out + h * D + 4 * g;
-#pragma unroll
-        for (int dt = 0; dt < D / 16; ++dt)
-            *reinterpret_cast<uint2*>(dst + dt * 16) = uint2{pack_e2(o[dt][0] * inv, o[dt][1] * inv),
-                                                             pack_e2(o[dt][2] * inv, o[dt][3] * inv)};
-    }
-}
-
+// One wave per (16-query tile, sequence, head) on varlen.h's tile with the window mask; every head has its own K and V (group 1).
 __global__ __launch_bounds__(64) void mb_attention_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
                                                           const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
                                                           int ld_out, const int32_t* __restrict__ seq_start,
@@ -220,7 +87,8 @@ __global__ __launch_bounds__(64) void mb_attention_kernel(const uint16_t* __rest
                                                           float scale_log2) {
     const int t = blockIdx.x;
     for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
-        mb_attention_tile(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, w, scale_log2, b, blockIdx.z, t);
+        attention_tile<64, true>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, 1, w, scale_log2, b,
+                                 blockIdx.z, t);
 }
 
 // ---- classification head: pooling -> head.dense -> GELU -> head.norm -> classifier -> sigmoid, fp32 ---------------------------
@@ -290,7 +158,7 @@ __global__ __launch_bounds__(64) void mb_head_kernel(const uint16_t* __restrict_
             sum += y[jj];
         }
     }
-    const float mean = mb_wave_sum(sum) / (float)H;
+    const float mean = wave_sum(sum) / (float)H;
     float var = 0.f;
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) {
@@ -299,7 +167,7 @@ __global__ __launch_bounds__(64) void mb_head_kernel(const uint16_t* __restrict_
             var += d * d;
         }
     }
-    const float rstd = rsqrtf(mb_wave_sum(var) / (float)H + eps);
+    const float rstd = rsqrtf(wave_sum(var) / (float)H + eps);
     float dot = 0.f;
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) {
@@ -308,7 +176,7 @@ __global__ __launch_bounds__(64) void mb_head_kernel(const uint16_t* __restrict_
             dot += (y[jj] - mean) * rstd * norm_g[o] * cls_w[o];
         }
     }
-    dot = mb_wave_sum(dot) + cls_b[0];
+    dot = wave_sum(dot) + cls_b[0];
     if (lane == 0) {
         scores[b] = 1.0f / (1.0f + expf(-dot));
         if (logits) logits[b] = dot;
@@ -343,26 +211,10 @@ int check_weights(const tt_modernbert_weights* w) {
     return TT_OK;
 }
 
-struct MbWs {
-    size_t off_ha, off_hb, off_x, off_qkv, off_vt, off_ctx, off_gu, off_act, off_zero, zero_bytes, total;
-};
-
-MbWs mb_plan(const tt_modernbert_weights* w, int n_rows) {
-    MbWs e{};
-    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    WsPlanner ws;
-    e.off_ha = ws.take(T * H * 2);
-    e.off_hb = ws.take(T * H * 2);
-    e.off_x = ws.take(T * H * 2);
-    e.off_qkv = ws.take(T * 3 * H * 2);
-    e.off_vt = ws.take(T * H * 2);
-    e.off_ctx = ws.take(T * H * 2);
-    e.off_gu = ws.take(T * 2 * F * 2);
-    e.off_act = ws.take(T * F * 2);
-    e.zero_bytes = std::max(3 * H, 2 * F) * 4;   // the GEMMs' bias operand and the LayerNorms' beta: the model has neither
-    e.off_zero = ws.take(e.zero_bytes);
-    e.total = ws.off;
-    return e;
+VarlenWs mb_plan(const tt_modernbert_weights* w, int n_rows) {
+    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn;
+    // zeros: the GEMMs' bias operand and the LayerNorms' beta (the model has neither)
+    return varlen_plan(n_rows, H, 3 * H, H, H, F, std::max(3 * H, 2 * F));
 }
 
 int layernorm_launch(const uint16_t* in, uint16_t* out, const float* g, const float* zero, int rows, int H, float eps, hipStream_t st) {
@@ -396,7 +248,7 @@ int window_attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0,
 
 int mb_run(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
            int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const MbWs e = mb_plan(w, n_rows);
+    const VarlenWs e = mb_plan(w, n_rows);
     char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, nh = w->heads, T = n_rows;
     uint16_t* ha = (uint16_t*)(ws + e.off_ha);
@@ -413,7 +265,7 @@ int mb_run(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* po
     TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * H * 2, st));
     {
         TtProfScope prof(TT_K_ROWOPS, st);
-        hipLaunchKernelGGL(mb_embed_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, hb);
+        hipLaunchKernelGGL(embed_gather_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, hb);
         TT_CHECK_LAUNCH();
     }
     if (int rc = layernorm_launch(hb, ha, w->emb_norm, zero, T, H, w->norm_eps, st)) return rc;
@@ -448,12 +300,7 @@ int mb_run(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* po
         GemmParams g1 = gemm_16(x, lw.wi_w, zero, T, 2 * F, H);
         g1.C = gu; g1.ldc = 2 * F;
         if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        {
-            TtProfScope prof(TT_K_ROWOPS, st);
-            const int64_t chunks = (int64_t)T * (F / 8);
-            hipLaunchKernelGGL(mb_geglu_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, gu, act, chunks, F);
-            TT_CHECK_LAUNCH();
-        }
+        if (int rc = gated_act_launch<GeluErf>(gu, act, T, F, st)) return rc;
         GemmParams g2 = gemm_16(act, lw.wo_w, zero, T, H, F);
         g2.residual = hb; g2.ldr = H; g2.C = ha; g2.ldc = H;
         if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
@@ -474,12 +321,9 @@ int tt_modernbert_forward(const tt_modernbert_weights* w, const int32_t* ids, co
                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                           void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_weights(w)) return rc;
-    TT_CHECK_ARG(type_ids == nullptr, "ModernBERT has no token types: type_ids must be NULL");
-    TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
-                 "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
-    TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
-    TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
-    if (int rc = tt_check_workspace("tt_modernbert_forward", workspace, workspace_bytes, mb_plan(w, n_rows).total)) return rc;
+    if (int rc = check_packed_forward_args("tt_modernbert_forward", "ModernBERT", ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows,
+                                           max_len, hidden_out, workspace, workspace_bytes, mb_plan(w, n_rows).total))
+        return rc;
     for (int l = 0; l < w->layers; ++l) {
         const tt_modernbert_layer_weights& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.o_w && lw.mlp_norm && lw.wi_w && lw.wo_w, "layer %d has a null weight pointer", l);

@@ -1,0 +1,205 @@
+// What the rotary, pre-norm, packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT): the attention
+// tile over the V8 layout, the embedding gather, the gated activation, the workspace plan and the forwards' argument checks.
+// Device code sits in an anonymous namespace or is a template: one copy per translation unit and element type (common.h TT_F16).
+#pragma once
+#include "common.h"
+#include "encoder.h"
+
+#include <algorithm>
+
+namespace {
+
+__device__ __forceinline__ float wave_max16(float v) {
+    // maximum over the four lanes l, l ^ 16, l ^ 32, l ^ 48 (one query column of an MFMA 16x16 result)
+    v = fmaxf(v, __shfl_xor(v, 16, 64));
+    return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+
+// ---- embedding gather: out[r] = table[ids[r]] (an id outside [0, vocab) gives a zero row); launched with 128 threads ---------
+__global__ __launch_bounds__(128) void embed_gather_kernel(const int32_t* __restrict__ ids, const uint16_t* __restrict__ table,
+                                                           int vocab, int H, uint16_t* __restrict__ out) {
+    const int row = blockIdx.x;
+    const int id = ids[row];
+    const bool ok = id >= 0 && id < vocab;
+    const uint4* src = reinterpret_cast<const uint4*>(table + (size_t)(ok ? id : 0) * H);
+    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)row * H);
+    for (int c = threadIdx.x; c < H / 8; c += blockDim.x) dst[c] = ok ? src[c] : uint4{0u, 0u, 0u, 0u};
+}
+
+// ---- gated activation: gu [T][2F] (activated columns, then the columns that multiply them) -> out [T][F] ---------------------
+// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (decoder.hip Silu, modernbert.hip GeluErf)
+template <class Act>
+__global__ __launch_bounds__(256) void gated_act_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
+                                                        int F) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_chunks) return;
+    const int64_t row = i / (F / 8), c = i % (F / 8);
+    const uint4 av = reinterpret_cast<const uint4*>(gu + row * 2 * F)[c];
+    const uint4 mv = reinterpret_cast<const uint4*>(gu + row * 2 * F + F)[c];
+    const uint32_t a4[4] = {av.x, av.y, av.z, av.w}, m4[4] = {mv.x, mv.y, mv.z, mv.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = pack_e2(Act::f(elo(a4[k])) * elo(m4[k]), Act::f(ehi(a4[k])) * ehi(m4[k]));
+    reinterpret_cast<uint4*>(out + row * F)[c] = uint4{o[0], o[1], o[2], o[3]};
+}
+
+template <class Act>
+int gated_act_launch(const uint16_t* gu, uint16_t* out, int rows, int F, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    const int64_t chunks = (int64_t)rows * (F / 8);
+    hipLaunchKernelGGL(gated_act_kernel<Act>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, gu, out, chunks, F);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
+// ---- attention over packed varlen sequences: one 16-query tile of one (sequence b, query head h) per call, one wave -------------
+// Query head h reads KV head h / group (group = 1: as many KV heads as query heads).  Tile t holds the queries q0 .. q0 + 15,
+// q0 = s0 + 16 t, of the sequence s0 .. s_end - 1.  Keys are visited in blocks of 32 on the absolute 8-row grid:
+//   WINDOW = false (causal):        the blocks from the sequence's first 8-row group up to the tile's last query; key k is live for
+//                                   query q iff s0 <= k <= q;
+//   WINDOW = true (bidirectional):  the blocks that intersect [max(s0, q0 - w), min(s_end - 1, q0 + 15 + w)]; key k is live for query
+//                                   q iff s0 <= k < s_end && |q - k| <= w.  w >= the batch's longest sequence: every key of the
+//                                   sequence, the walk and the bits of attention without a window.  (The callers keep w <= n_rows:
+//                                   q + w does not overflow.)
+// Either mask also removes the neighbouring sequences' rows of shared 8-row groups.
+//   S^T = K Q^T  (mfma 16x16x32, two tiles per key block).  The K rows each lane loads are permuted so that, for query c = lane & 15,
+//                lane l ends up holding the scores of keys kb + 8 (l >> 4) + j, j = 0..7 -- exactly the B operand of
+//   O^T += V^T P^T  (mfma 16x16x32 per 16 features), whose A operand is one 16-byte read of the V8 layout per lane.
+// Softmax in fp32 with a running maximum (log2 domain), P rounded to the element type for the product; the denominator sums the
+// rounded P, so the weights of a row sum to one as they are applied.  A block may hold no live key for some query of the tile (past
+// a window's edge, or past an earlier query of a causal tile): its P is zero and its running maximum stays where it was (-1e30
+// before the query's first live key, which only a window can put behind the tile's first block).  Each result column, maximum and
+// denominator belongs to one query: what a query gets does not depend on what the other 15 of its tile may see.
+// The kernels walk the sequences (a grid's y extent stops at 65535) and decode (b, h, t) from their own grids.
+// keep_row < 0: every query of the tile is stored, at its own row of `out`.  keep_row >= 0 (a pooled-row tail): only the query
+// at absolute row keep_row is stored, at row out_row of `out` -- the same arithmetic, so the same bits as the full tile gives it.
+template <int D, bool WINDOW>
+__device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
+                                               const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out, int ld_out,
+                                               const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len, int n_rows,
+                                               int group, int w, float scale_log2, int b, int h, int t, int keep_row = -1,
+                                               int out_row = 0) {
+    const int s0 = seq_start[b], L = seq_len[b];
+    if (s0 < 0 || 16 * t >= L) return;
+    const int s_end = min(s0 + L, n_rows);
+    const int q0 = s0 + 16 * t;
+    if (q0 >= s_end) return;
+    const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
+    const int kvh = h / group;
+    const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
+
+    // Q fragment, the B operand of S^T: lane holds Q[q0 + c][32 kk + 8 g + j]
+    ex8 qf[D / 32];
+    const int qrow = q0 + c;
+    const int q_lim = min(qrow, s_end - 1);      // rows past the sequence: computed against its keys, never stored
+#pragma unroll
+    for (int kk = 0; kk < D / 32; ++kk) {
+        const uint4 u = qrow < s_end ? *reinterpret_cast<const uint4*>(qkv + (size_t)qrow * ld + q_col0 + h * D + kk * 32 + 8 * g)
+                                     : zero4;
+        qf[kk] = __builtin_bit_cast(ex8, u);
+    }
+    f32x4 o[D / 16];
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -1e30f, l = 0.f;   // running maximum (log2 units) of query c, and this lane's share of the denominator
+
+    const int q_last = min(q0 + 15, s_end - 1);
+    const int k_first = WINDOW ? max(s0, q0 - w) : s0, k_last = WINDOW ? min(s_end - 1, q_last + w) : q_last;   // the tile's keys
+    const int k_lo = WINDOW ? max(s0, q_lim - w) : s0, k_hi = WINDOW ? min(s_end - 1, q_lim + w) : q_lim;       // this lane's query's
+    const uint16_t* kbase = qkv + k_col0 + (size_t)kvh * D + 8 * g;
+    const uint16_t* vbase = vt + ((size_t)kvh * D + c) * 8;
+    for (int kb = k_first & ~7; kb <= k_last; kb += 32) {
+        f32x4 s[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            // A row c of tile tt is key kb + 8 (c >> 2) + 4 tt + (c & 3): result row 4 g + i is then key kb + 8 g + 4 tt + i
+            const int krow = kb + 8 * (c >> 2) + 4 * tt + (c & 3);
+            s[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < D / 32; ++kk) {
+                const uint4 u = krow < n_rows ? *reinterpret_cast<const uint4*>(kbase + (size_t)krow * ld + kk * 32) : zero4;
+                s[tt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), qf[kk], s[tt]);
+            }
+        }
+        float x[8];
+        float bm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int key = kb + 8 * g + j;
+            const float v = s[j >> 2][j & 3] * scale_log2;
+            x[j] = (key >= k_lo && key <= k_hi) ? v : -INFINITY;
+            bm = fmaxf(bm, x[j]);
+        }
+        const float m_new = fmaxf(m, wave_max16(bm));
+        const float alpha = exp2f(m - m_new);
+        m = m_new;
+        uint32_t pk[4];
+        float ps = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            pk[j >> 1] = pack_e2_inrange(exp2f(x[j] - m_new), exp2f(x[j + 1] - m_new));
+            ps += elo(pk[j >> 1]);
+            ps += ehi(pk[j >> 1]);
+        }
+        l = l * alpha + ps;
+        const ex8 pf = __builtin_bit_cast(ex8, uint4{pk[0], pk[1], pk[2], pk[3]});
+        // V^T fragment: feature 16 dt + c, keys kb + 8 g .. + 7 (one 8-row group of the V8 layout)
+        const int grp = (kb >> 3) + g;
+        const bool vok = 8 * grp < n_rows;
+#pragma unroll
+        for (int dt = 0; dt < D / 16; ++dt) {
+            const uint4 u = vok ? *reinterpret_cast<const uint4*>(vbase + (size_t)grp * ldvt + (size_t)dt * 16 * 8) : zero4;
+            o[dt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, u), pf, o[dt] * alpha);
+        }
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (qrow < s_end && (keep_row < 0 || qrow == keep_row)) {   // (the only lane-dependent branch: the wave is whole again for the next sequence's tile)
+        const float inv = 1.0f / l;
+        uint16_t* dst = out + (size_t)(keep_row < 0 ? qrow : out_row) * ld_out + h * D + 4 * g;
+#pragma unroll
+        for (int dt = 0; dt < D / 16; ++dt)
+            *reinterpret_cast<uint2*>(dst + dt * 16) = uint2{pack_e2(o[dt][0] * inv, o[dt][1] * inv),
+                                                             pack_e2(o[dt][2] * inv, o[dt][3] * inv)};
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+// One forward's workspace: the residual stream twice (ha, hb), the normed rows x, the projections' outputs and the fp32 zeros that
+// stand in for the biases (and LayerNorm betas) these models do not have.  Rows are padded to the 256-row GEMM tile.
+struct VarlenWs {
+    size_t off_ha, off_hb, off_x, off_qkv, off_vt, off_ctx, off_gu, off_act, off_zero, zero_bytes, total;
+};
+
+inline VarlenWs varlen_plan(int n_rows, size_t H, size_t qkv_width, size_t vt_width, size_t ctx_width, size_t F, size_t zero_floats) {
+    VarlenWs e{};
+    const size_t T = ((size_t)n_rows + 255) / 256 * 256;
+    WsPlanner ws;
+    e.off_ha = ws.take(T * H * 2);
+    e.off_hb = ws.take(T * H * 2);
+    e.off_x = ws.take(T * H * 2);
+    e.off_qkv = ws.take(T * qkv_width * 2);
+    e.off_vt = ws.take(T * vt_width * 2);
+    e.off_ctx = ws.take(T * ctx_width * 2);
+    e.off_gu = ws.take(T * 2 * F * 2);
+    e.off_act = ws.take(T * F * 2);
+    e.zero_bytes = zero_floats * 4;
+    e.off_zero = ws.take(e.zero_bytes);
+    e.total = ws.off;
+    return e;
+}
+
+// the batch arguments every packed forward takes (`family`: "a decoder", "ModernBERT"; `need`: the plan's total -- the caller
+// computes it before n_rows is checked here: unsigned arithmetic, and not looked at unless n_rows passes)
+inline int check_packed_forward_args(const char* what, const char* family, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                                     const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len,
+                                     const void* hidden_out, const void* workspace, size_t workspace_bytes, size_t need) {
+    TT_CHECK_ARG(type_ids == nullptr, "%s has no token types: type_ids must be NULL", family);
+    TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
+                 "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
+    TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
+    TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
+    return tt_check_workspace(what, workspace, workspace_bytes, need);
+}
+
+}  // namespace

@@ -163,6 +163,37 @@ def test_a_window_that_covers_everything_is_no_window(dev, built_lib, dt):
     assert not torch.equal(less, off)
 
 
+@pytest.mark.parametrize("dt", list(DTYPES.values()), ids=list(DTYPES))
+@pytest.mark.parametrize("mode", ["tight", "aligned"])
+def test_causal_and_unwindowed_tiles_agree_on_last_rows(dev, built_lib, mode, dt):
+    """The decoder's causal kernel and the window kernel run one tile routine (csrc/varlen.h), whose arithmetic for a query does
+    not depend on what the other 15 queries of its tile may see.  For the last row of a sequence "keys <= q" and "every key of the
+    sequence" are the same set, walked in the same blocks: that row comes out of ``tt_attention_causal_gqa`` (heads == kv_heads,
+    head_dim 64) and of ``tt_attention_window`` (no window) with the same bits."""
+    _lib, lib, st = _lib_and_stream(dev)
+    heads, lens = 2, [1, 7, 8, 16, 17, 33, 40, 75]
+    H = heads * 64
+    starts, T = _pack(lens, mode)
+    assert T == 256
+    g = torch.Generator(device=dev).manual_seed(23)
+    q, k, v = (torch.randn(T, H, generator=g, device=dev) * s for s in (1.5, 1.5, 1.0))
+    qkv = torch.cat([q.to(dt), k.to(dt), v.to(dt)], dim=1).contiguous()
+    vt = _v8(v.to(dt))
+    ss = torch.tensor(starts, dtype=torch.int32, device=dev)
+    sl = torch.tensor(lens, dtype=torch.int32, device=dev)
+    causal, window = (torch.zeros(T, H, dtype=dt, device=dev) for _ in range(2))
+    rc = getattr(lib, "tt_attention_causal_gqa" + _sfx(dt))(qkv.data_ptr(), 3 * H, 0, H, vt.data_ptr(), 8 * H, causal.data_ptr(), H,
+                                                            ss.data_ptr(), sl.data_ptr(), len(lens), T, heads, heads, 64, max(lens), st)
+    _lib.check(rc, "tt_attention_causal_gqa")
+    rc = getattr(lib, "tt_attention_window" + _sfx(dt))(qkv.data_ptr(), 3 * H, 0, H, vt.data_ptr(), 8 * H, window.data_ptr(), H,
+                                                        ss.data_ptr(), sl.data_ptr(), len(lens), T, heads, 64, max(lens), -1, st)
+    _lib.check(rc, "tt_attention_window")
+    torch.cuda.synchronize()
+    last = torch.tensor([s + n - 1 for s, n in zip(starts, lens)], device=dev)
+    assert torch.isfinite(causal[last].float()).all(dim=1).all() and torch.isfinite(window[last].float()).all(dim=1).all()
+    assert torch.equal(causal[last], window[last])
+
+
 # ---- RoPE row op against fp64 -------------------------------------------------------------------------------------------------------
 def _rope_reference(x, pos, theta, heads):
     """fp64 rotate-half RoPE of the q and k heads of x [T][3H] -> (rotated [T][2H], angles [T][32])."""

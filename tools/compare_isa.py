@@ -31,6 +31,8 @@ def kernels(lib: str) -> dict:
     for line in text.splitlines():
         if "file format" in line or not line.strip() or line.startswith("Disassembly of section"):
             continue
+        if line.strip() == "...":     # llvm-objdump's mark for zero padding behind a function: depends on where its neighbour starts
+            continue
         m = SYMBOL.match(line)
         if m:
             if name is not None:
