@@ -728,6 +728,76 @@ int tt_attention_window_f16(const void* qkv, int ld, int q_col0, int k_col0, con
                             const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
                             int max_len, int window, void* stream);
 
+/* ---- EmbeddingGemma embedders: Gemma3TextModel with use_bidirectional_attention (google/embeddinggemma-300m; csrc/gemma.hip) ----
+ * With norm(v; w) = v * rsqrt(mean(v^2) + eps) * (1 + w) (note the 1 + w): h = embed_tokens[ids] * embed_scale (no position
+ * table, no token types); per layer, four norms around two sublayers, the residual added AFTER the post-norm:
+ *   x = norm(h; input_norm) -> q | k | v projection -> per-head norm of q and k (q_norm, k_norm), rotate-half RoPE with the layer
+ *   type's base (positions 0-based within each sequence) -> bidirectional grouped-query attention over the sequence's own tokens
+ *   (query head h reads KV head h / (heads / kv_heads); scale 1 / sqrt(head_dim)), on a "sliding" layer restricted to keys with
+ *   |q - k| <= window -> o projection -> h = h + norm(.; post_attn_norm) -> x = norm(h; pre_ffn_norm) -> gate | up projection ->
+ *   GELU_tanh(gate) * up -> down projection -> h = h + norm(.; post_ffn_norm);
+ * a final norm.  `window` is what the kernels compare with: transformers rewrites a bidirectional config's sliding_window S to
+ * S / 2 + 1 when it loads it and masks with |q - k| < that value, so a config.json holding S means window = S / 2.
+ * Same packed token layout as tt_encoder_forward (`pos` = position within the sequence, type_ids must be NULL), same projections
+ * (the 16-bit GEMMs), bf16 only: the model card rules fp16 out, and there are no `_f16` twins.  Matrices [out][in] in bf16, norm
+ * weights fp32 as the checkpoint stores them (w, not 1 + w).  hidden a multiple of 128 and <= 1024 (the scan's limit), head_dim 256,
+ * heads a multiple of kv_heads, (heads + 2 kv_heads) * head_dim a multiple of 128, heads * head_dim and ffn multiples of 64; anything
+ * else is refused before a launch. */
+typedef struct tt_gemma_layer_weights {
+    const void* qkv_w;           /* [(heads + 2 kv_heads) * head_dim][H]: q_proj, k_proj, v_proj rows concatenated */
+    const float* q_norm;         /* [head_dim] self_attn.q_norm */
+    const float* k_norm;         /* [head_dim] self_attn.k_norm */
+    const void* o_w;             /* [H][heads * head_dim] */
+    const float* input_norm;     /* [H] input_layernorm */
+    const float* post_attn_norm; /* [H] post_attention_layernorm */
+    const float* pre_ffn_norm;   /* [H] pre_feedforward_layernorm */
+    const float* post_ffn_norm;  /* [H] post_feedforward_layernorm */
+    const void* gate_up_w;       /* [2F][H]: gate_proj rows, then up_proj rows */
+    const void* down_w;          /* [H][F] */
+    int32_t sliding;             /* 1: a sliding_attention layer (window, local RoPE base); 0: full_attention (global base) */
+} tt_gemma_layer_weights;
+
+typedef struct tt_gemma_weights {
+    int32_t hidden, layers, heads, kv_heads, head_dim, ffn, vocab, window;
+    float rms_eps, global_rope_theta, local_rope_theta;
+    float embed_scale;           /* sqrt(hidden) rounded to bf16, as Gemma3TextScaledWordEmbedding rounds it to the weights' type */
+    const void* embed;           /* [vocab][H] embed_tokens */
+    const tt_gemma_layer_weights* layer; /* host array [layers] */
+    const float* final_norm;     /* [H] norm */
+    /* the sentence-transformers Dense modules behind the pooling (tt_gemma_pool_dense), fp32, no bias, identity activation */
+    int32_t dense1_out, dense2_out;
+    const float* dense1_wt;      /* [H][dense1_out]: 2_Dense linear.weight TRANSPOSED ([in][out]) */
+    const float* dense2_wt;      /* [dense1_out][dense2_out]: 3_Dense linear.weight TRANSPOSED */
+} tt_gemma_weights;
+
+size_t tt_gemma_workspace_bytes(const tt_gemma_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state (after the final norm) */
+int tt_gemma_forward(const tt_gemma_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                     const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* sentence-transformers Pooling(mean) -> Dense -> Dense -> Normalize in fp32: p = the mean of the sequence's rows of hidden
+ * [.][ld] bf16 (tt_gemma_forward's output), summed in ascending order; v = dense2(dense1(p)); out_f32[b] = v / max(||v||, 1e-12),
+ * [n_seq][dense2_out]; out_16 (optional) the same vector in bf16 (ready to be a scan query).  dense1_out a multiple of 64 up to
+ * 3072, dense2_out a multiple of 64 up to 1024.  A workgroup handles eight sequences, so the matrices are read once per eight; a
+ * sequence's vector does not depend on the batch it travels in. */
+int tt_gemma_pool_dense(const tt_gemma_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
+                        int n_seq, float* out_f32, void* out_16, void* stream);
+/* building blocks (parity tests; the forward's own kernels), bf16, head_dim 256.
+ * tt_gemma_qk_norm_rope: tt_qk_norm_rope's arguments and layout; q and k heads normalised with (1 + q_norm) / (1 + k_norm) and
+ *   rotated at pos[row] with base rope_theta in place, the v heads copied to the V8 layout.
+ * tt_gemma_add_norm: rows of H elements; h_out = h + norm(y; norm_a), x_out = norm(h + norm(y; norm_a); norm_b), both from the
+ *   unrounded sum and rounded once.  y NULL: x_out = norm(h; norm_b) only (norm_a, h_out unused).  The four buffers are distinct.
+ * tt_attention_window_gqa: out[q][h * head_dim ...] = softmax over the keys k of q's own sequence with |q - k| <= window of
+ *   (Q_h . K_{h/g}) / sqrt(head_dim), applied to V_{h/g} (window < 0: every key of the sequence); Q at q_col0 + h * head_dim, K at
+ *   k_col0 + kvh * head_dim of rows of ld elements, V in the V8 layout; any sequence start; rows of no sequence are not written. */
+int tt_gemma_qk_norm_rope(void* qkv, int ld, const int32_t* pos, const float* q_norm, const float* k_norm, int n_rows, int heads,
+                          int kv_heads, int head_dim, float eps, float rope_theta, void* vt, int ldvt, void* stream);
+int tt_gemma_add_norm(const void* y, const void* h, const float* norm_a, const float* norm_b, int n_rows, int hidden, float eps,
+                      void* h_out, void* x_out, void* stream);
+int tt_attention_window_gqa(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads,
+                            int head_dim, int max_len, int window, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

@@ -78,24 +78,31 @@ class HipHuggingFaceEmbedding:
         # sentence-transformers pooling: what the checkpoint directory declares (1_Pooling/config.json), unless the caller says
         # (model_kwargs["pooling"]); "cls" for the BGE family the reference defaults to, "mean" for e5 / all-MiniLM / gte ...,
         # "last" for the decoder embedders (also when their directory declares nothing)
-        pooling = (model_kwargs or {}).get("pooling") or _weights.pooling_mode(mdir, "last" if cfg.arch == "qwen3" else "cls")
+        default_pooling = {"qwen3": "last", "gemma3_text": "mean"}.get(cfg.arch, "cls")
+        pooling = (model_kwargs or {}).get("pooling") or _weights.pooling_mode(mdir, default_pooling)
         pooling = {"cls_token": "cls", "mean_tokens": "mean", "lasttoken": "last"}.get(pooling, pooling)
         if pooling not in ("cls", "mean", "last") or (pooling == "last" and cfg.arch != "qwen3"):
             # no silent wrong vectors: anything else (max, weighted mean, last token of an encoder ...) has no kernel here
             raise NotImplementedError(f"{model_name}: sentence-transformers pooling '{pooling}' is not supported "
                                       f"(CLS and mean pooling, and last-token pooling of decoder embedders, all followed by "
                                       f"L2 normalisation, are)")
+        if cfg.arch == "gemma3_text" and pooling != "mean":
+            raise NotImplementedError(f"{model_name}: pooling '{pooling}': an EmbeddingGemma checkpoint pools the mean (its Dense "
+                                      f"modules follow it)")
         self.pooling = pooling
         # precision.resolve(): model_kwargs (torch_dtype float32 = the reference's own default, config_schema.py:66-76),
         # ModelManager.precision, TT_PRECISION; default: the reference's fp32 semantics.  (`_model.parameters()` is read by the memory accounting.)
         self._model, self._encoder, self.precision = _precision.build_encoder(cfg, state, dev, model_kwargs, f"embedder {model_name}")
+        # width of an embedding: the hidden size, or what the checkpoint's last Dense module writes (EmbeddingGemma)
+        self.embed_dim = getattr(self._model, "out_dim", cfg.hidden)
         self._tokenizer = (model_kwargs or {}).get("tokenizer") or load_tokenizer(mdir, cfg.arch, cfg.vocab_size)
         self.max_length = min(max_length or cfg.max_seq_len, cfg.max_seq_len)
         self.query_instruction = query_instruction_for(model_name) if query_instruction is None else query_instruction
         self.text_instruction = text_instruction or ""
-        if cfg.arch == "modernbert":
-            # sentence-transformers prompts (config_sentence_transformers.json), e.g. nomic's "search_query: " / "search_document: ":
-            # "query" for queries, "document" for texts, where the checkpoint names them
+        if cfg.arch in ("modernbert", "gemma3_text"):
+            # sentence-transformers prompts (config_sentence_transformers.json), e.g. nomic's "search_query: " / "search_document: " or
+            # EmbeddingGemma's "task: search result | query: " / "title: none | text: ": "query" for queries, "document" for
+            # texts, where the checkpoint names them
             pr = _weights.prompts(mdir)
             if query_instruction is None:
                 self.query_instruction = pr.get("query", "")
@@ -141,7 +148,7 @@ class HipHuggingFaceEmbedding:
                                                 pooling=self.pooling)
             parts.append(emb)
             lo = hi
-        out = torch.empty((len(seqs), self.config.hidden), dtype=torch.float32, device=self.device)
+        out = torch.empty((len(seqs), self.embed_dim), dtype=torch.float32, device=self.device)
         if parts:  # one scatter back to the caller's order (one small index upload per call, not per batch)
             out[torch.tensor(order, dtype=torch.int64).to(self.device, non_blocking=True)] = torch.cat(parts)
         return out
@@ -154,7 +161,7 @@ class HipHuggingFaceEmbedding:
 
         lens = np.asarray(lens, dtype=np.int64)
         n = len(lens)
-        out = torch.empty((n, self.config.hidden), dtype=torch.float32, device=self.device)
+        out = torch.empty((n, self.embed_dim), dtype=torch.float32, device=self.device)
         if n == 0:
             return out
         flat = np.asarray(flat, dtype=np.int32)
@@ -201,7 +208,7 @@ class HipHuggingFaceEmbedding:
         while bounds[-1] < n:
             bounds.append(min(n, bounds[-1] + win))
         spans = list(zip(bounds[:-1], bounds[1:]))
-        out = torch.empty((n, self.config.hidden), dtype=torch.float32, device=self.device)
+        out = torch.empty((n, self.embed_dim), dtype=torch.float32, device=self.device)
         with ThreadPoolExecutor(max_workers=2) as pool:
             futs = [pool.submit(self._tokenize, texts[a:b], prefix) for a, b in spans[:2]]
             for i, (a, b) in enumerate(spans):

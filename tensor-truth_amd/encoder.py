@@ -35,7 +35,9 @@ from . import _lib
 class EncoderConfig:
     """The HF config fields the hot path reads."""
 
-    arch: str = "xlmr"  # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig) | "modernbert" (modernbert.ModernBertConfig)
+    # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig) | "modernbert" (modernbert.ModernBertConfig) |
+    # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig)
+    arch: str = "xlmr"
     vocab_size: int = 250002
     hidden: int = 1024
     layers: int = 24
@@ -129,6 +131,7 @@ class EncoderPath:
     rows_workspace: Optional[str] = None  # (``pooled_rows``), and its workspace size
     score: Optional[str] = None      # decoder paths: the *ForSequenceClassification score head over those rows
     pooled_head: Optional[str] = None  # ModernBERT paths: pooling ("cls" / "mean") + classification head over the full forward
+    pool_dense: Optional[str] = None   # EmbeddingGemma path: mean pooling + the two Dense modules + L2 norm over the full forward
 
 
 BF16_PATH = EncoderPath(forward="tt_encoder_forward", workspace="tt_encoder_workspace_bytes",
@@ -164,6 +167,12 @@ MODERNBERT_FP16_PATH = EncoderPath(forward="tt_modernbert_forward_f16", workspac
                                    pool_mean="tt_embed_pool_mean_f16", head=None, scratch="enc", head_scratch="head",
                                    hidden=torch.float16, pool_writes_bf16=False, pooled_head="tt_modernbert_head_f16",
                                    no_fp8="the ModernBERT path has no fp8 projections")
+# EmbeddingGemma embedders (gemma.GemmaWeights): full forward, then the sentence-transformers tail in one entry point (mean pooling,
+# Dense, Dense, Normalize); bf16 only, no other pooling, no head.
+GEMMA_BF16_PATH = EncoderPath(forward="tt_gemma_forward", workspace="tt_gemma_workspace_bytes", cls_forward=None, cls_workspace=None,
+                              pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc", head_scratch="head",
+                              hidden=torch.bfloat16, pool_dense="tt_gemma_pool_dense",
+                              no_fp8="the EmbeddingGemma path has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -793,6 +802,19 @@ class Encoder:
         "last" (the last token of every sequence: decoder embedders)."""
         p, dev = self.path, self.device
         B, H = len(batch.seq_len), self.cfg.hidden
+        if p.pool_dense is not None:
+            # EmbeddingGemma: the checkpoint's own tail (mean pooling -> Dense -> Dense -> Normalize) behind the full forward
+            if pooling != "mean":
+                raise ValueError(f"pooling '{pooling}': an EmbeddingGemma checkpoint pools the mean (its Dense modules follow it)")
+            hidden, starts, lens = self.forward_packed(batch, want_lens=True)
+            out = torch.empty((B, self.w.out_dim), dtype=torch.float32, device=dev)
+            out16 = torch.empty((B, self.w.out_dim), dtype=torch.bfloat16, device=dev)
+            with torch.cuda.device(dev):
+                rc = getattr(self.lib, p.pool_dense)(ctypes.byref(self.w.struct), hidden.data_ptr(), H, starts.data_ptr(),
+                                                     lens.data_ptr(), B, out.data_ptr(), out16.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(rc, p.pool_dense)
+            return out, out16
         out = torch.empty((B, H), dtype=torch.float32, device=dev)
         # the 16-bit copy of an embedding is a SCAN QUERY, i.e. bf16 like the corpus: the pooling kernels write it themselves,
         # except in the fp16 mode, where it is rounded from the fp32 vector here (round to nearest even either way)

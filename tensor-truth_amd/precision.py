@@ -125,6 +125,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
         return _build_decoder(cfg, state, device, mode, what)
     if getattr(cfg, "arch", "") == "modernbert":
         return _build_modernbert(cfg, state, device, mode, what)
+    if getattr(cfg, "arch", "") == "gemma3_text":
+        return _build_gemma(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
     make, desc = _implementations()[impl]
     w = make(cfg, state, device)
@@ -176,4 +178,22 @@ def _build_modernbert(cfg, state, device, mode: str, what: str) -> Tuple[Any, An
     w = ModernBertWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
     desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
     logger.info("%s: ModernBERT encoder, precision = %s", what, desc)
+    return w, Encoder(w), desc
+
+
+def _build_gemma(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """EmbeddingGemma embedders: bf16 only.  The model card rules float16 out (the activations overflow its range), and the
+    reference precision (fp32 semantics, what no torch_dtype means for the XLM-R / BERT family) has no implementation here:
+    refused, never computed in another precision behind the caller's back."""
+    from .encoder import Encoder
+    from .gemma import GemmaWeights
+
+    if mode != "bf16":
+        why = (" (the model card: float16 is not supported, the activations overflow its range)" if mode == "fp16" else "")
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for EmbeddingGemma embedders{why}; pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}}")
+    w = GemmaWeights(cfg, state, device)
+    desc = "bf16 (fp32 accumulate)"
+    logger.info("%s: EmbeddingGemma embedder, precision = %s", what, desc)
     return w, Encoder(w), desc

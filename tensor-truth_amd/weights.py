@@ -107,8 +107,56 @@ def _modernbert_config_from_hf(d: dict) -> EncoderConfig:
         local_attention=int(d.get("local_attention", 128)), classifier_pooling=str(d.get("classifier_pooling", "cls")))
 
 
+def _gemma_config_from_hf(d: dict) -> EncoderConfig:
+    """``model_type == "gemma3_text"`` with ``use_bidirectional_attention`` (google/embeddinggemma-300m): every size from
+    config.json.  ``layer_types`` is read; derived from ``sliding_window_pattern`` only where an older export does not carry it,
+    like the two RoPE bases (``rope_parameters``, else ``rope_theta`` / ``rope_local_base_freq``).  The window the kernels compare
+    with is ``sliding_window // 2``: transformers rewrites a bidirectional config's S to ``S // 2 + 1`` on load and masks with
+    ``|q - k| <`` that value."""
+    from .gemma import LAYER_KINDS, GemmaConfig, default_layer_types
+
+    layers = d["num_hidden_layers"]
+    layer_types = d.get("layer_types") or default_layer_types(layers, int(d.get("sliding_window_pattern", 6)))
+    rp = d.get("rope_parameters") or {}
+    g, loc = rp.get("full_attention") or {}, rp.get("sliding_attention") or {}
+    rope_types = sorted({str(x.get("rope_type", x.get("type", "default"))) for x in (g, loc, d.get("rope_scaling") or {})})
+    head_dim = d.get("head_dim") or 256     # Gemma3TextConfig's default (not hidden // heads)
+    act = d.get("hidden_activation", "gelu_pytorch_tanh")
+    qpas = d.get("query_pre_attn_scalar", 256)
+    kinds = sorted(set(layer_types))
+    # variants the EmbeddingGemma kernels do not compute are refused by field name, never run as the plain model
+    bad = [f"{n}={v!r}" for n, v, ok in (
+        ("use_bidirectional_attention", d.get("use_bidirectional_attention"), d.get("use_bidirectional_attention") is True),
+        ("attn_logit_softcapping", d.get("attn_logit_softcapping"), d.get("attn_logit_softcapping") is None),
+        ("attention_bias", d.get("attention_bias", False), not d.get("attention_bias", False)),
+        ("hidden_activation", act, act == "gelu_pytorch_tanh"),
+        ("rope_type", rope_types, rope_types == ["default"]),
+        ("query_pre_attn_scalar", qpas, qpas == head_dim),
+        ("layer_types", kinds, not set(kinds) - set(LAYER_KINDS))) if not ok]
+    if bad:
+        raise NotImplementedError(f"gemma3_text checkpoint with {', '.join(bad)}: the EmbeddingGemma path computes the bias-free "
+                                  "bidirectional text encoder with default RoPE, GELU_tanh and a 1 / sqrt(head_dim) score scale "
+                                  "only (use_bidirectional_attention false or absent is a causal language model)")
+    if "ForSequenceClassification" in " ".join(d.get("architectures") or []):
+        raise NotImplementedError("gemma3_text classification checkpoints are not supported (architectures names a "
+                                  "*ForSequenceClassification)")
+    heads = d["num_attention_heads"]
+    pad = d.get("pad_token_id")
+    vocab = d["vocab_size"]
+    return GemmaConfig(
+        arch="gemma3_text", vocab_size=vocab, hidden=d["hidden_size"], layers=layers, heads=heads, ffn=d["intermediate_size"],
+        max_pos=d["max_position_embeddings"], type_vocab=1, pad_id=int(pad) if pad is not None and 0 <= int(pad) < vocab else 0,
+        ln_eps=d.get("rms_norm_eps", 1e-6), num_labels=0, kv_heads=d.get("num_key_value_heads") or heads, head_dim=head_dim,
+        layer_types=tuple(layer_types),
+        global_rope_theta=float(g.get("rope_theta") or d.get("rope_theta") or 1e6),
+        local_rope_theta=float(loc.get("rope_theta") or d.get("rope_local_base_freq") or 1e4),
+        window=int(d.get("sliding_window", 4096)) // 2)
+
+
 def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
     mt = d.get("model_type", "xlm-roberta")
+    if mt == "gemma3_text":
+        return _gemma_config_from_hf(d)
     if mt == "qwen3":
         return _decoder_config_from_hf(d)
     if mt == "modernbert":
@@ -231,7 +279,12 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
     if mdir is not None:
         with open(os.path.join(mdir, "config.json")) as f:
             cfg = _config_from_hf(json.load(f), 1 if want_head else 0)
-        return cfg, load_state(mdir), mdir
+        state = load_state(mdir)
+        if cfg.arch == "gemma3_text" and not want_head:
+            from .gemma import dense_modules
+
+            state.update(dense_modules(mdir))      # the sentence-transformers Dense pair lives beside the transformer's tensors
+        return cfg, state, mdir
     if "synthetic_seed" in mk:
         if cfg is None:
             raise ValueError(f"no architecture known for '{model_name}': pass model_kwargs['encoder_config']")
@@ -244,6 +297,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .modernbert import synthetic_state as modernbert_state
 
             return cfg, modernbert_state(cfg, seed), None
+        if cfg.arch == "gemma3_text":
+            from .gemma import synthetic_state as gemma_state
+
+            return cfg, gemma_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
