@@ -798,6 +798,48 @@ int tt_attention_window_gqa(const void* qkv, int ld, int q_col0, int k_col0, con
                             const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads,
                             int head_dim, int max_len, int window, void* stream);
 
+/* ---- MPNet encoders: MPNetModel embedders (csrc/mpnet.hip) ---------------------------------------------------------------------
+ * sentence-transformers/all-mpnet-base-v2, all-mpnet-base-v1, multi-qa-mpnet-base-dot-v1 / -cos-v1.  The post-LN block of
+ * tt_encoder_forward (separate q / k / v / o projections with biases, concatenated to the [3H][H] layout; exact-erf GELU) with two
+ * differences: the embeddings are LayerNorm(word[id] + position[pos]) -- no token types; positions start at padding_idx + 1 = 2,
+ * as in XLM-R -- and every layer's attention adds a learned relative-position bias to the scores before the softmax,
+ *   softmax(q . k / 8 + rel_bias[bucket(key - query)][h]),  bidirectional within the sequence,
+ * one [32 buckets][heads] table for all layers; bucket = MPNetEncoder.relative_position_bucket with 32 buckets and max_distance
+ * 128 (both hard-coded in transformers): with n = query - key, 16 [n < 0] + f(|n|), f(m) = m below 8, else
+ * min(15, 8 + trunc(log(m / 8) / log(16) * 8)).  Every distance beyond +-128 falls into the last bucket of its side, so the bias
+ * of a distance is ONE lookup in a per-head table over the clamped distance, which the caller builds when it loads the weights:
+ *   bias_table[h][d + 128] = rel_bias[bucket(d)][h] * log2(e),  d = key - query in [-128, 128]      ([heads][257] fp32).
+ * Same packed token layout as tt_encoder_forward (type_ids must be NULL), the same projections and LayerNorms, bf16 -- or fp16 for
+ * the `_f16` twins.  enc.type_emb, the classification head and ffn_absmax_out are not read.  hidden a multiple of 128 and <= 1024,
+ * hidden = 64 * heads (head_dim 64), ffn a multiple of 128, no fp8 pointer in any layer; anything else is refused before a
+ * launch. */
+typedef struct tt_mpnet_weights {
+    tt_encoder_weights enc;   /* the encoder's tensors (type_emb, cls_*, ffn_absmax_out unused) */
+    const float* rel_bias;    /* [32][heads] fp32: attention.relative_attention_bias.weight as the checkpoint stores it -- what
+                                 bias_table was built from; must be present, the kernels read bias_table */
+    const float* bias_table;  /* [heads][257] fp32, see above */
+} tt_mpnet_weights;
+
+size_t tt_mpnet_workspace_bytes(const tt_mpnet_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state */
+int tt_mpnet_forward(const tt_mpnet_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                     const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* building block (parity tests; the forward's own kernel): tt_attention_window's operands without a window, plus the bias --
+ *   out[q][h * 64 ...] = softmax over the keys k of q's own sequence of (Q_h . K_h) / 8 + bias_table[h][clamp(k - q, -128, 128) + 128]
+ *   / log2(e), applied to V_h.  An all-zero table gives tt_attention_window's bits (window < 0).  head_dim must be 64. */
+int tt_attention_relbias(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                         int max_len, const float* bias_table, void* stream);
+/* the fp16 twins (mpnet.hip compiled a second time) */
+size_t tt_mpnet_workspace_bytes_f16(const tt_mpnet_weights* w, int n_rows);
+int tt_mpnet_forward_f16(const tt_mpnet_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int tt_attention_relbias_f16(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                             const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                             int max_len, const float* bias_table, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

@@ -226,6 +226,17 @@ SIGNATURES = {
     "tt_gemma_add_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "tt_attention_window_gqa": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    # MPNet encoders (csrc/mpnet.hip) and their fp16 twins (same signatures)
+    "tt_mpnet_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "tt_mpnet_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_attention_relbias": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tt_mpnet_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
+    "tt_mpnet_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_attention_relbias_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

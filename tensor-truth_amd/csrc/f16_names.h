@@ -53,3 +53,7 @@
 #define tt_modernbert_head tt_modernbert_head_f16
 #define tt_rope_v8 tt_rope_v8_f16
 #define tt_attention_window tt_attention_window_f16
+// mpnet.hip a second time: the MPNet encoders in fp16
+#define tt_mpnet_workspace_bytes tt_mpnet_workspace_bytes_f16
+#define tt_mpnet_forward tt_mpnet_forward_f16
+#define tt_attention_relbias tt_attention_relbias_f16

@@ -1,4 +1,5 @@
-// What the rotary, pre-norm, packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT): the attention
+// What the rotary, pre-norm, packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT; gemma.hip; and,
+// for the attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias): the attention
 // tile over the V8 layout, the embedding gather, the gated activation, the workspace plan and the forwards' argument checks.
 // Device code sits in an anonymous namespace or is a template: one copy per translation unit and element type (common.h TT_F16).
 #pragma once
@@ -73,12 +74,34 @@ int gated_act_launch(const uint16_t* gu, uint16_t* out, int rows, int F, hipStre
 // The kernels walk the sequences (a grid's y extent stops at 65535) and decode (b, h, t) from their own grids.
 // keep_row < 0: every query of the tile is stored, at its own row of `out`.  keep_row >= 0 (a pooled-row tail): only the query
 // at absolute row keep_row is stored, at row out_row of `out` -- the same arithmetic, so the same bits as the full tile gives it.
-template <int D, bool WINDOW>
+// Bias policy (MPNet's relative-position bias, mpnet.hip): what is added to a score, in log2 units, before the mask.
+//   NoBias (default): nothing -- the code of a tile without the parameter.
+//   RelBias: x = s * scale_log2 + tbl[clamp(key - query, -R, R) + R], tbl the head's 2R + 1 floats.  The workgroup stages them in
+//            LDS once, PAD copies of the end values on either side (relbias_stage): a lane's eight keys of a block are eight
+//            consecutive distances, so ONE clamp of the first distance to [-R - PAD, R + 1] leaves eight consecutive reads that
+//            give the clamped entries (all eight at tbl[0] below the range, all at tbl[2R] above it).  Dword reads: within a
+//            32-lane half the first distances 8 g - c span 24 consecutive dwords -- distinct banks, equal addresses broadcast.
+struct NoBias {
+    static constexpr bool on = false;
+};
+struct RelBias {
+    static constexpr bool on = true;
+    static constexpr int R = 128, PAD = 8, LDS_FLOATS = 2 * R + 1 + 2 * PAD;
+    const float* lds;   // the staged table: lds[i] = tbl[clamp(i - PAD, 0, 2R)]
+};
+// stage head h's table (tbl + h * (2R + 1)) for RelBias; every thread of the workgroup calls it, `lds` holds LDS_FLOATS floats
+__device__ __forceinline__ void relbias_stage(const float* __restrict__ tbl, int h, float* lds) {
+    for (int i = threadIdx.x; i < RelBias::LDS_FLOATS; i += blockDim.x)
+        lds[i] = tbl[(size_t)h * (2 * RelBias::R + 1) + min(max(i - RelBias::PAD, 0), 2 * RelBias::R)];
+    __syncthreads();
+}
+
+template <int D, bool WINDOW, class Bias = NoBias>
 __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
                                                const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out, int ld_out,
                                                const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len, int n_rows,
                                                int group, int w, float scale_log2, int b, int h, int t, int keep_row = -1,
-                                               int out_row = 0) {
+                                               int out_row = 0, Bias bias = Bias{}) {
     const int s0 = seq_start[b], L = seq_len[b];
     if (s0 < 0 || 16 * t >= L) return;
     const int s_end = min(s0 + L, n_rows);
@@ -123,10 +146,14 @@ __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv,
         }
         float x[8];
         float bm = -INFINITY;
+        const float* brow = nullptr;   // RelBias: the staged entry of this lane's first key of the block
+        if constexpr (Bias::on)
+            brow = bias.lds + (min(max(kb + 8 * g - qrow, -Bias::R - Bias::PAD), Bias::R + 1) + Bias::R + Bias::PAD);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int key = kb + 8 * g + j;
-            const float v = s[j >> 2][j & 3] * scale_log2;
+            float v = s[j >> 2][j & 3] * scale_log2;
+            if constexpr (Bias::on) v += brow[j];
             x[j] = (key >= k_lo && key <= k_hi) ? v : -INFINITY;
             bm = fmaxf(bm, x[j]);
         }

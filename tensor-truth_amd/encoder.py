@@ -36,7 +36,7 @@ class EncoderConfig:
     """The HF config fields the hot path reads."""
 
     # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig) | "modernbert" (modernbert.ModernBertConfig) |
-    # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig)
+    # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig) | "mpnet" (MPNet embedders: mpnet.MpnetWeights; positions as "xlmr")
     arch: str = "xlmr"
     vocab_size: int = 250002
     hidden: int = 1024
@@ -51,8 +51,8 @@ class EncoderConfig:
 
     @property
     def max_seq_len(self) -> int:
-        # XLM-R reserves positions 0..pad_id for padding
-        return self.max_pos - (self.pad_id + 1) if self.arch == "xlmr" else self.max_pos
+        # XLM-R (and MPNet) reserves positions 0..pad_id for padding
+        return self.max_pos - (self.pad_id + 1) if self.arch in ("xlmr", "mpnet") else self.max_pos
 
 
 BGE_M3 = EncoderConfig()
@@ -173,6 +173,15 @@ GEMMA_BF16_PATH = EncoderPath(forward="tt_gemma_forward", workspace="tt_gemma_wo
                               pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc", head_scratch="head",
                               hidden=torch.bfloat16, pool_dense="tt_gemma_pool_dense",
                               no_fp8="the EmbeddingGemma path has no fp8 projections")
+# MPNet embedders (mpnet.MpnetWeights): full forward with the relative-position bias in the attention; first-token and mean pooling
+# with the encoder's kernels; no CLS-only forward, no head, no fp8.
+MPNET_BF16_PATH = EncoderPath(forward="tt_mpnet_forward", workspace="tt_mpnet_workspace_bytes", cls_forward=None, cls_workspace=None,
+                              pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc", head_scratch="head",
+                              hidden=torch.bfloat16, no_fp8="the MPNet path has no fp8 projections")
+MPNET_FP16_PATH = EncoderPath(forward="tt_mpnet_forward_f16", workspace="tt_mpnet_workspace_bytes_f16", cls_forward=None,
+                              cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
+                              scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
+                              no_fp8="the MPNet path has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -492,7 +501,7 @@ def pack_tokens(seqs: Sequence[Sequence[int]], cfg: EncoderConfig,
         raise ValueError("token id outside the vocabulary")
     ids = np.full(n_rows, cfg.pad_id, dtype=np.int32)
     pos = np.zeros(n_rows, dtype=np.int32)
-    pos_off = cfg.pad_id + 1 if cfg.arch == "xlmr" else 0
+    pos_off = cfg.pad_id + 1 if cfg.arch in ("xlmr", "mpnet") else 0
     ids[dest] = flat
     pos[dest] = within + pos_off
     types = None
@@ -529,7 +538,7 @@ def pack_flat(flat: np.ndarray, first: np.ndarray, lens: np.ndarray, sel: np.nda
         raise ValueError("token id outside the vocabulary")
     ids = np.full(n_rows, cfg.pad_id, dtype=np.int32)
     pos = np.zeros(n_rows, dtype=np.int32)
-    pos_off = cfg.pad_id + 1 if cfg.arch == "xlmr" else 0
+    pos_off = cfg.pad_id + 1 if cfg.arch in ("xlmr", "mpnet") else 0
     ids[dest] = vals
     pos[dest] = within + pos_off
     return PackedBatch(ids, pos, None, starts.astype(np.int32), ln.astype(np.int32), int(n_rows), int(ln.max()), total)
@@ -549,7 +558,7 @@ def pack_token_matrix(ids2d: np.ndarray, cfg: EncoderConfig, type_ids2d: Optiona
     n_rows = _round_rows(n * stride)
     ids = np.full(n_rows, cfg.pad_id, dtype=np.int32)
     pos = np.zeros(n_rows, dtype=np.int32)
-    pos_off = cfg.pad_id + 1 if cfg.arch == "xlmr" else 0
+    pos_off = cfg.pad_id + 1 if cfg.arch in ("xlmr", "mpnet") else 0
     view = ids[: n * stride].reshape(n, stride)
     view[:, :length] = ids2d
     pos[: n * stride].reshape(n, stride)[:, :length] = np.arange(length, dtype=np.int32) + pos_off

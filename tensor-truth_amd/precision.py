@@ -127,6 +127,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
         return _build_modernbert(cfg, state, device, mode, what)
     if getattr(cfg, "arch", "") == "gemma3_text":
         return _build_gemma(cfg, state, device, mode, what)
+    if getattr(cfg, "arch", "") == "mpnet":
+        return _build_mpnet(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
     make, desc = _implementations()[impl]
     w = make(cfg, state, device)
@@ -196,4 +198,23 @@ def _build_gemma(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, st
     w = GemmaWeights(cfg, state, device)
     desc = "bf16 (fp32 accumulate)"
     logger.info("%s: EmbeddingGemma embedder, precision = %s", what, desc)
+    return w, Encoder(w), desc
+
+
+def _build_mpnet(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """MPNet embedders: bf16 or fp16, resolved as for the ModernBERT encoders.  The reference precision (fp32 semantics, what no
+    torch_dtype means for the XLM-R / BERT family) has no MPNet implementation: refused, never computed in another precision
+    behind the caller's back."""
+    import torch
+
+    from .encoder import Encoder
+    from .mpnet import MpnetWeights
+
+    if mode not in ("bf16", "fp16"):
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for MPNet encoders; pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}} or {{'torch_dtype': 'float16'}}")
+    w = MpnetWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
+    desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
+    logger.info("%s: MPNet encoder, precision = %s", what, desc)
     return w, Encoder(w), desc

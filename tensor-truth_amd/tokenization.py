@@ -118,7 +118,7 @@ def assemble_pairs(tk, pairs, max_length: int):
 
 class SpecialTokens:
     def __init__(self, arch: str):
-        if arch == "xlmr":
+        if arch in ("xlmr", "mpnet"):      # MPNet: <s> 0, <pad> 1, </s> 2, <unk> 3 and the pair <s> A </s></s> B </s> too
             self.bos, self.pad, self.eos, self.unk, self.first_free = 0, 1, 2, 3, 4
             self.pair_sep = [2, 2]          # <s> A </s></s> B </s>
         else:
@@ -180,8 +180,9 @@ class HashTokenizer:
         na, nb = truncate_longest_first(len(ia), len(ib), max(budget, 0))      # (the Rust library's rule: one definition for both tokenizers)
         ia, ib = ia[:na], ib[:nb]
         ids = [self.sp.bos] + ia + self.sp.pair_sep + ib + [self.sp.eos]
-        n_a = 1 + len(ia) + (1 if self.arch != "xlmr" else len(self.sp.pair_sep))
-        types = [0] * n_a + [1] * (len(ids) - n_a) if self.arch != "xlmr" else [0] * len(ids)
+        one_type = self.arch in ("xlmr", "mpnet")
+        n_a = 1 + len(ia) + (1 if not one_type else len(self.sp.pair_sep))
+        types = [0] * n_a + [1] * (len(ids) - n_a) if not one_type else [0] * len(ids)
         return ids, types
 
 

@@ -153,8 +153,34 @@ def _gemma_config_from_hf(d: dict) -> EncoderConfig:
         window=int(d.get("sliding_window", 4096)) // 2)
 
 
+def _mpnet_config_from_hf(d: dict) -> EncoderConfig:
+    """``model_type == "mpnet"`` (sentence-transformers/all-mpnet-base-v2, multi-qa-mpnet-base-*): every size from config.json.
+    The bucket function's 32 buckets and max_distance 128 are hard-coded in transformers; ``relative_attention_num_buckets`` only
+    sizes the table, and any other size is refused by name.  Embedders only: a ``*ForSequenceClassification`` is refused."""
+    from .mpnet import NUM_BUCKETS
+
+    nb = d.get("relative_attention_num_buckets", NUM_BUCKETS)
+    act = d.get("hidden_act", "gelu")
+    bad = [f"{n}={v!r}" for n, v, ok in (("relative_attention_num_buckets", nb, nb == NUM_BUCKETS),
+                                         ("hidden_act", act, act == "gelu")) if not ok]
+    if bad:
+        raise NotImplementedError(f"mpnet checkpoint with {', '.join(bad)}: the MPNet path computes the {NUM_BUCKETS}-bucket "
+                                  "relative-position bias and exact-erf GELU only")
+    archs = " ".join(d.get("architectures") or [])
+    if "ForSequenceClassification" in archs:
+        raise NotImplementedError(f"mpnet classification checkpoints are not supported (architectures={d.get('architectures')!r} "
+                                  "names a *ForSequenceClassification): MPNet cross-encoders are out of scope")
+    pad = d.get("pad_token_id", 1)
+    return EncoderConfig(
+        arch="mpnet", vocab_size=d["vocab_size"], hidden=d["hidden_size"], layers=d["num_hidden_layers"],
+        heads=d["num_attention_heads"], ffn=d["intermediate_size"], max_pos=d["max_position_embeddings"], type_vocab=1,
+        pad_id=1 if pad is None else int(pad), ln_eps=d.get("layer_norm_eps", 1e-12), num_labels=0)
+
+
 def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
     mt = d.get("model_type", "xlm-roberta")
+    if mt == "mpnet":
+        return _mpnet_config_from_hf(d)
     if mt == "gemma3_text":
         return _gemma_config_from_hf(d)
     if mt == "qwen3":
@@ -271,6 +297,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
     """-> (config, state dict, model_dir or None)."""
     mk = model_kwargs or {}
     cfg = mk.get("encoder_config") or KNOWN_CONFIGS.get(model_name)
+    if cfg is None:
+        from .mpnet import KNOWN_CONFIGS as mpnet_configs
+
+        cfg = mpnet_configs.get(model_name)
     if "state_dict" in mk:
         if cfg is None:
             raise ValueError(f"no architecture known for '{model_name}': pass model_kwargs['encoder_config']")
@@ -301,6 +331,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .gemma import synthetic_state as gemma_state
 
             return cfg, gemma_state(cfg, seed), None
+        if cfg.arch == "mpnet":
+            from .mpnet import synthetic_state as mpnet_state
+
+            return cfg, mpnet_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
