@@ -840,6 +840,70 @@ int tt_attention_relbias_f16(const void* qkv, int ld, int q_col0, int k_col0, co
                              const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
                              int max_len, const float* bias_table, void* stream);
 
+/* ---- DeBERTa-v2 / v3 cross-encoders: DebertaV2ForSequenceClassification (csrc/deberta.hip) ------------------------------------
+ * mixedbread-ai/mxbai-rerank-xsmall-v1 / -base-v1 / -large-v1, the deberta-v3 checkpoints under cross-encoder/, fine-tunes of
+ * microsoft/deberta-v3-{xsmall,small,base,large}.  The post-LN block of tt_encoder_forward (separate query / key / value / output
+ * projections with biases, concatenated to the [3H][H] layout; exact-erf GELU) with two differences: the embeddings are
+ * LayerNorm(word[id]) -- no absolute positions (position_biased_input false), no token types -- and every layer's attention is
+ * DISENTANGLED (pos_att_type c2p + p2c, share_att_key): for query q and key k of a sequence and head h, 64 wide,
+ *   i(q, k) = clamp(bucket(q - k) + span, 0, 2 span - 1),  span = position_buckets, bucket = make_log_bucket_position
+ *   score   = (Q[q] . K[k] + Q[q] . PK[i(q, k)] + K[k] . PQ[i(q, k)]) / sqrt(3 * 64),  softmax over the sequence's keys,
+ * PK / PQ = this layer's key / query projection (with bias) of LayerNorm(encoder.rel_embeddings)[0 : 2 span].  Both depend on the
+ * weights only: the caller computes them when it loads the checkpoint (pos_key / pos_query, [n_pos][H] in the element type,
+ * n_pos = 2 span), and the index as a table over the distance, so that no logarithm runs on the device:
+ *   dist_index[d + max_pos - 1] = i for d = q - k in [-(max_pos - 1), max_pos - 1]       (int32 [2 max_pos - 1], non-decreasing).
+ * Per layer one launch writes the two position score tables into the workspace in fp32,
+ *   C[t][h][w] = Q[t,h] . PK[w,h],  P[t][h][w] = K[t,h] . PQ[w,h]   (w over the indices the batch's max_len reaches),
+ * and the attention adds C[q][h][i] + P[k][h][i] to the raw score of every live pair: n_rows * heads * n_pos * 8 bytes of
+ * workspace beside the encoder's buffers.
+ * Same packed token layout as tt_encoder_forward; type_ids must be NULL; pos must be present and its values are not used.  bf16, or
+ * fp16 for the `_f16` twins.  enc.pos_emb, enc.type_emb, enc.cls_* and ffn_absmax_out are not read.  hidden a multiple of 128 and
+ * <= 1024, hidden = 64 * heads (head_dim 64), ffn a multiple of 128, n_pos a positive multiple of 4, max_pos <= 512, max_len <=
+ * max_pos, no fp8 pointer in any layer, tables that fit in size_t; anything else is refused before a launch. */
+typedef struct tt_deberta_weights {
+    tt_encoder_weights enc;        /* the encoder's tensors (pos_emb, type_emb, cls_*, ffn_absmax_out unused; enc.max_pos unused) */
+    const void* const* pos_key;    /* host array [layers]: layer l's PK, device [n_pos][H] in the element type, 16-byte aligned */
+    const void* const* pos_query;  /* host array [layers]: layer l's PQ, likewise */
+    const int32_t* dist_index;     /* device [2 max_pos - 1], see above; entries are clamped to [0, n_pos - 1] when read */
+    int32_t n_pos;                 /* 2 * position_buckets */
+    int32_t max_pos;               /* max_position_embeddings: the longest sequence */
+    /* classification head (tt_deberta_head; NULL for weights without one), all fp32 */
+    const float* pooler_dense_wt;  /* [H][H] pooler.dense.weight TRANSPOSED: [in][out] */
+    const float* pooler_dense_b;   /* [H] */
+    const float* cls_w;            /* [H] classifier.weight (one label) */
+    const float* cls_b;            /* [1] classifier.bias */
+} tt_deberta_weights;
+
+size_t tt_deberta_workspace_bytes(const tt_deberta_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state */
+int tt_deberta_forward(const tt_deberta_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* Head of DebertaV2ForSequenceClassification, one label, fp32 arithmetic, tt_modernbert_head's arguments: p = hidden[seq_start[b]]
+ * (pooling must be 0; seq_len is not read); logits[b] = classifier(GELU_erf(pooler.dense(p))), scores[b] = sigmoid(logits[b]);
+ * hidden [.][ld] in the element type (tt_deberta_forward's output); logits optional. */
+int tt_deberta_head(const tt_deberta_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
+                    int n_seq, int pooling, float* scores, float* logits, void* stream);
+/* building block (parity tests; the forward's own kernels): tt_attention_window's operands without a window, plus the position
+ * terms -- out[q][h * 64 ...] = softmax over the keys k of q's own sequence of (Q_h[q] . K_h[k] + Q_h[q] . PK_h[i] + K_h[k] . PQ_h[i])
+ * / sqrt(192), i = dist_index[q - k + max_pos - 1], applied to V_h.  pos_key / pos_query [n_pos][heads * 64] in the element type;
+ * workspace: 2 * align256(n_rows * heads * n_pos * 4) bytes, 256-byte aligned.  head_dim must be 64. */
+int tt_attention_disentangled(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                              const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                              int max_len, const void* pos_key, const void* pos_query, int n_pos, const int32_t* dist_index,
+                              int max_pos, void* workspace, size_t workspace_bytes, void* stream);
+/* the fp16 twins (deberta.hip compiled a second time) */
+size_t tt_deberta_workspace_bytes_f16(const tt_deberta_weights* w, int n_rows);
+int tt_deberta_forward_f16(const tt_deberta_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int tt_deberta_head_f16(const tt_deberta_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
+                        int n_seq, int pooling, float* scores, float* logits, void* stream);
+int tt_attention_disentangled_f16(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                                  const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                                  int max_len, const void* pos_key, const void* pos_query, int n_pos, const int32_t* dist_index,
+                                  int max_pos, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

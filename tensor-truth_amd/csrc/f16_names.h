@@ -57,3 +57,8 @@
 #define tt_mpnet_workspace_bytes tt_mpnet_workspace_bytes_f16
 #define tt_mpnet_forward tt_mpnet_forward_f16
 #define tt_attention_relbias tt_attention_relbias_f16
+// deberta.hip a second time: the DeBERTa-v2 / v3 cross-encoders in fp16
+#define tt_deberta_workspace_bytes tt_deberta_workspace_bytes_f16
+#define tt_deberta_forward tt_deberta_forward_f16
+#define tt_deberta_head tt_deberta_head_f16
+#define tt_attention_disentangled tt_attention_disentangled_f16

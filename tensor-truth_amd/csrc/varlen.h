@@ -1,5 +1,6 @@
 // What the rotary, pre-norm, packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT; gemma.hip; and,
-// for the attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias): the attention
+// for the attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias, and deberta.hip:
+// DeBERTa-v2/v3's post-LN layer with disentangled attention): the attention
 // tile over the V8 layout, the embedding gather, the gated activation, the workspace plan and the forwards' argument checks.
 // Device code sits in an anonymous namespace or is a template: one copy per translation unit and element type (common.h TT_F16).
 #pragma once
@@ -81,11 +82,17 @@ int gated_act_launch(const uint16_t* gu, uint16_t* out, int rows, int F, hipStre
 //            consecutive distances, so ONE clamp of the first distance to [-R - PAD, R + 1] leaves eight consecutive reads that
 //            give the clamped entries (all eight at tbl[0] below the range, all at tbl[2R] above it).  Dword reads: within a
 //            32-lane half the first distances 8 g - c span 24 consecutive dwords -- distinct banks, equal addresses broadcast.
+//   Disentangled (DeBERTa-v2/v3, deberta.hip): x = (s + C[query][i] + P[key][i]) * scale_log2, i = idx[query - key]: the two
+//            position terms of a live (query, key) pair, read from the fp32 score tables a launch before the attention wrote
+//            (C[t][h][w] = Q[t,h] . PK[w,h], P[t][h][w] = K[t,h] . PQ[w,h]) and added to the RAW score.  The workgroup stages the
+//            index table (distance d at d + center) in LDS once, PAD copies of the end values on either side (disent_stage): a
+//            lane's eight keys of a block are eight consecutive distances, descending, so one clamp of the first leaves eight
+//            reads that are exact wherever the distance is one a sequence can hold.  Masked pairs read nothing.
 struct NoBias {
-    static constexpr bool on = false;
+    static constexpr bool on = false, content = false;
 };
 struct RelBias {
-    static constexpr bool on = true;
+    static constexpr bool on = true, content = false;
     static constexpr int R = 128, PAD = 8, LDS_FLOATS = 2 * R + 1 + 2 * PAD;
     const float* lds;   // the staged table: lds[i] = tbl[clamp(i - PAD, 0, 2R)]
 };
@@ -93,6 +100,23 @@ struct RelBias {
 __device__ __forceinline__ void relbias_stage(const float* __restrict__ tbl, int h, float* lds) {
     for (int i = threadIdx.x; i < RelBias::LDS_FLOATS; i += blockDim.x)
         lds[i] = tbl[(size_t)h * (2 * RelBias::R + 1) + min(max(i - RelBias::PAD, 0), 2 * RelBias::R)];
+    __syncthreads();
+}
+
+struct Disentangled {
+    static constexpr bool on = false, content = true;
+    static constexpr int PAD = 8, MAX_POS = 512, LDS_INTS = 2 * MAX_POS - 1 + 2 * PAD;
+    const int32_t* idx;   // the staged index table: idx[i] = clamp(dist_index[clamp(i - PAD, 0, 2 max_pos - 2)], 0, n_pos - 1)
+    int center, idx_max;  // max_pos - 1, 2 max_pos - 2
+    const float* c;       // the head's column block of C: C + h * n_pos, rows of ld floats
+    const float* p;       // likewise of P
+    size_t ld;            // heads * n_pos
+};
+// stage the index table for Disentangled; every thread of the workgroup calls it, `lds` holds LDS_INTS ints (max_pos <= MAX_POS)
+__device__ __forceinline__ void disent_stage(const int32_t* __restrict__ dist_index, int max_pos, int n_pos, int32_t* lds) {
+    const int n = 2 * max_pos - 1;
+    for (int i = threadIdx.x; i < n + 2 * Disentangled::PAD; i += blockDim.x)
+        lds[i] = min(max(dist_index[min(max(i - Disentangled::PAD, 0), n - 1)], 0), n_pos - 1);
     __syncthreads();
 }
 
@@ -149,10 +173,26 @@ __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv,
         const float* brow = nullptr;   // RelBias: the staged entry of this lane's first key of the block
         if constexpr (Bias::on)
             brow = bias.lds + (min(max(kb + 8 * g - qrow, -Bias::R - Bias::PAD), Bias::R + 1) + Bias::R + Bias::PAD);
+        const int32_t* irow = nullptr;  // Disentangled: the staged index of this lane's first key of the block (the next keys': irow[-j])
+        const float* crow = nullptr;    //               and the C row of this lane's query
+        if constexpr (Bias::content) {
+            irow = bias.idx + (min(max(q_lim - (kb + 8 * g) + bias.center, -1), bias.idx_max + Bias::PAD) + Bias::PAD);
+            crow = bias.c + (size_t)q_lim * bias.ld;
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int key = kb + 8 * g + j;
-            float v = s[j >> 2][j & 3] * scale_log2;
+            float v;
+            if constexpr (Bias::content) {
+                float sv = s[j >> 2][j & 3];
+                if (key >= k_lo && key <= k_hi) {   // (a live key is a row of the batch and within max_pos of the query)
+                    const int i = irow[-j];
+                    sv += crow[i] + bias.p[(size_t)key * bias.ld + i];
+                }
+                v = sv * scale_log2;
+            } else {
+                v = s[j >> 2][j & 3] * scale_log2;
+            }
             if constexpr (Bias::on) v += brow[j];
             x[j] = (key >= k_lo && key <= k_hi) ? v : -INFINITY;
             bm = fmaxf(bm, x[j]);

@@ -75,6 +75,9 @@ class HipHuggingFaceEmbedding:
         cfg, state, mdir = _weights.resolve(model_name, model_kwargs, dev, want_head=False)
         _report_unused_kwargs(model_name, model_kwargs, tokenizer_kwargs, decoder=cfg.arch == "qwen3")
         self.config = cfg
+        if cfg.arch == "deberta-v2":
+            raise NotImplementedError(f"{model_name}: DeBERTa-v2 / v3 checkpoints are served as cross-encoders only "
+                                      "(HipSentenceTransformerRerank); a DebertaV2Model embedder is out of scope")
         # sentence-transformers pooling: what the checkpoint directory declares (1_Pooling/config.json), unless the caller says
         # (model_kwargs["pooling"]); "cls" for the BGE family the reference defaults to, "mean" for e5 / all-MiniLM / gte ...,
         # "last" for the decoder embedders (also when their directory declares nothing)

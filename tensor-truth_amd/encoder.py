@@ -36,7 +36,8 @@ class EncoderConfig:
     """The HF config fields the hot path reads."""
 
     # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig) | "modernbert" (modernbert.ModernBertConfig) |
-    # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig) | "mpnet" (MPNet embedders: mpnet.MpnetWeights; positions as "xlmr")
+    # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig) | "mpnet" (MPNet embedders: mpnet.MpnetWeights; positions as "xlmr") |
+    # "deberta-v2" (DeBERTa-v2 / v3 cross-encoders: deberta.DebertaConfig)
     arch: str = "xlmr"
     vocab_size: int = 250002
     hidden: int = 1024
@@ -130,7 +131,7 @@ class EncoderPath:
     rows_forward: Optional[str] = None    # decoder paths: the forward whose last layer runs for ONE row per sequence only
     rows_workspace: Optional[str] = None  # (``pooled_rows``), and its workspace size
     score: Optional[str] = None      # decoder paths: the *ForSequenceClassification score head over those rows
-    pooled_head: Optional[str] = None  # ModernBERT paths: pooling ("cls" / "mean") + classification head over the full forward
+    pooled_head: Optional[str] = None  # ModernBERT / DeBERTa paths: pooling ("cls" / "mean") + classification head over the full forward
     pool_dense: Optional[str] = None   # EmbeddingGemma path: mean pooling + the two Dense modules + L2 norm over the full forward
 
 
@@ -182,6 +183,17 @@ MPNET_FP16_PATH = EncoderPath(forward="tt_mpnet_forward_f16", workspace="tt_mpne
                               cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
                               scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
                               no_fp8="the MPNet path has no fp8 projections")
+
+# DeBERTa-v2 / v3 cross-encoders (deberta.DebertaWeights): full forward with disentangled attention; the classification head
+# (ContextPooler + classifier) reads the full forward's first rows; no CLS-only forward, no fp8.
+DEBERTA_BF16_PATH = EncoderPath(forward="tt_deberta_forward", workspace="tt_deberta_workspace_bytes", cls_forward=None,
+                                cls_workspace=None, pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc",
+                                head_scratch="head", hidden=torch.bfloat16, pooled_head="tt_deberta_head",
+                                no_fp8="the DeBERTa path has no fp8 projections")
+DEBERTA_FP16_PATH = EncoderPath(forward="tt_deberta_forward_f16", workspace="tt_deberta_workspace_bytes_f16", cls_forward=None,
+                                cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
+                                scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
+                                pooled_head="tt_deberta_head_f16", no_fp8="the DeBERTa path has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -866,11 +878,12 @@ class Encoder:
             _lib.check(rc, p.score)
             return (scores, logits) if want_logits else scores
         if p.pooled_head is not None:
-            # ModernBERT cross-encoder: the head pools the full forward's rows as the checkpoint says and scores them
+            # ModernBERT cross-encoder: the head pools the full forward's rows as the checkpoint says and scores them (a DeBERTa
+            # cross-encoder's reads the first rows: it has no ``classifier_pooling``)
             hidden, starts, lens = self.forward_packed(batch, want_lens=True)
             with torch.cuda.device(dev):
                 rc = getattr(self.lib, p.pooled_head)(ctypes.byref(self.w.struct), hidden.data_ptr(), H, starts.data_ptr(),
-                                                      lens.data_ptr(), B, 1 if self.cfg.classifier_pooling == "mean" else 0,
+                                                      lens.data_ptr(), B, 1 if getattr(self.cfg, "classifier_pooling", "cls") == "mean" else 0,
                                                       scores.data_ptr(), logits.data_ptr() if want_logits else None,
                                                       torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(rc, p.pooled_head)

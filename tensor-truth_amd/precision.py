@@ -129,6 +129,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
         return _build_gemma(cfg, state, device, mode, what)
     if getattr(cfg, "arch", "") == "mpnet":
         return _build_mpnet(cfg, state, device, mode, what)
+    if getattr(cfg, "arch", "") == "deberta-v2":
+        return _build_deberta(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
     make, desc = _implementations()[impl]
     w = make(cfg, state, device)
@@ -217,4 +219,23 @@ def _build_mpnet(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, st
     w = MpnetWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
     desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
     logger.info("%s: MPNet encoder, precision = %s", what, desc)
+    return w, Encoder(w), desc
+
+
+def _build_deberta(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """DeBERTa-v2 / v3 cross-encoders: bf16 or fp16, resolved as for the MPNet encoders.  The reference precision (fp32 semantics,
+    what no torch_dtype means for the XLM-R / BERT family) has no DeBERTa implementation: refused, never computed in another
+    precision behind the caller's back."""
+    import torch
+
+    from .deberta import DebertaWeights
+    from .encoder import Encoder
+
+    if mode not in ("bf16", "fp16"):
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for DeBERTa encoders; pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}} or {{'torch_dtype': 'float16'}}")
+    w = DebertaWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
+    desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
+    logger.info("%s: DeBERTa encoder, precision = %s", what, desc)
     return w, Encoder(w), desc

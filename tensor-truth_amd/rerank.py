@@ -13,6 +13,9 @@ pair template decides the special tokens, and scored at the token transformers p
 ``model_kwargs["query_template"]`` / ``["document_template"]`` (``str.format`` with ``{query}`` / ``{document}``) wrap the two
 sides before tokenisation -- the chat-style prompt of the Qwen3-Reranker model card, which ``SentenceTransformerRerank`` does not
 apply by itself; default: none, the strings as the reference passes them.
+
+DeBERTa-v2 / v3 cross-encoders (a ``DebertaV2ForSequenceClassification`` directory, e.g. mixedbread-ai/mxbai-rerank-base-v1; bf16 or
+fp16, named the same way): pairs are laid out by the checkpoint's own tokenizer, ``[CLS] A [SEP] B [SEP]`` with one token type.
 """
 from __future__ import annotations
 
@@ -238,10 +241,11 @@ class HipSentenceTransformerRerank:
         """Would ids made by the tokenizer ``signature`` (with ``instruction`` prepended to the text) be THIS model's ids?"""
         from .tokenization import tokenizer_signature
 
-        if self.config.arch in ("qwen3", "modernbert") or self.query_template is not None or self.document_template is not None:
+        if (self.config.arch in ("qwen3", "modernbert", "deberta-v2") or self.query_template is not None
+                or self.document_template is not None):
             # stored ids are laid out by tokenization.SpecialTokens, which knows the XLM-R and BERT pair layouts only: a decoder
-            # (or ModernBERT) reranker's layout is its tokenizer's template (and a text template changes the passage's tokens): pairs
-            # come from text
+            # (or ModernBERT, or DeBERTa) reranker's layout is its tokenizer's template (and a text template changes the passage's
+            # tokens): pairs come from text
             return False
         return not self._use_types and not instruction and signature == tokenizer_signature(self._tokenizer)
 

@@ -121,6 +121,9 @@ class SpecialTokens:
         if arch in ("xlmr", "mpnet"):      # MPNet: <s> 0, <pad> 1, </s> 2, <unk> 3 and the pair <s> A </s></s> B </s> too
             self.bos, self.pad, self.eos, self.unk, self.first_free = 0, 1, 2, 3, 4
             self.pair_sep = [2, 2]          # <s> A </s></s> B </s>
+        elif arch == "deberta-v2":         # the DeBERTa-v2 / v3 sentencepiece vocabulary: [PAD] 0, [CLS] 1, [SEP] 2, [UNK] 3
+            self.bos, self.pad, self.eos, self.unk, self.first_free = 1, 0, 2, 3, 4
+            self.pair_sep = [2]             # [CLS] A [SEP] B [SEP]
         else:
             self.bos, self.pad, self.eos, self.unk, self.first_free = 101, 0, 102, 100, 1000
             self.pair_sep = [102]           # [CLS] A [SEP] B [SEP]
@@ -180,7 +183,7 @@ class HashTokenizer:
         na, nb = truncate_longest_first(len(ia), len(ib), max(budget, 0))      # (the Rust library's rule: one definition for both tokenizers)
         ia, ib = ia[:na], ib[:nb]
         ids = [self.sp.bos] + ia + self.sp.pair_sep + ib + [self.sp.eos]
-        one_type = self.arch in ("xlmr", "mpnet")
+        one_type = self.arch in ("xlmr", "mpnet", "deberta-v2")      # (DeBERTa-v3 checkpoints: type_vocab_size 0)
         n_a = 1 + len(ia) + (1 if not one_type else len(self.sp.pair_sep))
         types = [0] * n_a + [1] * (len(ids) - n_a) if not one_type else [0] * len(ids)
         return ids, types
@@ -251,7 +254,7 @@ class HFTokenizer:
 
     def encode_pair_batch(self, pairs: Sequence[Tuple[str, str]], max_length: int = 512):
         encs = self._batch(self._pairs(max_length), [(a, b) for a, b in pairs])
-        if self.arch in ("xlmr", "qwen3", "modernbert"):
+        if self.arch in ("xlmr", "qwen3", "modernbert", "deberta-v2"):
             # XLM-R (and a decoder or ModernBERT reranker) has ONE token type (type_vocab 1): the segment ids are all zero and no caller reads them -- building 400 x 292
             # more Python ints per rerank batch under the GIL is a third of this call
             return [(enc.ids, None) for enc in encs]
@@ -268,7 +271,7 @@ def load_tokenizer(model_dir: Optional[str], arch: str, vocab_size: int):
     tj = os.path.join(model_dir, "tokenizer.json")
     if os.path.exists(tj):
         return HFTokenizer(tj, arch)
-    slow_files = ("sentencepiece.bpe.model", "spiece.model", "tokenizer.model", "vocab.txt")
+    slow_files = ("sentencepiece.bpe.model", "spiece.model", "spm.model", "tokenizer.model", "vocab.txt")     # (spm.model: DeBERTa-v3)
     if any(os.path.exists(os.path.join(model_dir, f)) for f in slow_files):
         try:
             from transformers import AutoTokenizer

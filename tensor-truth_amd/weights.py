@@ -177,10 +177,69 @@ def _mpnet_config_from_hf(d: dict) -> EncoderConfig:
         pad_id=1 if pad is None else int(pad), ln_eps=d.get("layer_norm_eps", 1e-12), num_labels=0)
 
 
+def _deberta_config_from_hf(d: dict) -> EncoderConfig:
+    """``model_type == "deberta-v2"`` (DebertaV2ForSequenceClassification: mixedbread-ai/mxbai-rerank-*-v1, the deberta-v3 checkpoints
+    under cross-encoder/, fine-tunes of microsoft/deberta-v3-*): every size from config.json.  The kernels compute the v3 form of the
+    disentangled attention -- c2p + p2c with shared projections, log buckets, normalised relative embeddings, no absolute positions,
+    no token types, no convolution; every other variant of the architecture is refused by field name, never run as that form."""
+    from .deberta import DebertaConfig
+
+    pat = d.get("pos_att_type")
+    if isinstance(pat, str):
+        pat = [x.strip() for x in pat.lower().split("|") if x.strip()]
+    pat = sorted(str(x).lower() for x in (pat or []))
+    hidden, heads = d["hidden_size"], d["num_attention_heads"]
+    max_pos = d["max_position_embeddings"]
+    mrp = d.get("max_relative_positions", -1)
+    mrp = max_pos if mrp is None or mrp < 1 else int(mrp)
+    buckets = d.get("position_buckets", -1)
+    norm = str(d.get("norm_rel_ebd", "none")).lower()
+    emb = d.get("embedding_size") or hidden
+    pool = d.get("pooler_hidden_size") or hidden
+    act, pact = d.get("hidden_act", "gelu"), d.get("pooler_hidden_act", "gelu")
+    bad = [f"{n}={v!r}" for n, v, ok in (
+        ("relative_attention", d.get("relative_attention", False), d.get("relative_attention", False) is True),
+        ("pos_att_type", d.get("pos_att_type"), pat == ["c2p", "p2c"]),
+        ("share_att_key", d.get("share_att_key", False), d.get("share_att_key", False) is True),
+        ("norm_rel_ebd", d.get("norm_rel_ebd", "none"), norm == "layer_norm"),
+        ("position_biased_input", d.get("position_biased_input", True), d.get("position_biased_input", True) is False),
+        ("type_vocab_size", d.get("type_vocab_size", 0), not d.get("type_vocab_size", 0)),
+        ("conv_kernel_size", d.get("conv_kernel_size", 0), not (d.get("conv_kernel_size") or 0) > 0),
+        ("embedding_size", emb, emb == hidden),
+        ("pooler_hidden_size", pool, pool == hidden),
+        ("pooler_hidden_act", pact, pact == "gelu"),
+        ("hidden_act", act, act == "gelu"),
+        ("position_buckets", buckets, isinstance(buckets, int) and buckets > 0),
+        ("max_relative_positions", d.get("max_relative_positions", -1), mrp <= max_pos)) if not ok]
+    if bad:
+        raise NotImplementedError(f"deberta-v2 checkpoint with {', '.join(bad)}: the DeBERTa path computes the v3 disentangled "
+                                  "attention only (relative_attention with pos_att_type c2p|p2c, share_att_key, norm_rel_ebd "
+                                  "layer_norm, position_buckets > 0, no position_biased_input, no token types, no convolution, "
+                                  "exact-erf GELU)")
+    if heads <= 0 or hidden != 64 * heads or hidden % 128 or hidden > 1024:
+        raise NotImplementedError(f"deberta-v2 checkpoint with hidden_size={hidden}, num_attention_heads={heads}: head_dim must be 64 "
+                                  "and hidden_size a multiple of 128 up to 1024")
+    num_labels = 0
+    if "ForSequenceClassification" in " ".join(d.get("architectures") or []):
+        n = d.get("num_labels") or (len(d["id2label"]) if d.get("id2label") else 1)
+        if n != 1:
+            raise NotImplementedError(f"deberta-v2 classification checkpoint with num_labels={n}: only single-label (sigmoid) "
+                                      "cross-encoder heads are supported")
+        num_labels = 1
+    pad = d.get("pad_token_id", 0)
+    vocab = d["vocab_size"]
+    return DebertaConfig(
+        arch="deberta-v2", vocab_size=vocab, hidden=hidden, layers=d["num_hidden_layers"], heads=heads, ffn=d["intermediate_size"],
+        max_pos=max_pos, type_vocab=1, pad_id=int(pad) if pad is not None and 0 <= int(pad) < vocab else 0,
+        ln_eps=d.get("layer_norm_eps", 1e-7), num_labels=num_labels, position_buckets=int(buckets), max_relative_positions=mrp)
+
+
 def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
     mt = d.get("model_type", "xlm-roberta")
     if mt == "mpnet":
         return _mpnet_config_from_hf(d)
+    if mt == "deberta-v2":
+        return _deberta_config_from_hf(d)
     if mt == "gemma3_text":
         return _gemma_config_from_hf(d)
     if mt == "qwen3":
@@ -301,6 +360,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
         from .mpnet import KNOWN_CONFIGS as mpnet_configs
 
         cfg = mpnet_configs.get(model_name)
+    if cfg is None:
+        from .deberta import KNOWN_CONFIGS as deberta_configs
+
+        cfg = deberta_configs.get(model_name)
     if "state_dict" in mk:
         if cfg is None:
             raise ValueError(f"no architecture known for '{model_name}': pass model_kwargs['encoder_config']")
@@ -335,6 +398,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .mpnet import synthetic_state as mpnet_state
 
             return cfg, mpnet_state(cfg, seed), None
+        if cfg.arch == "deberta-v2":
+            from .deberta import synthetic_state as deberta_state
+
+            return cfg, deberta_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
