@@ -904,6 +904,58 @@ int tt_attention_disentangled_f16(const void* qkv, int ld, int q_col0, int k_col
                                   int max_len, const void* pos_key, const void* pos_query, int n_pos, const int32_t* dist_index,
                                   int max_pos, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- RoPE-BERT encoders: post-LN BERT blocks with rotary positions (csrc/ropebert.hip) ------------------------------------------
+ * NomicBertModel (nomic-ai/nomic-embed-text-v1 / -v1.5) and JinaEmbeddingsV3Model (jina-embeddings-v3 in its transformers format),
+ * one layer class in transformers.  No position table; q and k rotated by rotate-half RoPE with one base for every layer
+ * (positions 0-based within each sequence, angles in fp32); bidirectional attention over the sequence's own tokens:
+ *   h = LayerNorm(word[ids] + type[0]; emb_ln);  per layer
+ *   q | k | v = h Wqkv^T (+ b_qkv) -> RoPE(q), RoPE(k) -> a = softmax(q k^T / 8) v -> h = LayerNorm(h + a Wo^T (+ b_o); ln1)
+ *   mlp_kind 1 (SwiGLU, NomicBERT): m = (SiLU(h Wgate^T) * (h Wup^T)) Wdown^T                    -- no biases
+ *   mlp_kind 0 (GELU, Jina):        m = GELU_erf(h W1^T + b1) W2^T + b2
+ *   h = LayerNorm(h + m; ln2);  no final norm.
+ * Same packed token layout as tt_encoder_forward (`pos` = position within the sequence; type_ids must be NULL: every token of an
+ * embedder call is of type 0, whose row is still added), the same projections (the 16-bit GEMMs) and LayerNorms, tt_rope_v8 and
+ * the attention kernel of tt_attention_varlen at every length; bf16 -- or fp16 for the `_f16` twins.  Matrices [out][in] in the
+ * element type, norms and biases fp32; a NULL bias pointer means no bias.  hidden a multiple of 128 and <= 1024, hidden = 64 *
+ * heads (head_dim 64), ffn a multiple of 64 (of 128 with mlp_kind 0, whose up-projection is ffn columns wide), mlp_kind 0 or 1;
+ * anything else is refused before a launch. */
+typedef struct tt_ropebert_layer_weights {
+    const void* qkv_w;        /* [3H][H]: q_proj, k_proj, v_proj rows concatenated */
+    const float* qkv_b;       /* [3H] or NULL */
+    const void* o_w;          /* [H][H] self_attn.o_proj */
+    const float* o_b;         /* [H] or NULL */
+    const float* ln1_g;       /* [H] post_attention_layernorm */
+    const float* ln1_b;
+    const void* up_w;         /* mlp_kind 1: [2F][H], gate_proj rows then up_proj rows; mlp_kind 0: [F][H] mlp.fc1 */
+    const float* up_b;        /* mlp_kind 0: [F] or NULL; mlp_kind 1: NULL */
+    const void* down_w;       /* [H][F] down_proj / mlp.fc2 */
+    const float* down_b;      /* mlp_kind 0: [H] or NULL; mlp_kind 1: NULL */
+    const float* ln2_g;       /* [H] post_mlp_layernorm */
+    const float* ln2_b;
+} tt_ropebert_layer_weights;
+
+typedef struct tt_ropebert_weights {
+    int32_t hidden, layers, heads, ffn, vocab, type_vocab;
+    int32_t mlp_kind;         /* 0: GELU_erf(fc1) fc2 with biases; 1: SwiGLU without */
+    float ln_eps, rope_theta;
+    const void* word_emb;     /* [vocab][H] */
+    const void* type_emb;     /* [type_vocab][H]; row 0 is added to every token */
+    const float* emb_ln_g;    /* [H] embeddings.LayerNorm */
+    const float* emb_ln_b;
+    const tt_ropebert_layer_weights* layer; /* host array [layers] */
+} tt_ropebert_weights;
+
+size_t tt_ropebert_workspace_bytes(const tt_ropebert_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state */
+int tt_ropebert_forward(const tt_ropebert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* the fp16 twins (ropebert.hip compiled a second time) */
+size_t tt_ropebert_workspace_bytes_f16(const tt_ropebert_weights* w, int n_rows);
+int tt_ropebert_forward_f16(const tt_ropebert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

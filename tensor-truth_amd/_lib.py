@@ -250,6 +250,13 @@ SIGNATURES = {
     "tt_deberta_head_f16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_attention_disentangled_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
         c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    # RoPE-BERT encoders: NomicBERT, Jina-v3 (csrc/ropebert.hip) and their fp16 twins (same signatures)
+    "tt_ropebert_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "tt_ropebert_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_ropebert_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
+    "tt_ropebert_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

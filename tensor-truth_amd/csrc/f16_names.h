@@ -62,3 +62,6 @@
 #define tt_deberta_forward tt_deberta_forward_f16
 #define tt_deberta_head tt_deberta_head_f16
 #define tt_attention_disentangled tt_attention_disentangled_f16
+// ropebert.hip a second time: the NomicBERT / Jina-v3 encoders in fp16
+#define tt_ropebert_workspace_bytes tt_ropebert_workspace_bytes_f16
+#define tt_ropebert_forward tt_ropebert_forward_f16

@@ -38,6 +38,7 @@ class EncoderConfig:
     # "xlmr" | "bert" | "qwen3" (decoder embedder: decoder.DecoderConfig) | "modernbert" (modernbert.ModernBertConfig) |
     # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig) | "mpnet" (MPNet embedders: mpnet.MpnetWeights; positions as "xlmr") |
     # "deberta-v2" (DeBERTa-v2 / v3 cross-encoders: deberta.DebertaConfig)
+    # "nomic_bert" | "jina_embeddings_v3" (post-LN encoders with RoPE: ropebert.RopeBertConfig; positions 0-based)
     arch: str = "xlmr"
     vocab_size: int = 250002
     hidden: int = 1024
@@ -194,6 +195,16 @@ DEBERTA_FP16_PATH = EncoderPath(forward="tt_deberta_forward_f16", workspace="tt_
                                 cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
                                 scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
                                 pooled_head="tt_deberta_head_f16", no_fp8="the DeBERTa path has no fp8 projections")
+
+# NomicBERT / Jina-v3 embedders (ropebert.RopeBertWeights): post-LN layers with RoPE; first-token and mean pooling with the
+# encoder's kernels; no CLS-only forward, no head, no fp8.
+ROPEBERT_BF16_PATH = EncoderPath(forward="tt_ropebert_forward", workspace="tt_ropebert_workspace_bytes", cls_forward=None,
+                                 cls_workspace=None, pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc",
+                                 head_scratch="head", hidden=torch.bfloat16, no_fp8="the NomicBERT / Jina-v3 path has no fp8 projections")
+ROPEBERT_FP16_PATH = EncoderPath(forward="tt_ropebert_forward_f16", workspace="tt_ropebert_workspace_bytes_f16", cls_forward=None,
+                                 cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
+                                 scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
+                                 no_fp8="the NomicBERT / Jina-v3 path has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -246,6 +246,10 @@ def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
         return _decoder_config_from_hf(d)
     if mt == "modernbert":
         return _modernbert_config_from_hf(d)
+    if mt in ("nomic_bert", "jina_embeddings_v3"):
+        from .ropebert import config_from_hf as ropebert_config_from_hf
+
+        return ropebert_config_from_hf(d)
     arch = "bert" if mt == "bert" else "xlmr"
     archs = " ".join(d.get("architectures", []))
     num_labels = 1 if "SequenceClassification" in archs else num_labels_default
@@ -372,6 +376,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
     if mdir is not None:
         with open(os.path.join(mdir, "config.json")) as f:
             cfg = _config_from_hf(json.load(f), 1 if want_head else 0)
+        if want_head and cfg.arch in ("nomic_bert", "jina_embeddings_v3"):
+            # (HipSentenceTransformerRerank's loader: refused before the weights are read)
+            raise ValueError(f"'{model_name}': {cfg.arch} checkpoints are served as embedders only (HipHuggingFaceEmbedding); "
+                             "a *ForSequenceClassification head of this type is not supported -- no such cross-encoder is published")
         state = load_state(mdir)
         if cfg.arch == "gemma3_text" and not want_head:
             from .gemma import dense_modules
@@ -402,6 +410,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .deberta import synthetic_state as deberta_state
 
             return cfg, deberta_state(cfg, seed), None
+        if cfg.arch in ("nomic_bert", "jina_embeddings_v3"):
+            from .ropebert import synthetic_state as ropebert_state
+
+            return cfg, ropebert_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
