@@ -277,7 +277,7 @@ int tt_adjacent_cosine(const float* emb_f32, int n, int hidden, float* out_dist,
 /* tt_gemm_bf16: m, n multiples of 128 and k of 64 (tiled kernels), or m a multiple of 64 up to 256 with n % 16 == 0 and
  * k % 32 == 0 (weight-streaming skinny kernel; same bits as the tiled kernels for the same rows). */
 int tt_gemm_bf16(const void* a, const void* w, const float* bias, const void* residual, void* c,
-                 int m, int n, int k, int epilogue /*0 bias,1 gelu,2 +residual,3 tanh*/, void* stream);
+                 int m, int n, int k, int epilogue /*0 bias,1 gelu,2 +residual,3 tanh,7 relu*/, void* stream);
 int tt_layernorm_bf16(const void* in, void* out, const float* gamma, const float* beta, int rows, int hidden,
                       float eps, void* stream);
 int tt_attention_varlen(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,
@@ -955,6 +955,67 @@ size_t tt_ropebert_workspace_bytes_f16(const tt_ropebert_weights* w, int n_rows)
 int tt_ropebert_forward_f16(const tt_ropebert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                             const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- T5 encoders: T5EncoderModel embedders (csrc/t5.hip) ------------------------------------------------------------------------
+ * sentence-transformers/sentence-t5-base / -large, gtr-t5-base / -large, hkunlp/instructor-base / -large (model_type "t5",
+ * transformers/models/t5/modeling_t5.py).  Pre-norm blocks without biases; norm(v; w) = bf16(v * rsqrt(mean(v^2) + eps)) * w
+ * (T5LayerNorm: no mean subtraction, fp32 statistics, rounded to the element type BEFORE the weight multiplies):
+ *   h = embed[ids]                                           no scaling, no LayerNorm, no position table, no token types
+ *   x = norm(h; ln_attn) -> q | k | v = x Wqkv^T -> a = softmax(q . k + rel_bias[bucket(key - query)][head]) v -> h = h + a Wo^T
+ *   x = norm(h; ln_ffn)  -> mlp_kind 0 (feed_forward_proj "relu"):        h = h + relu(x wi^T) wo^T
+ *                           mlp_kind 1 ("gated-gelu", T5 v1.1 / flan):    h = h + (gelu_new(x wi_0^T) * (x wi_1^T)) wo^T
+ *   hidden_out = norm(h; final_norm)
+ * T5 does NOT divide the scores by sqrt(d_kv).  The attention is tt_attention_relbias, which computes q . k / 8 + table: THE Q
+ * ROWS OF qkv_w (its first d_model rows) ARE STORED PRE-SCALED BY 8 -- a shift of the exponent, exact in bf16, and x (8 W)^T =
+ * 8 (x W^T) bit for bit.  The bias table [32 buckets][heads] belongs to block 0 and is added in every block; the bucket function
+ * (32 buckets, max_distance 128, bidirectional, key - query) is MPNet's, so bias_table is built the same way:
+ *   bias_table[h][d + 128] = rel_bias[bucket(d)][h] * log2(e),  d = key - query in [-128, 128]      ([heads][257] fp32).
+ * The ReLU sits in the up-projection's GEMM epilogue (tt_gemm_bf16 epilogue 7): no extra pass over [T][d_ff].
+ * Same packed token layout as tt_encoder_forward; `pos` must be present and its values are not used; type_ids must be NULL.
+ * Sequences up to 512 tokens, as for MPNet.  bf16 only: the FFN activations leave fp16's range (transformers' fp16 run clamps
+ * them, which is another model), so there are no `_f16` twins.  Matrices [out][in] in bf16, norm weights fp32.
+ * d_model a multiple of 128 and <= 1024, d_kv = 64 and heads * 64 = d_model, d_ff a multiple of 128, num_buckets = 32,
+ * max_distance = 128, mlp_kind 0 or 1, dense_out (with dense_wt) a multiple of 128 and <= 1024; anything else is refused before a
+ * launch with the field named. */
+typedef struct tt_t5_layer_weights {
+    const float* ln_attn;     /* [d_model] layer.0.layer_norm */
+    const void* qkv_w;        /* [3 d_model][d_model]: q rows TIMES 8, then k rows, then v rows */
+    const void* o_w;          /* [d_model][d_model] SelfAttention.o */
+    const float* ln_ffn;      /* [d_model] layer.1.layer_norm */
+    const void* wi;           /* mlp_kind 0: [d_ff][d_model] DenseReluDense.wi; mlp_kind 1: [2 d_ff][d_model], wi_0 rows then wi_1 rows */
+    const void* wo;           /* [d_model][d_ff] DenseReluDense.wo */
+} tt_t5_layer_weights;
+
+typedef struct tt_t5_weights {
+    int32_t d_model, layers, heads, d_kv, d_ff, vocab;
+    int32_t mlp_kind;         /* 0: relu; 1: gated-gelu (gelu_new) */
+    int32_t num_buckets;      /* relative_attention_num_buckets: 32 */
+    int32_t max_distance;     /* relative_attention_max_distance: 128 */
+    float eps;                /* layer_norm_epsilon */
+    const void* embed;        /* [vocab][d_model] shared */
+    const tt_t5_layer_weights* layer; /* host array [layers] */
+    const float* final_norm;  /* [d_model] encoder.final_layer_norm */
+    const float* rel_bias;    /* [32][heads] fp32: block 0's relative_attention_bias.weight as the checkpoint stores it -- what
+                                 bias_table was built from; must be present, the kernels read bias_table */
+    const float* bias_table;  /* [heads][257] fp32, see above */
+    /* the sentence-transformers Dense module behind the pooling (tt_t5_pool_dense), fp32, no bias, identity activation */
+    int32_t dense_out;        /* 0 with dense_wt NULL: the checkpoint has no Dense module */
+    const float* dense_wt;    /* [d_model][dense_out]: 2_Dense linear.weight TRANSPOSED ([in][out]); NULL: none */
+} tt_t5_weights;
+
+size_t tt_t5_workspace_bytes(const tt_t5_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][d_model] last hidden state (after the final norm) */
+int tt_t5_forward(const tt_t5_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                  const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* sentence-transformers Pooling(mean) -> Dense (if any) -> Normalize in fp32: p = the mean of the rows seq_start[b] ..
+ * seq_start[b] + seq_len[b] - 1 of hidden [.][ld] bf16 (tt_t5_forward's output), summed in ascending order -- any sub-range of a
+ * sequence (INSTRUCTOR's include_prompt false: the rows behind the instruction), any row alignment; v = p dense^T, or p itself
+ * without a Dense module; out_f32[b] = v / max(||v||, 1e-12), [n_seq][dense_out or d_model]; out_16 (optional) the same vector in
+ * bf16 (ready to be a scan query).  A workgroup handles eight sequences, so the matrix is read once per eight; a sequence's vector
+ * does not depend on the batch it travels in. */
+int tt_t5_pool_dense(const tt_t5_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
+                     int n_seq, float* out_f32, void* out_16, void* stream);
 
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the

@@ -257,6 +257,11 @@ SIGNATURES = {
     "tt_ropebert_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
     "tt_ropebert_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    # T5 encoders (csrc/t5.hip): bf16 only, no twins
+    "tt_t5_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "tt_t5_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_t5_pool_dense": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

@@ -5,7 +5,8 @@
 enum { TT_EPI_BIAS = 0, TT_EPI_GELU = 1, TT_EPI_RESIDUAL = 2, TT_EPI_TANH = 3, TT_EPI_QKV = 4,
        TT_EPI_VT = 5 /* internal: whole output stored transposed into vt (the V third of a QKV projection) */,
        TT_EPI_SCAN = 6 /* internal: similarity scan -- A = corpus rows, W = 256 queries, nothing is stored: scores >= the
-                          query's threshold (bias[n]) are appended to per-query candidate lists (scan_api.hip) */ };
+                          query's threshold (bias[n]) are appended to per-query candidate lists (scan_api.hip) */,
+       TT_EPI_RELU = 7 /* max(acc + bias, 0): the up-projection of a ReLU MLP (T5 encoders, t5.hip) */ };
 
 struct GemmParams {
     const uint16_t* A;        // [M][lda] bf16

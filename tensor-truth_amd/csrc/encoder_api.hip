@@ -353,7 +353,7 @@ int tt_adjacent_cosine(const float* emb_f32, int n, int hidden, float* out_dist,
 #endif
 int tt_gemm_bf16(const void* a, const void* w, const float* bias, const void* residual, void* c, int m, int n,
                  int k, int epilogue, void* stream) {
-    TT_CHECK_ARG(epilogue >= TT_EPI_BIAS && epilogue <= TT_EPI_TANH, "epilogue %d", epilogue);
+    TT_CHECK_ARG((epilogue >= TT_EPI_BIAS && epilogue <= TT_EPI_TANH) || epilogue == TT_EPI_RELU, "epilogue %d", epilogue);
     GemmParams g{};
     g.A = (const uint16_t*)a; g.lda = k; g.W = (const uint16_t*)w; g.bias = bias;
     g.residual = (const uint16_t*)residual; g.ldr = n; g.C = (uint16_t*)c; g.ldc = n;

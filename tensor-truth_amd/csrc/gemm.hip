@@ -69,6 +69,8 @@ __device__ __forceinline__ void gemm_epilogue_tile(const GemmParams& p, f32x4 (&
                 v0 = gelu_erf(v0); v1 = gelu_erf(v1); v2 = gelu_erf(v2); v3 = gelu_erf(v3);
             } else if constexpr (EPI == TT_EPI_TANH) {
                 v0 = tanhf(v0); v1 = tanhf(v1); v2 = tanhf(v2); v3 = tanhf(v3);
+            } else if constexpr (EPI == TT_EPI_RELU) {
+                v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f);
             } else if constexpr (EPI == TT_EPI_RESIDUAL) {
                 const uint2 r = *reinterpret_cast<const uint2*>(p.residual + (size_t)m * p.ldr + n);
                 v0 += elo(r.x);
@@ -163,6 +165,9 @@ __device__ __forceinline__ void gemm_epilogue_wide(const GemmParams& p, f32x4 (&
             } else if constexpr (EPI == TT_EPI_TANH) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = tanhf(v[k]);
+            } else if constexpr (EPI == TT_EPI_RELU) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
             } else if constexpr (EPI == TT_EPI_RESIDUAL) {
                 const uint4 r = *reinterpret_cast<const uint4*>(p.residual + (size_t)m * p.ldr + n);
                 v[0] += elo(r.x); v[1] += ehi(r.x);
@@ -595,6 +600,9 @@ __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2
                     } else if constexpr (EPI == TT_EPI_TANH) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k) v[k] = tanhf(v[k]);
+                    } else if constexpr (EPI == TT_EPI_RELU) {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
                     } else if constexpr (EPI == TT_EPI_RESIDUAL) {
                         const u32x4 r = res[qn][nt];
 #if TT_DIAG
@@ -2670,6 +2678,7 @@ int tt_gemm_launch(const GemmParams& p, int epilogue, hipStream_t st) {
                 if (!p.residual || p.ldr % 4) { tt_set_error("gemm: residual epilogue without residual"); return TT_E_INVALID; }
                 return launch_skinny<TT_EPI_RESIDUAL>(p, st);
             case TT_EPI_TANH: return launch_skinny<TT_EPI_TANH>(p, st);
+            case TT_EPI_RELU: return launch_skinny<TT_EPI_RELU>(p, st);
             case TT_EPI_QKV:
                 if (!p.vt || p.vt_col0 % 16) { tt_set_error("gemm: qkv epilogue without vt"); return TT_E_INVALID; }
                 return launch_skinny<TT_EPI_QKV>(p, st);
@@ -2687,6 +2696,8 @@ int tt_gemm_launch(const GemmParams& p, int epilogue, hipStream_t st) {
             if (!p.residual) { tt_set_error("gemm: residual epilogue without residual"); return TT_E_INVALID; }
             return launch<TT_EPI_RESIDUAL>(p, st);
         case TT_EPI_TANH: return launch<TT_EPI_TANH>(p, st);
+        // (ReLU is a bias-grade epilogue: store-bound, so it takes the one-tile kernel's whole-line stores like TT_EPI_BIAS)
+        case TT_EPI_RELU: return launch<TT_EPI_RELU>(p, st);
         case TT_EPI_QKV: {
             if (!p.vt) { tt_set_error("gemm: qkv epilogue without vt"); return TT_E_INVALID; }
             static const int variant = TT_DIAG_ENV_INT("TT_GEMM_VARIANT", 5);

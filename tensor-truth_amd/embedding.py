@@ -82,7 +82,7 @@ class HipHuggingFaceEmbedding:
         # (model_kwargs["pooling"]); "cls" for the BGE family the reference defaults to, "mean" for e5 / all-MiniLM / gte ...,
         # "last" for the decoder embedders (also when their directory declares nothing)
         default_pooling = {"qwen3": "last", "gemma3_text": "mean", "nomic_bert": "mean",
-                           "jina_embeddings_v3": "mean"}.get(cfg.arch, "cls")
+                           "jina_embeddings_v3": "mean", "t5": "mean"}.get(cfg.arch, "cls")
         pooling = (model_kwargs or {}).get("pooling") or _weights.pooling_mode(mdir, default_pooling)
         pooling = {"cls_token": "cls", "mean_tokens": "mean", "lasttoken": "last"}.get(pooling, pooling)
         if pooling not in ("cls", "mean", "last") or (pooling == "last" and cfg.arch != "qwen3"):
@@ -93,6 +93,9 @@ class HipHuggingFaceEmbedding:
         if cfg.arch == "gemma3_text" and pooling != "mean":
             raise NotImplementedError(f"{model_name}: pooling '{pooling}': an EmbeddingGemma checkpoint pools the mean (its Dense "
                                       f"modules follow it)")
+        if cfg.arch == "t5" and pooling != "mean":
+            raise NotImplementedError(f"{model_name}: pooling '{pooling}': a T5 encoder checkpoint pools the mean (its Dense "
+                                      f"module follows it)")
         self.pooling = pooling
         # precision.resolve(): model_kwargs (torch_dtype float32 = the reference's own default, config_schema.py:66-76),
         # ModelManager.precision, TT_PRECISION; default: the reference's fp32 semantics.  (`_model.parameters()` is read by the memory accounting.)
@@ -101,6 +104,14 @@ class HipHuggingFaceEmbedding:
         self.embed_dim = getattr(self._model, "out_dim", cfg.hidden)
         self._tokenizer = (model_kwargs or {}).get("tokenizer") or load_tokenizer(mdir, cfg.arch, cfg.vocab_size)
         self.max_length = min(max_length or cfg.max_seq_len, cfg.max_seq_len)
+        # INSTRUCTOR's Pooling setting ``include_prompt: false``: the instruction's tokens stay out of the mean (T5 path only)
+        self.include_prompt = True
+        if cfg.arch == "t5":
+            from . import t5 as _t5
+
+            # the checkpoint's own limit (sentence_bert_config.json: 256 for sentence-t5, 512 for gtr-t5 and INSTRUCTOR)
+            self.max_length = min(max_length or _t5.max_seq_length(mdir), cfg.max_seq_len)
+            self.include_prompt = _t5.include_prompt(mdir)
         self.query_instruction = query_instruction_for(model_name) if query_instruction is None else query_instruction
         self.text_instruction = text_instruction or ""
         if cfg.arch in ("modernbert", "gemma3_text", "nomic_bert", "jina_embeddings_v3"):
@@ -133,8 +144,9 @@ class HipHuggingFaceEmbedding:
         self.stats = {"sequences": 0, "tokens": 0, "sum_len_sq": 0}
 
     # ---- token-id level (what the kernels see) ------------------------------------------------
-    def embed_token_batches(self, seqs: Sequence[Sequence[int]]) -> torch.Tensor:
-        """Embeds tokenised sequences -> fp32 [n, H] on the device, original order."""
+    def embed_token_batches(self, seqs: Sequence[Sequence[int]], skip: int = 0) -> torch.Tensor:
+        """Embeds tokenised sequences -> fp32 [n, H] on the device, original order.  ``skip``: the leading tokens of every
+        sequence (its instruction) that stay out of the mean (``include_prompt: false``, T5 path)."""
         order = sorted(range(len(seqs)), key=lambda i: -len(seqs[i]))
         parts = []
         lo = 0
@@ -149,7 +161,7 @@ class HipHuggingFaceEmbedding:
             self.stats["tokens"] += sum(lens)
             self.stats["sum_len_sq"] += sum(n * n for n in lens)
             emb, _ = self._encoder.embed_packed(pack_tokens([seqs[i] for i in sel], self.config, None, self.max_length),
-                                                pooling=self.pooling)
+                                                pooling=self.pooling, **({"skip": skip} if skip else {}))
             parts.append(emb)
             lo = hi
         out = torch.empty((len(seqs), self.embed_dim), dtype=torch.float32, device=self.device)
@@ -205,8 +217,13 @@ class HipHuggingFaceEmbedding:
         formed inside a window (sorted by length, ``embed_batch_size`` each); results do not depend on the
         batching (tests/test_configs_gpu.py)."""
         n, win = len(texts), self.pipeline_window
+        skip = 0
+        if not self.include_prompt and prefix:
+            from .t5 import prompt_tokens
+
+            skip = prompt_tokens(self._tokenizer, prefix)
         if n <= win:
-            return self.embed_token_batches(self._tokenize(texts, prefix))
+            return self.embed_token_batches(self._tokenize(texts, prefix), skip)
         # a short first window puts the GPU to work early; after that two windows are always being tokenized ahead
         bounds = [0, max(64, win // 8)]
         while bounds[-1] < n:
@@ -219,7 +236,7 @@ class HipHuggingFaceEmbedding:
                 seqs = futs[i].result()
                 if i + 2 < len(spans):
                     futs.append(pool.submit(self._tokenize, texts[spans[i + 2][0]:spans[i + 2][1]], prefix))
-                out[a:b] = self.embed_token_batches(seqs)
+                out[a:b] = self.embed_token_batches(seqs, skip)
                 futs[i] = None
         return out
 

@@ -39,6 +39,7 @@ class EncoderConfig:
     # "gemma3_text" (EmbeddingGemma: gemma.GemmaConfig) | "mpnet" (MPNet embedders: mpnet.MpnetWeights; positions as "xlmr") |
     # "deberta-v2" (DeBERTa-v2 / v3 cross-encoders: deberta.DebertaConfig)
     # "nomic_bert" | "jina_embeddings_v3" (post-LN encoders with RoPE: ropebert.RopeBertConfig; positions 0-based)
+    # "t5" (T5 encoders: t5.T5Config; no positions)
     arch: str = "xlmr"
     vocab_size: int = 250002
     hidden: int = 1024
@@ -133,7 +134,7 @@ class EncoderPath:
     rows_workspace: Optional[str] = None  # (``pooled_rows``), and its workspace size
     score: Optional[str] = None      # decoder paths: the *ForSequenceClassification score head over those rows
     pooled_head: Optional[str] = None  # ModernBERT / DeBERTa paths: pooling ("cls" / "mean") + classification head over the full forward
-    pool_dense: Optional[str] = None   # EmbeddingGemma path: mean pooling + the two Dense modules + L2 norm over the full forward
+    pool_dense: Optional[str] = None   # EmbeddingGemma / T5 paths: mean pooling + the Dense module(s) + L2 norm over the full forward
 
 
 BF16_PATH = EncoderPath(forward="tt_encoder_forward", workspace="tt_encoder_workspace_bytes",
@@ -205,6 +206,12 @@ ROPEBERT_FP16_PATH = EncoderPath(forward="tt_ropebert_forward_f16", workspace="t
                                  cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
                                  scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
                                  no_fp8="the NomicBERT / Jina-v3 path has no fp8 projections")
+
+# T5 encoders (t5.T5Weights): full forward with MPNet's biased attention kernel; the sentence-transformers tail in one entry point
+# (mean pooling over a row range, the optional Dense, Normalize); bf16 only, no other pooling, no head.
+T5_BF16_PATH = EncoderPath(forward="tt_t5_forward", workspace="tt_t5_workspace_bytes", cls_forward=None, cls_workspace=None,
+                           pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc", head_scratch="head",
+                           hidden=torch.bfloat16, pool_dense="tt_t5_pool_dense", no_fp8="the T5 path has no fp8 projections")
 
 
 def _strip_prefix(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -828,17 +835,31 @@ class Encoder:
             self._compact = have
         return have[0][:n], have[1][:n]
 
-    def embed_packed(self, batch: PackedBatch, pooling: str = "cls") -> Tuple[torch.Tensor, torch.Tensor]:
+    def embed_packed(self, batch: PackedBatch, pooling: str = "cls", skip: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (embeddings fp32 [B, H] L2-normalised, same rounded to bf16).  ``pooling``: "cls" (the BGE family: the last layer
         runs for the CLS rows only), "mean" (sentence-transformers mean pooling over a sequence's tokens: full last layer) or
-        "last" (the last token of every sequence: decoder embedders)."""
+        "last" (the last token of every sequence: decoder embedders).  ``skip`` (T5 path: a checkpoint whose Pooling module says
+        ``include_prompt: false``): the first ``skip`` tokens of every sequence -- its instruction -- stay out of the mean."""
         p, dev = self.path, self.device
         B, H = len(batch.seq_len), self.cfg.hidden
+        if skip and self.cfg.arch != "t5":
+            raise ValueError("a prompt is left out of the mean on the T5 path only")
         if p.pool_dense is not None:
-            # EmbeddingGemma: the checkpoint's own tail (mean pooling -> Dense -> Dense -> Normalize) behind the full forward
+            # EmbeddingGemma: the checkpoint's own tail (mean pooling -> Dense -> Dense -> Normalize) behind the full forward; T5:
+            # mean pooling -> Dense (where the checkpoint has one) -> Normalize
             if pooling != "mean":
+                if self.cfg.arch == "t5":
+                    raise ValueError(f"pooling '{pooling}': a T5 encoder checkpoint pools the mean (its Dense module follows it)")
                 raise ValueError(f"pooling '{pooling}': an EmbeddingGemma checkpoint pools the mean (its Dense modules follow it)")
+            ranges = None
+            if skip:
+                from .t5 import pooled_ranges
+
+                ranges = pooled_ranges(batch.seq_start, batch.seq_len, skip)     # (raises before anything is enqueued)
             hidden, starts, lens = self.forward_packed(batch, want_lens=True)
+            if ranges is not None:
+                both = torch.from_numpy(np.concatenate(ranges)).to(dev)
+                starts, lens = both[:B], both[B:]
             out = torch.empty((B, self.w.out_dim), dtype=torch.float32, device=dev)
             out16 = torch.empty((B, self.w.out_dim), dtype=torch.bfloat16, device=dev)
             with torch.cuda.device(dev):

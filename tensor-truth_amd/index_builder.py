@@ -157,6 +157,10 @@ def _build_with_workers(index, documents, embed_model, chunking_strategy, chunk_
     if (W <= 0 or node_parser is not None or chunking_strategy not in ("hierarchical", "semantic_hierarchical")
             or not hasattr(embed_model, "embed_token_batches") or len(documents) < min_docs):
         return False
+    if not getattr(embed_model, "include_prompt", True) and getattr(embed_model, "text_instruction", ""):
+        # a checkpoint whose mean leaves the instruction's tokens out (INSTRUCTOR's include_prompt: false): the workers send token
+        # ids with the instruction already in them and no word of where it ends -- the in-process loop counts it (``_embed_texts``)
+        return False
     try:
         tk_spec = iw.tokenizer_spec(embed_model._tokenizer)
     except TypeError:

@@ -133,6 +133,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
         return _build_deberta(cfg, state, device, mode, what)
     if getattr(cfg, "arch", "") in ("nomic_bert", "jina_embeddings_v3"):
         return _build_ropebert(cfg, state, device, mode, what)
+    if getattr(cfg, "arch", "") == "t5":
+        return _build_t5(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
     make, desc = _implementations()[impl]
     w = make(cfg, state, device)
@@ -259,4 +261,26 @@ def _build_ropebert(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any,
     w = RopeBertWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
     desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
     logger.info("%s: %s encoder, precision = %s", what, cfg.arch, desc)
+    return w, Encoder(w), desc
+
+
+def _build_t5(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """T5 encoders: bf16 only.  The FFN activations of a T5 leave float16's range -- transformers' own float16 run clamps them,
+    which is another model -- the fp8 projections exist for the XLM-R / BERT family only, and the reference precision (fp32
+    semantics, what no torch_dtype means for that family) has no implementation here: refused, never computed in another
+    precision behind the caller's back."""
+    from .encoder import Encoder
+    from .t5 import T5Weights
+
+    if mode != "bf16":
+        why = {"fp16": " (T5's feed-forward activations leave float16's range; transformers clamps them in float16, which is "
+                       "another model)",
+               "fp8": " (the fp8 projections exist for the XLM-R / BERT family only)",
+               "reference": " (the fp32-semantics paths exist for the XLM-R / BERT family only)"}.get(mode, "")
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for T5 encoders{why}; pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}}")
+    w = T5Weights(cfg, state, device)
+    desc = "bf16 (fp32 accumulate)"
+    logger.info("%s: T5 encoder, precision = %s", what, desc)
     return w, Encoder(w), desc

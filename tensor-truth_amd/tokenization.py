@@ -124,6 +124,9 @@ class SpecialTokens:
         elif arch == "deberta-v2":         # the DeBERTa-v2 / v3 sentencepiece vocabulary: [PAD] 0, [CLS] 1, [SEP] 2, [UNK] 3
             self.bos, self.pad, self.eos, self.unk, self.first_free = 1, 0, 2, 3, 4
             self.pair_sep = [2]             # [CLS] A [SEP] B [SEP]
+        elif arch == "t5":                 # the T5 sentencepiece vocabulary: <pad> 0, </s> 1, <unk> 2; no opening token: A </s>
+            self.bos, self.pad, self.eos, self.unk, self.first_free = None, 0, 1, 2, 3
+            self.pair_sep = [1]
         else:
             self.bos, self.pad, self.eos, self.unk, self.first_free = 101, 0, 102, 100, 1000
             self.pair_sep = [102]           # [CLS] A [SEP] B [SEP]
@@ -166,9 +169,10 @@ class HashTokenizer:
 
     def encode(self, text: str, max_length: Optional[int] = None) -> List[int]:
         body = self._ids(text)
+        head = [] if self.sp.bos is None else [self.sp.bos]
         if max_length is not None:
-            body = body[: max(0, max_length - 2)]
-        return [self.sp.bos] + body + [self.sp.eos]
+            body = body[: max(0, max_length - 1 - len(head))]
+        return head + body + [self.sp.eos]
 
     def encode_batch(self, texts: Sequence[str], max_length: Optional[int] = None) -> List[List[int]]:
         return [self.encode(t, max_length) for t in texts]

@@ -250,6 +250,13 @@ def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
         from .ropebert import config_from_hf as ropebert_config_from_hf
 
         return ropebert_config_from_hf(d)
+    if mt == "t5":
+        from .t5 import config_from_hf as t5_config_from_hf
+
+        return t5_config_from_hf(d)
+    if mt == "umt5":
+        raise NotImplementedError("umt5 checkpoints carry a relative-position bias table in every block (the T5 path adds block "
+                                  "0's table in every block): not supported")
     arch = "bert" if mt == "bert" else "xlmr"
     archs = " ".join(d.get("architectures", []))
     num_labels = 1 if "SequenceClassification" in archs else num_labels_default
@@ -368,6 +375,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
         from .deberta import KNOWN_CONFIGS as deberta_configs
 
         cfg = deberta_configs.get(model_name)
+    if cfg is None:
+        from .t5 import KNOWN_CONFIGS as t5_configs
+
+        cfg = t5_configs.get(model_name)
     if "state_dict" in mk:
         if cfg is None:
             raise ValueError(f"no architecture known for '{model_name}': pass model_kwargs['encoder_config']")
@@ -380,7 +391,14 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             # (HipSentenceTransformerRerank's loader: refused before the weights are read)
             raise ValueError(f"'{model_name}': {cfg.arch} checkpoints are served as embedders only (HipHuggingFaceEmbedding); "
                              "a *ForSequenceClassification head of this type is not supported -- no such cross-encoder is published")
+        if want_head and cfg.arch == "t5":
+            raise ValueError(f"'{model_name}': t5 checkpoints are served as embedders only (HipHuggingFaceEmbedding); a T5 "
+                             "cross-encoder is not supported")
         state = load_state(mdir)
+        if cfg.arch == "t5":
+            from .t5 import dense_module
+
+            state.update(dense_module(mdir))       # the sentence-transformers Dense module, where the directory has one
         if cfg.arch == "gemma3_text" and not want_head:
             from .gemma import dense_modules
 
@@ -414,6 +432,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .ropebert import synthetic_state as ropebert_state
 
             return cfg, ropebert_state(cfg, seed), None
+        if cfg.arch == "t5":
+            from .t5 import synthetic_state as t5_state
+
+            return cfg, t5_state(cfg, seed), None
         if mk.get("synthetic_on_device", cfg.layers * cfg.hidden >= 12 * 768):
             return cfg, synthetic_state_device(cfg, device, seed), None
         return cfg, synthetic_state(cfg, seed), None
