@@ -956,6 +956,69 @@ int tt_ropebert_forward_f16(const tt_ropebert_weights* w, const int32_t* ids, co
                             const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- JinaBERT encoders: post-LN BERT blocks with ALiBi attention and a GEGLU feed-forward (csrc/jinabert.hip) ------------------
+ * The remote-code architecture (jinaai/jina-bert-implementation) behind jinaai/jina-embeddings-v2-small-en / -base-en; its
+ * config.json says model_type "bert" with position_embedding_type "alibi".  No position table and no RoPE; every head h adds the
+ * ALiBi bias -slope_h |query - key| to its scores AFTER the 1 / sqrt(64) scaling, symmetric, bidirectional over the sequence's
+ * own tokens; slope_h follows the original ALiBi rule for `heads` heads (a geometric series for a power of two, else the series of
+ * the power of two below plus every other term of the next one's):
+ *   h = LayerNorm(word[ids] + type[0]; emb_ln);  per layer
+ *   q | k | v = h Wqkv^T + b_qkv -> a = softmax(q k^T / 8 - slope_h |i - j|) v -> h = LayerNorm(h + a Wo^T + b_o; ln1)
+ *   g = h Wgate^T  [T][2F], no bias -> m = (GELU_erf(g[:, :F]) * g[:, F:]) Wdown^T + b_down -> h = LayerNorm(h + m; ln2)
+ * no final norm.  alibi_slope_log2[h] = slope_h * log2(e), computed in double and rounded once by the caller: the kernel works in
+ * the log2 domain, x = s * (log2(e) / 8) - alibi_slope_log2[h] * float(|key - query|), in registers -- no table and no clamp, exact
+ * at any distance a packed batch can hold.  Same packed token layout as tt_ropebert_forward (`pos` must be present and its values
+ * are not used; type_ids must be NULL: every token of an embedder call is of type 0, whose row is still added), the same
+ * projections (the 16-bit GEMMs; the QKV epilogue writes V in the V8 layout) and LayerNorms, the gated-activation row op of the
+ * ModernBERT path; the attention is tt_attention_alibi at every length.  bf16 -- or fp16 for the `_f16` twins.  Matrices
+ * [out][in] in the element type, norms and biases fp32.  hidden a multiple of 128 and <= 1024, hidden = 64 * heads (head_dim 64),
+ * ffn a multiple of 128; anything else is refused before a launch with the field named. */
+typedef struct tt_jinabert_layer_weights {
+    const void* qkv_w;        /* [3H][H]: attention.self.query, .key, .value rows concatenated */
+    const float* qkv_b;       /* [3H] */
+    const void* o_w;          /* [H][H] attention.output.dense */
+    const float* o_b;         /* [H] */
+    const float* ln1_g;       /* [H] attention.output.LayerNorm */
+    const float* ln1_b;
+    const void* gate_w;       /* [2F][H] mlp.gated_layers: the rows GELU is applied to, then the rows that multiply them; no bias */
+    const void* down_w;       /* [H][F] mlp.wo */
+    const float* down_b;      /* [H] */
+    const float* ln2_g;       /* [H] mlp.layernorm */
+    const float* ln2_b;
+} tt_jinabert_layer_weights;
+
+typedef struct tt_jinabert_weights {
+    int32_t hidden, layers, heads, ffn, vocab, type_vocab;
+    float ln_eps;
+    const void* word_emb;     /* [vocab][H] */
+    const void* type_emb;     /* [type_vocab][H]; row 0 is added to every token */
+    const float* emb_ln_g;    /* [H] embeddings.LayerNorm */
+    const float* emb_ln_b;
+    const float* alibi_slope_log2;   /* [heads] fp32, DEVICE memory: slope_h * log2(e) */
+    const tt_jinabert_layer_weights* layer; /* host array [layers] */
+} tt_jinabert_weights;
+
+size_t tt_jinabert_workspace_bytes(const tt_jinabert_weights* w, int n_rows);   /* 0 for a refused shape */
+/* hidden_out: [n_rows][H] last hidden state */
+int tt_jinabert_forward(const tt_jinabert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* building block (parity tests; the forward's own kernel): tt_attention_window's operands without a window, plus the slopes --
+ *   out[q][h * 64 ...] = softmax over the keys k of q's own sequence of (Q_h . K_h) / 8 - slope_log2[h] / log2(e) * |k - q|,
+ *   applied to V_h; slope_log2 [heads] fp32 in device memory.  One wave per (16-query tile, sequence, head); rows of no sequence
+ *   are not written.  All-zero slopes give attention without a bias.  head_dim must be 64. */
+int tt_attention_alibi(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim, int max_len,
+                       const float* slope_log2, void* stream);
+/* the fp16 twins (jinabert.hip compiled a second time) */
+size_t tt_jinabert_workspace_bytes_f16(const tt_jinabert_weights* w, int n_rows);
+int tt_jinabert_forward_f16(const tt_jinabert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int tt_attention_alibi_f16(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
+                           int max_len, const float* slope_log2, void* stream);
+
 /* ---- T5 encoders: T5EncoderModel embedders (csrc/t5.hip) ------------------------------------------------------------------------
  * sentence-transformers/sentence-t5-base / -large, gtr-t5-base / -large, hkunlp/instructor-base / -large (model_type "t5",
  * transformers/models/t5/modeling_t5.py).  Pre-norm blocks without biases; norm(v; w) = bf16(v * rsqrt(mean(v^2) + eps)) * w

@@ -262,6 +262,17 @@ SIGNATURES = {
     "tt_t5_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_t5_pool_dense": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    # JinaBERT encoders: jina-embeddings-v2 (csrc/jinabert.hip) and their fp16 twins (same signatures)
+    "tt_jinabert_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "tt_jinabert_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_attention_alibi": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tt_jinabert_workspace_bytes_f16": (c_size_t, [c_void_p, c_int]),
+    "tt_jinabert_forward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_attention_alibi_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

@@ -65,3 +65,7 @@
 // ropebert.hip a second time: the NomicBERT / Jina-v3 encoders in fp16
 #define tt_ropebert_workspace_bytes tt_ropebert_workspace_bytes_f16
 #define tt_ropebert_forward tt_ropebert_forward_f16
+// jinabert.hip a second time: the JinaBERT (jina-embeddings-v2) encoders in fp16
+#define tt_jinabert_workspace_bytes tt_jinabert_workspace_bytes_f16
+#define tt_jinabert_forward tt_jinabert_forward_f16
+#define tt_attention_alibi tt_attention_alibi_f16

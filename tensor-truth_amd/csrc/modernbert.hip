@@ -26,23 +26,7 @@
 
 namespace {
 
-// GELU(x) = 0.5 x (1 + erf(x / sqrt 2)), the exact-erf form of the encoder's GEMM epilogue (gemm.hip gelu_erf2, one value at a
-// time): gelu(x) = max(x, 0) - |x| 2^Q(|x|), Q the degree-7 fit of log2 Phi(-u) on [0, 9]; abs error <= 1e-5.
-__device__ __forceinline__ float mb_gelu_erf(float x) {
-    const float u = fabsf(x);
-    float q = u * -9.697845371e-07f + 4.016999810e-05f;
-    q = q * u + -7.211678312e-04f;
-    q = q * u + 7.490924560e-03f;
-    q = q * u + -5.142170191e-02f;
-    q = q * u + -4.614778757e-01f;
-    q = q * u + -1.149914980e+00f;
-    q = q * u + -1.000091195e+00f;
-    return fmaxf(x, 0.f) - u * __builtin_amdgcn_exp2f(q);
-}
-// GELU_erf(input) * gate through varlen.h's gated_act_kernel: gu [T][2F] (input columns, then gate columns) -> out [T][F]
-struct GeluErf {
-    static __device__ __forceinline__ float f(float x) { return mb_gelu_erf(x); }
-};
+// (the exact-erf GELU gate, GeluErf, is varlen.h's: the JinaBERT path uses it too)
 
 // ---- rotate-half RoPE of the q and k heads with base theta, in place; V heads copied to the V8 layout ------------------------
 // One block per token row, one wave per head at a time; heads of 64: lane i < 32 holds the pair (i, i + 32).

@@ -15,7 +15,7 @@
 //   mlp_kind 0:  a  = GELU_erf(GEMM(x1, W1) + b1)                                             (TT_EPI_GELU)
 //   y    = GEMM(a, Wdown) + b_down + x1                                                       (TT_EPI_RESIDUAL)
 //   x    = LayerNorm(y; post_mlp_layernorm)
-// with x = LayerNorm(word[ids] + type[0]) before the first layer (rb_embed_ln_kernel below: the encoder's embedding kernel adds a
+// with x = LayerNorm(word[ids] + type[0]) before the first layer (varlen.h rb_embed_ln_kernel: the encoder's embedding kernel adds a
 // position row, which these models do not have) and no norm behind the last.  A missing bias is the workspace's row of fp32 zeros,
 // as on the ModernBERT path.  The attention is the encoder's bidirectional kernel at every length -- the one DESIGN 4.4 builds for
 // whole sequences (K / V staged in LDS for four or eight query blocks per workgroup) and the ModernBERT path runs on its global
@@ -31,74 +31,7 @@ struct Silu {
     static __device__ __forceinline__ float f(float x) { return x / (1.0f + expf(-x)); }
 };
 
-// ---- embeddings: out[r] = LayerNorm(word[ids[r]] + type[0]) * gamma + beta ------------------------------------------------------
-// One wave per row, four rows per block, as rowops.hip: lane l holds the 16-byte pieces l and l + 64 of the row (H <= 1024), the sum
-// in fp32, two-pass statistics (mean, then centred variance), one rounding.  An id outside [0, vocab) is clamped into the table
-// (the host validates too).
-constexpr int kRbRowThreads = 256;
-
-__device__ __forceinline__ void rb_unpack8(const uint4& u, float (&f)[8]) {
-    f[0] = elo(u.x); f[1] = ehi(u.x);
-    f[2] = elo(u.y); f[3] = ehi(u.y);
-    f[4] = elo(u.z); f[5] = ehi(u.z);
-    f[6] = elo(u.w); f[7] = ehi(u.w);
-}
-
-__global__ __launch_bounds__(kRbRowThreads) void rb_embed_ln_kernel(const int32_t* __restrict__ ids, const uint16_t* __restrict__ word,
-                                                                    const uint16_t* __restrict__ type_row, const float* __restrict__ gamma,
-                                                                    const float* __restrict__ beta, uint16_t* __restrict__ out, int T,
-                                                                    int H, int vocab, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * (kRbRowThreads / 64) + (threadIdx.x >> 6);
-    if (row >= T) return;   // (wave-uniform)
-    int id = ids[row];
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    const int nch = H / 8;
-    float x[2][8];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int ch = lane + 64 * c;
-        if (ch < nch) {
-            float a[8], t[8];
-            rb_unpack8(*reinterpret_cast<const uint4*>(word + (size_t)id * H + ch * 8), a);
-            rb_unpack8(*reinterpret_cast<const uint4*>(type_row + ch * 8), t);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                x[c][i] = a[i] + t[i];
-                s += x[c][i];
-            }
-        }
-    }
-    const float mean = wave_sum(s) / (float)H;
-    float v = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-        if (lane + 64 * c < nch)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float d = x[c][i] - mean;
-                v += d * d;
-            }
-    const float rstd = rsqrtf(wave_sum(v) / (float)H + eps);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int ch = lane + 64 * c;
-        if (ch < nch) {
-            const float4 g0 = *reinterpret_cast<const float4*>(gamma + ch * 8);
-            const float4 g1 = *reinterpret_cast<const float4*>(gamma + ch * 8 + 4);
-            const float4 b0 = *reinterpret_cast<const float4*>(beta + ch * 8);
-            const float4 b1 = *reinterpret_cast<const float4*>(beta + ch * 8 + 4);
-            const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-            const float b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            float y[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) y[i] = (x[c][i] - mean) * rstd * g[i] + b[i];
-            *reinterpret_cast<uint4*>(out + (size_t)row * H + ch * 8) =
-                uint4{pack_e2(y[0], y[1]), pack_e2(y[2], y[3]), pack_e2(y[4], y[5]), pack_e2(y[6], y[7])};
-        }
-    }
-}
+// (the embedding row op, rb_embed_ln_kernel, is varlen.h's: the JinaBERT path uses it too)
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
 int check_weights(const tt_ropebert_weights* w) {

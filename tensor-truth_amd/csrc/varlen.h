@@ -1,6 +1,6 @@
 // What the rotary, pre-norm, packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT; gemma.hip; and,
 // for the attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias, and deberta.hip:
-// DeBERTa-v2/v3's post-LN layer with disentangled attention): the attention
+// DeBERTa-v2/v3's post-LN layer with disentangled attention; jinabert.hip: JinaBERT's post-LN layer with ALiBi): the attention
 // tile over the V8 layout, the embedding gather, the gated activation, the workspace plan and the forwards' argument checks.
 // Device code sits in an anonymous namespace or is a template: one copy per translation unit and element type (common.h TT_F16).
 #pragma once
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(128) void embed_gather_kernel(const int32_t* __rest
 }
 
 // ---- gated activation: gu [T][2F] (activated columns, then the columns that multiply them) -> out [T][F] ---------------------
-// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (decoder.hip Silu, modernbert.hip GeluErf)
+// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (decoder.hip Silu, GeluErf below)
 template <class Act>
 __global__ __launch_bounds__(256) void gated_act_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
                                                         int F) {
@@ -54,9 +54,97 @@ int gated_act_launch(const uint16_t* gu, uint16_t* out, int rows, int F, hipStre
     return TT_OK;
 }
 
+// GELU(x) = 0.5 x (1 + erf(x / sqrt 2)), the exact-erf form of the encoder's GEMM epilogue (gemm.hip gelu_erf2, one value at a
+// time): gelu(x) = max(x, 0) - |x| 2^Q(|x|), Q the degree-7 fit of log2 Phi(-u) on [0, 9]; abs error <= 1e-5.
+__device__ __forceinline__ float mb_gelu_erf(float x) {
+    const float u = fabsf(x);
+    float q = u * -9.697845371e-07f + 4.016999810e-05f;
+    q = q * u + -7.211678312e-04f;
+    q = q * u + 7.490924560e-03f;
+    q = q * u + -5.142170191e-02f;
+    q = q * u + -4.614778757e-01f;
+    q = q * u + -1.149914980e+00f;
+    q = q * u + -1.000091195e+00f;
+    return fmaxf(x, 0.f) - u * __builtin_amdgcn_exp2f(q);
+}
+// GELU_erf(input) * gate through varlen.h's gated_act_kernel: gu [T][2F] (input columns, then gate columns) -> out [T][F]
+struct GeluErf {
+    static __device__ __forceinline__ float f(float x) { return mb_gelu_erf(x); }
+};
+
+// ---- embeddings: out[r] = LayerNorm(word[ids[r]] + type[0]) * gamma + beta ------------------------------------------------------
+// One wave per row, four rows per block, as rowops.hip: lane l holds the 16-byte pieces l and l + 64 of the row (H <= 1024), the sum
+// in fp32, two-pass statistics (mean, then centred variance), one rounding.  An id outside [0, vocab) is clamped into the table
+// (the host validates too).
+constexpr int kRbRowThreads = 256;
+
+__device__ __forceinline__ void rb_unpack8(const uint4& u, float (&f)[8]) {
+    f[0] = elo(u.x); f[1] = ehi(u.x);
+    f[2] = elo(u.y); f[3] = ehi(u.y);
+    f[4] = elo(u.z); f[5] = ehi(u.z);
+    f[6] = elo(u.w); f[7] = ehi(u.w);
+}
+
+__global__ __launch_bounds__(kRbRowThreads) void rb_embed_ln_kernel(const int32_t* __restrict__ ids, const uint16_t* __restrict__ word,
+                                                                    const uint16_t* __restrict__ type_row, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, uint16_t* __restrict__ out, int T,
+                                                                    int H, int vocab, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (kRbRowThreads / 64) + (threadIdx.x >> 6);
+    if (row >= T) return;   // (wave-uniform)
+    int id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    const int nch = H / 8;
+    float x[2][8];
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nch) {
+            float a[8], t[8];
+            rb_unpack8(*reinterpret_cast<const uint4*>(word + (size_t)id * H + ch * 8), a);
+            rb_unpack8(*reinterpret_cast<const uint4*>(type_row + ch * 8), t);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                x[c][i] = a[i] + t[i];
+                s += x[c][i];
+            }
+        }
+    }
+    const float mean = wave_sum(s) / (float)H;
+    float v = 0.f;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        if (lane + 64 * c < nch)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float d = x[c][i] - mean;
+                v += d * d;
+            }
+    const float rstd = rsqrtf(wave_sum(v) / (float)H + eps);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nch) {
+            const float4 g0 = *reinterpret_cast<const float4*>(gamma + ch * 8);
+            const float4 g1 = *reinterpret_cast<const float4*>(gamma + ch * 8 + 4);
+            const float4 b0 = *reinterpret_cast<const float4*>(beta + ch * 8);
+            const float4 b1 = *reinterpret_cast<const float4*>(beta + ch * 8 + 4);
+            const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+            const float b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+            float y[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) y[i] = (x[c][i] - mean) * rstd * g[i] + b[i];
+            *reinterpret_cast<uint4*>(out + (size_t)row * H + ch * 8) =
+                uint4{pack_e2(y[0], y[1]), pack_e2(y[2], y[3]), pack_e2(y[4], y[5]), pack_e2(y[6], y[7])};
+        }
+    }
+}
+
 // ---- attention over packed varlen sequences: one 16-query tile of one (sequence b, query head h) per call, one wave -------------
 // Query head h reads KV head h / group (group = 1: as many KV heads as query heads).  Tile t holds the queries q0 .. q0 + 15,
-// q0 = s0 + 16 t, of the sequence s0 .. s_end - 1.  Keys are visited in blocks of 32 on the absolute 8-row grid:
+// q0 = s0 + 16 t, of the sequence s0 .. s_end - 1.  Keys are visited in blocks of 32 on the absolute 8-row grid (the Alibi policy:
+// counted from s0, see below):
 //   WINDOW = false (causal):        the blocks from the sequence's first 8-row group up to the tile's last query; key k is live for
 //                                   query q iff s0 <= k <= q;
 //   WINDOW = true (bidirectional):  the blocks that intersect [max(s0, q0 - w), min(s_end - 1, q0 + 15 + w)]; key k is live for query
@@ -88,11 +176,20 @@ int gated_act_launch(const uint16_t* gu, uint16_t* out, int rows, int F, hipStre
 //            index table (distance d at d + center) in LDS once, PAD copies of the end values on either side (disent_stage): a
 //            lane's eight keys of a block are eight consecutive distances, descending, so one clamp of the first leaves eight
 //            reads that are exact wherever the distance is one a sequence can hold.  Masked pairs read nothing.
+//   Alibi (JinaBERT, jinabert.hip): x = s * scale_log2 - slope_log2 * float(|key - query|), slope_log2 the head's ALiBi slope times
+//            log2(e), rounded once from double by the host.  Computed in registers from the row numbers: no table, no LDS, no
+//            clamp -- a distance within a packed batch is below 2^24 and converts exactly, so the bias is exact to its two
+//            roundings (the product, the subtraction; one if the compiler contracts them) at any distance.
+//            The policy is also ANCHORED: its key blocks are counted from the sequence's own first row, kb = s0 (mod 8), not from
+//            the batch's 8-row grid, so a sequence's rows are the same bits wherever it starts -- on the grid (what pack_tokens
+//            gives) or right behind its neighbour.  K rows are read row by row either way; a lane's eight V values of a block
+//            then straddle two 8-row groups of the V8 layout when s0 is off the grid: two 16-byte reads and a funnel shift by
+//            s0 % 8 elements (v8_shift; wave-uniform, and a start on the grid takes the one read of every other policy).
 struct NoBias {
-    static constexpr bool on = false, content = false;
+    static constexpr bool on = false, content = false, linear = false, anchored = false;
 };
 struct RelBias {
-    static constexpr bool on = true, content = false;
+    static constexpr bool on = true, content = false, linear = false, anchored = false;
     static constexpr int R = 128, PAD = 8, LDS_FLOATS = 2 * R + 1 + 2 * PAD;
     const float* lds;   // the staged table: lds[i] = tbl[clamp(i - PAD, 0, 2R)]
 };
@@ -104,7 +201,7 @@ __device__ __forceinline__ void relbias_stage(const float* __restrict__ tbl, int
 }
 
 struct Disentangled {
-    static constexpr bool on = false, content = true;
+    static constexpr bool on = false, content = true, linear = false, anchored = false;
     static constexpr int PAD = 8, MAX_POS = 512, LDS_INTS = 2 * MAX_POS - 1 + 2 * PAD;
     const int32_t* idx;   // the staged index table: idx[i] = clamp(dist_index[clamp(i - PAD, 0, 2 max_pos - 2)], 0, n_pos - 1)
     int center, idx_max;  // max_pos - 1, 2 max_pos - 2
@@ -119,6 +216,27 @@ __device__ __forceinline__ void disent_stage(const int32_t* __restrict__ dist_in
         lds[i] = min(max(dist_index[min(max(i - Disentangled::PAD, 0), n - 1)], 0), n_pos - 1);
     __syncthreads();
 }
+
+// ALiBi (JinaBERT, jinabert.hip): the head's slope times log2(e), one register; nothing is staged and nothing is clamped
+// the 16-bit elements r .. r + 7 of the sixteen in (a, b), r in 1 .. 7 and wave-uniform: eight consecutive rows of one feature that
+// start r rows into an 8-row group of the V8 layout
+__device__ __forceinline__ uint4 v8_shift(const uint4& a, const uint4& b, int r) {
+    const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint32_t e[5];
+    switch (r >> 1) {
+        case 0: e[0] = d[0]; e[1] = d[1]; e[2] = d[2]; e[3] = d[3]; e[4] = d[4]; break;
+        case 1: e[0] = d[1]; e[1] = d[2]; e[2] = d[3]; e[3] = d[4]; e[4] = d[5]; break;
+        case 2: e[0] = d[2]; e[1] = d[3]; e[2] = d[4]; e[3] = d[5]; e[4] = d[6]; break;
+        default: e[0] = d[3]; e[1] = d[4]; e[2] = d[5]; e[3] = d[6]; e[4] = d[7]; break;
+    }
+    if (r & 1)
+        return uint4{(e[0] >> 16) | (e[1] << 16), (e[1] >> 16) | (e[2] << 16), (e[2] >> 16) | (e[3] << 16), (e[3] >> 16) | (e[4] << 16)};
+    return uint4{e[0], e[1], e[2], e[3]};
+}
+struct Alibi {
+    static constexpr bool on = false, content = false, linear = true, anchored = true;
+    float slope_log2;
+};
 
 template <int D, bool WINDOW, class Bias = NoBias>
 __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
@@ -155,7 +273,9 @@ __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv,
     const int k_lo = WINDOW ? max(s0, q_lim - w) : s0, k_hi = WINDOW ? min(s_end - 1, q_lim + w) : q_lim;       // this lane's query's
     const uint16_t* kbase = qkv + k_col0 + (size_t)kvh * D + 8 * g;
     const uint16_t* vbase = vt + ((size_t)kvh * D + c) * 8;
-    for (int kb = k_first & ~7; kb <= k_last; kb += 32) {
+    // the first key block: on the batch's 8-row grid, or (an anchored policy) a multiple of 8 rows behind the sequence's first row
+    const int kb0 = Bias::anchored ? k_first - ((k_first - s0) & 7) : k_first & ~7;
+    for (int kb = kb0; kb <= k_last; kb += 32) {
         f32x4 s[2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -190,6 +310,8 @@ __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv,
                     sv += crow[i] + bias.p[(size_t)key * bias.ld + i];
                 }
                 v = sv * scale_log2;
+            } else if constexpr (Bias::linear) {
+                v = s[j >> 2][j & 3] * scale_log2 - bias.slope_log2 * (float)abs(key - qrow);
             } else {
                 v = s[j >> 2][j & 3] * scale_log2;
             }
@@ -213,6 +335,19 @@ __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv,
         // V^T fragment: feature 16 dt + c, keys kb + 8 g .. + 7 (one 8-row group of the V8 layout)
         const int grp = (kb >> 3) + g;
         const bool vok = 8 * grp < n_rows;
+        if constexpr (Bias::anchored) {
+            if (s0 & 7) {   // (wave-uniform) keys kb + 8 g .. + 7 start s0 % 8 rows into group grp
+                const bool vok1 = 8 * (grp + 1) < n_rows;
+#pragma unroll
+                for (int dt = 0; dt < D / 16; ++dt) {
+                    const uint16_t* vp = vbase + (size_t)grp * ldvt + (size_t)dt * 16 * 8;
+                    const uint4 u0 = vok ? *reinterpret_cast<const uint4*>(vp) : zero4;
+                    const uint4 u1 = vok1 ? *reinterpret_cast<const uint4*>(vp + ldvt) : zero4;
+                    o[dt] = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, v8_shift(u0, u1, s0 & 7)), pf, o[dt] * alpha);
+                }
+                continue;
+            }
+        }
 #pragma unroll
         for (int dt = 0; dt < D / 16; ++dt) {
             const uint4 u = vok ? *reinterpret_cast<const uint4*>(vbase + (size_t)grp * ldvt + (size_t)dt * 16 * 8) : zero4;

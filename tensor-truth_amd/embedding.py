@@ -82,7 +82,7 @@ class HipHuggingFaceEmbedding:
         # (model_kwargs["pooling"]); "cls" for the BGE family the reference defaults to, "mean" for e5 / all-MiniLM / gte ...,
         # "last" for the decoder embedders (also when their directory declares nothing)
         default_pooling = {"qwen3": "last", "gemma3_text": "mean", "nomic_bert": "mean",
-                           "jina_embeddings_v3": "mean", "t5": "mean"}.get(cfg.arch, "cls")
+                           "jina_embeddings_v3": "mean", "t5": "mean", "jina_bert": "mean"}.get(cfg.arch, "cls")
         pooling = (model_kwargs or {}).get("pooling") or _weights.pooling_mode(mdir, default_pooling)
         pooling = {"cls_token": "cls", "mean_tokens": "mean", "lasttoken": "last"}.get(pooling, pooling)
         if pooling not in ("cls", "mean", "last") or (pooling == "last" and cfg.arch != "qwen3"):
@@ -114,7 +114,7 @@ class HipHuggingFaceEmbedding:
             self.include_prompt = _t5.include_prompt(mdir)
         self.query_instruction = query_instruction_for(model_name) if query_instruction is None else query_instruction
         self.text_instruction = text_instruction or ""
-        if cfg.arch in ("modernbert", "gemma3_text", "nomic_bert", "jina_embeddings_v3"):
+        if cfg.arch in ("modernbert", "gemma3_text", "nomic_bert", "jina_embeddings_v3", "jina_bert"):
             # sentence-transformers prompts (config_sentence_transformers.json), e.g. nomic's "search_query: " / "search_document: " or
             # EmbeddingGemma's "task: search result | query: " / "title: none | text: ": "query" for queries, "document" for
             # texts, where the checkpoint names them

@@ -40,6 +40,7 @@ class EncoderConfig:
     # "deberta-v2" (DeBERTa-v2 / v3 cross-encoders: deberta.DebertaConfig)
     # "nomic_bert" | "jina_embeddings_v3" (post-LN encoders with RoPE: ropebert.RopeBertConfig; positions 0-based)
     # "t5" (T5 encoders: t5.T5Config; no positions)
+    # "jina_bert" (JinaBERT, jina-embeddings-v2: jinabert.JinaBertConfig; ALiBi attention, no position table)
     arch: str = "xlmr"
     vocab_size: int = 250002
     hidden: int = 1024
@@ -206,6 +207,16 @@ ROPEBERT_FP16_PATH = EncoderPath(forward="tt_ropebert_forward_f16", workspace="t
                                  cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
                                  scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
                                  no_fp8="the NomicBERT / Jina-v3 path has no fp8 projections")
+
+# JinaBERT embedders (jinabert.JinaBertWeights): post-LN layers with ALiBi attention and GEGLU; first-token and mean pooling with
+# the encoder's kernels; no CLS-only forward, no head, no fp8.
+JINABERT_BF16_PATH = EncoderPath(forward="tt_jinabert_forward", workspace="tt_jinabert_workspace_bytes", cls_forward=None,
+                                 cls_workspace=None, pool="tt_embed_pool", pool_mean="tt_embed_pool_mean", head=None, scratch="enc",
+                                 head_scratch="head", hidden=torch.bfloat16, no_fp8="the JinaBERT path has no fp8 projections")
+JINABERT_FP16_PATH = EncoderPath(forward="tt_jinabert_forward_f16", workspace="tt_jinabert_workspace_bytes_f16", cls_forward=None,
+                                 cls_workspace=None, pool="tt_embed_pool_f16", pool_mean="tt_embed_pool_mean_f16", head=None,
+                                 scratch="enc", head_scratch="head", hidden=torch.float16, pool_writes_bf16=False,
+                                 no_fp8="the JinaBERT path has no fp8 projections")
 
 # T5 encoders (t5.T5Weights): full forward with MPNet's biased attention kernel; the sentence-transformers tail in one entry point
 # (mean pooling over a row range, the optional Dense, Normalize); bf16 only, no other pooling, no head.

@@ -133,6 +133,8 @@ def build_encoder(cfg, state, device, model_kwargs: Optional[Dict[str, Any]], wh
         return _build_deberta(cfg, state, device, mode, what)
     if getattr(cfg, "arch", "") in ("nomic_bert", "jina_embeddings_v3"):
         return _build_ropebert(cfg, state, device, mode, what)
+    if getattr(cfg, "arch", "") == "jina_bert":
+        return _build_jinabert(cfg, state, device, mode, what)
     if getattr(cfg, "arch", "") == "t5":
         return _build_t5(cfg, state, device, mode, what)
     impl = reference_impl(cfg) if mode == "reference" else mode
@@ -283,4 +285,23 @@ def _build_t5(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
     w = T5Weights(cfg, state, device)
     desc = "bf16 (fp32 accumulate)"
     logger.info("%s: T5 encoder, precision = %s", what, desc)
+    return w, Encoder(w), desc
+
+
+def _build_jinabert(cfg, state, device, mode: str, what: str) -> Tuple[Any, Any, str]:
+    """JinaBERT embedders (jina-embeddings-v2): bf16 or fp16, resolved as for the ModernBERT encoders.  The reference precision
+    (fp32 semantics, what no torch_dtype means for the XLM-R / BERT family) has no implementation for them: refused, never computed
+    in another precision behind the caller's back."""
+    import torch
+
+    from .encoder import Encoder
+    from .jinabert import JinaBertWeights
+
+    if mode not in ("bf16", "fp16"):
+        raise NotImplementedError(
+            f"{what}: precision '{mode}' is not available for JinaBERT encoders; pass "
+            f"model_kwargs={{'torch_dtype': 'bfloat16'}} or {{'torch_dtype': 'float16'}}")
+    w = JinaBertWeights(cfg, state, device, dtype=torch.float16 if mode == "fp16" else torch.bfloat16)
+    desc = "fp16 (fp32 accumulate)" if mode == "fp16" else "bf16 (fp32 accumulate)"
+    logger.info("%s: JinaBERT encoder, precision = %s", what, desc)
     return w, Encoder(w), desc

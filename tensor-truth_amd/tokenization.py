@@ -127,7 +127,7 @@ class SpecialTokens:
         elif arch == "t5":                 # the T5 sentencepiece vocabulary: <pad> 0, </s> 1, <unk> 2; no opening token: A </s>
             self.bos, self.pad, self.eos, self.unk, self.first_free = None, 0, 1, 2, 3
             self.pair_sep = [1]
-        else:
+        else:                              # "bert", and "jina_bert" (jina-embeddings-v2 ships the bert-base-uncased WordPiece vocabulary)
             self.bos, self.pad, self.eos, self.unk, self.first_free = 101, 0, 102, 100, 1000
             self.pair_sep = [102]           # [CLS] A [SEP] B [SEP]
 

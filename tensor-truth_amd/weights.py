@@ -257,6 +257,11 @@ def _config_from_hf(d: dict, num_labels_default: int = 0) -> EncoderConfig:
     if mt == "umt5":
         raise NotImplementedError("umt5 checkpoints carry a relative-position bias table in every block (the T5 path adds block "
                                   "0's table in every block): not supported")
+    if mt == "bert" and d.get("position_embedding_type") == "alibi":
+        # JinaBERT (jina-embeddings-v2): a remote-code architecture whose config.json says "bert"
+        from .jinabert import config_from_hf as jinabert_config_from_hf
+
+        return jinabert_config_from_hf(d)
     arch = "bert" if mt == "bert" else "xlmr"
     archs = " ".join(d.get("architectures", []))
     num_labels = 1 if "SequenceClassification" in archs else num_labels_default
@@ -391,6 +396,9 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             # (HipSentenceTransformerRerank's loader: refused before the weights are read)
             raise ValueError(f"'{model_name}': {cfg.arch} checkpoints are served as embedders only (HipHuggingFaceEmbedding); "
                              "a *ForSequenceClassification head of this type is not supported -- no such cross-encoder is published")
+        if want_head and cfg.arch == "jina_bert":
+            raise ValueError(f"'{model_name}': jina_bert checkpoints are served as embedders only (HipHuggingFaceEmbedding); "
+                             "a *ForSequenceClassification head of this type is not supported (jina-reranker-v1 has 32-wide heads)")
         if want_head and cfg.arch == "t5":
             raise ValueError(f"'{model_name}': t5 checkpoints are served as embedders only (HipHuggingFaceEmbedding); a T5 "
                              "cross-encoder is not supported")
@@ -432,6 +440,10 @@ def resolve(model_name: str, model_kwargs: Optional[dict], device: torch.device,
             from .ropebert import synthetic_state as ropebert_state
 
             return cfg, ropebert_state(cfg, seed), None
+        if cfg.arch == "jina_bert":
+            from .jinabert import synthetic_state as jinabert_state
+
+            return cfg, jinabert_state(cfg, seed), None
         if cfg.arch == "t5":
             from .t5 import synthetic_state as t5_state
 
