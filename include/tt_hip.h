@@ -1080,6 +1080,50 @@ int tt_t5_forward(const tt_t5_weights* w, const int32_t* ids, const int32_t* pos
 int tt_t5_pool_dense(const tt_t5_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
                      int n_seq, float* out_f32, void* out_16, void* stream);
 
+/* ---- ColBERT late interaction: MaxSim, the per-token projection, key-limited attention (csrc/colbert.hip) -----------------------
+ * colbert-ir/colbertv2.0, answerdotai/answerai-colbert-small-v1 and the same models in PyLate's layout: a BERT encoder
+ * (tt_encoder_weights) whose every kept token row is projected to `dim` values and L2-normalised.  Passages are encoded once, when
+ * they are indexed; at query time only the query runs through the encoder and every candidate is scored over vectors that already
+ * sit in device memory.  All pointers are device memory unless said otherwise; 16-bit operands are bf16 -- or fp16 for the `_f16`
+ * twins.
+ *
+ * tt_maxsim: scores[q][c] = sum over i < q_len[q] of max over j < d_len[doc] of <Q[q_start[q] + i], D[d_start[doc] + j]>, doc =
+ *   cand[q * n_cand + c] (cand NULL: doc = c for every query).  Vectors are row-major with a row stride of dim.  Products on
+ *   mfma_f32_16x16x32 with fp32 accumulation; the maximum starts from -inf; the sum over the query's tokens runs in index order in
+ *   fp32, so a score does not depend on which other pairs are in the launch.  A negative candidate writes -inf; a document of
+ *   length 0 scores 0.  dim a multiple of 32 up to 128 (anything else is refused before a launch); q_len 1 .. 128, d_len 0 .. 512:
+ *   the kernel clamps a length into its range, and the host wrapper (colbert.py), which holds the lengths, refuses one outside it.
+ * tt_colbert_project: for n < n_out, y = W hidden[rows[n]] (W [dim][H], no bias, fp32 accumulation), out[n] = y / max(||y||_2, 1e-12)
+ *   in fp32, rounded once; out [n_out][dim].  Nothing is computed for rows that are not listed; a row number outside [0, n_rows)
+ *   and an all-zero row give zeros.  H a multiple of 128 up to 1024, dim as above.
+ * tt_attention_keylimit: tt_attention_varlen's operands plus key_len [n_seq]: every one of a sequence's seq_len rows is a query,
+ *   only its first key_len[b] rows are keys (clamped into [1, seq_len]; the host wrapper refuses a value outside).  Sequences of up
+ *   to 128 rows, at any start row (a neighbour's rows in a shared 8-row group are masked); head_dim 32 or 64.  Rows of no
+ *   sequence are not written.
+ * tt_encoder_forward_keylen: tt_encoder_forward with that attention in every layer (same workspace: tt_encoder_workspace_bytes);
+ *   max_len <= 128. */
+int tt_maxsim(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs, const int64_t* d_start,
+              const int32_t* d_len, const int32_t* cand, int n_cand, int dim, float* scores, void* stream);
+int tt_colbert_project(const void* hidden, int n_rows, int H, const void* w, int dim, const int32_t* rows, int n_out, void* out,
+                       void* stream);
+int tt_attention_keylimit(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                          const int32_t* seq_start, const int32_t* seq_len, const int32_t* key_len, int n_seq, int heads, int head_dim,
+                          int max_len, void* stream);
+int tt_encoder_forward_keylen(const tt_encoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                              const int32_t* seq_start, const int32_t* seq_len, const int32_t* key_len, int n_seq, int n_rows,
+                              int max_len, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+/* the fp16 twins (colbert.hip and encoder_api.hip compiled a second time) */
+int tt_maxsim_f16(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs, const int64_t* d_start,
+                  const int32_t* d_len, const int32_t* cand, int n_cand, int dim, float* scores, void* stream);
+int tt_colbert_project_f16(const void* hidden, int n_rows, int H, const void* w, int dim, const int32_t* rows, int n_out, void* out,
+                           void* stream);
+int tt_attention_keylimit_f16(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
+                              const int32_t* seq_start, const int32_t* seq_len, const int32_t* key_len, int n_seq, int heads,
+                              int head_dim, int max_len, void* stream);
+int tt_encoder_forward_keylen_f16(const tt_encoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                                  const int32_t* seq_start, const int32_t* seq_len, const int32_t* key_len, int n_seq, int n_rows,
+                                  int max_len, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

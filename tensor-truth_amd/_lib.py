@@ -273,6 +273,21 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_attention_alibi_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                        c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # ColBERT late interaction (csrc/colbert.hip; the key-limited forward is encoder_api.hip's) and the fp16 twins (same signatures)
+    "tt_maxsim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                          c_void_p]),
+    "tt_colbert_project": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "tt_attention_keylimit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_int, c_int, c_int, c_void_p]),
+    "tt_encoder_forward_keylen": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_maxsim_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                              c_void_p]),
+    "tt_colbert_project_f16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "tt_attention_keylimit_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "tt_encoder_forward_keylen_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                              c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

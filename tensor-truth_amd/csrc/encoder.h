@@ -123,6 +123,9 @@ struct AttnParams {
     int qk_lo_off;            // CLS variant, f16c: Q / K are TWO fp16 planes, the lo plane qk_lo_off columns behind the hi one (0 = one plane)
 };
 int tt_attention_launch(const AttnParams& p, hipStream_t st);
+// key-limited variant (colbert.hip): every row of a sequence is a query, its first key_len[b] rows are the keys; sequences of up to
+// 128 rows; reads qk, vt, out, seq_start, seq_len, n_seq, heads, head_dim, max_len, the strides and scale
+int tt_attention_keylimit_launch(const AttnParams& p, const int32_t* key_len, hipStream_t st);
 // CLS-only variant: one query row (seq_start[b]) per sequence; out row index = sequence index
 int tt_attention_cls_launch(const AttnParams& p, hipStream_t st);
 

@@ -90,8 +90,10 @@ size_t tt_encoder_workspace_bytes(const tt_encoder_weights* w, int n_rows) {
 static int forward_impl(const tt_encoder_weights* w, const int32_t* ids, const int32_t* pos,
                         const int32_t* type_ids, const int32_t* seq_start, const int32_t* seq_len, int n_seq,
                         int n_rows, int max_len, void* hidden_out, void* cls_out, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+                        size_t workspace_bytes, void* stream, const int32_t* key_len = nullptr) {
+    // key_len (tt_encoder_forward_keylen): every layer's attention is the key-limited kernel of colbert.hip; NULL: today's path
     if (int rc = check_weights(w)) return rc;
+    TT_CHECK_ARG(key_len == nullptr || cls_out == nullptr, "key_len: the full forward only");
     TT_CHECK_ARG(n_rows > 0 && (n_rows % 128 == 0 || (n_rows < 256 && n_rows % 64 == 0)),
                  "n_rows=%d must be a positive multiple of 128 (or 64 / 192)", n_rows);
     TT_CHECK_ARG(n_seq > 0 && max_len > 0, "n_seq=%d max_len=%d", n_seq, max_len);
@@ -244,7 +246,7 @@ static int forward_impl(const tt_encoder_weights* w, const int32_t* ids, const i
         }
         // attention
         a.out = ctx; a.total_rows = n_rows;
-        if (int rc = tt_attention_launch(a, st)) return rc;
+        if (int rc = key_len ? tt_attention_keylimit_launch(a, key_len, st) : tt_attention_launch(a, st)) return rc;
         // x1 is free again after the FFN-down GEMM has consumed it as residual; the second LayerNorm's output
         // goes to the other hidden buffer (or straight to hidden_out on the last layer)
         uint16_t* x1 = (x == xa) ? xb : xa;
@@ -263,6 +265,15 @@ int tt_encoder_forward(const tt_encoder_weights* w, const int32_t* ids, const in
     TT_CHECK_ARG(hidden_out != nullptr, "null hidden_out");
     return forward_impl(w, ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, nullptr, workspace,
                         workspace_bytes, stream);
+}
+
+int tt_encoder_forward_keylen(const tt_encoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
+                              const int32_t* seq_start, const int32_t* seq_len, const int32_t* key_len, int n_seq, int n_rows,
+                              int max_len, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream) {
+    TT_CHECK_ARG(hidden_out != nullptr, "null hidden_out");
+    TT_CHECK_ARG(key_len != nullptr, "null key_len");
+    return forward_impl(w, ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, nullptr, workspace,
+                        workspace_bytes, stream, key_len);
 }
 
 size_t tt_encoder_cls_workspace_bytes(const tt_encoder_weights* w, int n_rows, int n_seq) {

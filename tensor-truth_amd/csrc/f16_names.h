@@ -7,6 +7,7 @@
 #define tt_gemm_skinny_enabled tt_gemm_skinny_enabled_f16
 #define tt_attention_launch tt_attention_launch_f16
 #define tt_attention_cls_launch tt_attention_cls_launch_f16
+#define tt_attention_keylimit_launch tt_attention_keylimit_launch_f16
 #define tt_absmax_launch tt_absmax_launch_f16
 #define tt_embed_ln_launch tt_embed_ln_launch_f16
 #define tt_layernorm_launch tt_layernorm_launch_f16
@@ -21,6 +22,7 @@
 #define tt_encoder_cls_workspace_bytes tt_encoder_cls_workspace_bytes_f16
 #define tt_encoder_forward tt_encoder_forward_f16
 #define tt_encoder_forward_cls tt_encoder_forward_cls_f16
+#define tt_encoder_forward_keylen tt_encoder_forward_keylen_f16
 #define tt_embed_pool tt_embed_pool_f16
 #define tt_embed_pool_mean tt_embed_pool_mean_f16
 #define tt_rerank_head tt_rerank_head_f16
@@ -69,3 +71,7 @@
 #define tt_jinabert_workspace_bytes tt_jinabert_workspace_bytes_f16
 #define tt_jinabert_forward tt_jinabert_forward_f16
 #define tt_attention_alibi tt_attention_alibi_f16
+// colbert.hip a second time: late-interaction scoring, projection and key-limited attention in fp16
+#define tt_maxsim tt_maxsim_f16
+#define tt_colbert_project tt_colbert_project_f16
+#define tt_attention_keylimit tt_attention_keylimit_f16

@@ -177,13 +177,23 @@ class ModelManager:
             assert self._reranker is not None
             return self._reranker
 
+    @staticmethod
+    def _reranker_class(model_name: str, model_kwargs: Optional[Dict[str, Any]]) -> type:
+        """``HipColbertRerank`` when the resolved checkpoint directory is a late-interaction one (``artifact.metadata``, or a PyLate
+        Dense module: ``colbert.detect_layout``); every other name goes to the cross-encoder class."""
+        from . import weights as _weights
+        from .colbert import HipColbertRerank, detect_layout
+        from .rerank import HipSentenceTransformerRerank
+
+        if detect_layout(_weights.find_model_dir(model_name, model_kwargs)) is not None:
+            return HipColbertRerank
+        return HipSentenceTransformerRerank
+
     def _load_reranker(self, model_name: str, top_n: int, device: str) -> None:
         try:
-            from .rerank import HipSentenceTransformerRerank
-
-            self._reranker = HipSentenceTransformerRerank(
-                model=model_name, top_n=top_n, device=device,
-                model_kwargs=self._with_precision(self.model_kwargs_overrides.get(model_name)))
+            model_kwargs = self._with_precision(self.model_kwargs_overrides.get(model_name))
+            self._reranker = self._reranker_class(model_name, model_kwargs)(
+                model=model_name, top_n=top_n, device=device, model_kwargs=model_kwargs)
             self._reranker_model_name, self._reranker_top_n, self._reranker_device = model_name, top_n, device
         except Exception as e:  # noqa: BLE001
             self._reranker = None
