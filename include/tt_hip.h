@@ -1124,6 +1124,69 @@ int tt_encoder_forward_keylen_f16(const tt_encoder_weights* w, const int32_t* id
                                   const int32_t* seq_start, const int32_t* seq_len, const int32_t* key_len, int n_seq, int n_rows,
                                   int max_len, void* hidden_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Lexical weights and hybrid scoring: BGE-M3's sparse head (csrc/lexical.hip) -----------------------------------------------
+ * BAAI/bge-m3 ships a second head, sparse_linear.pt (weight [1][H], bias [1]): the forward pass that gives the dense vector also
+ * gives a weight per token, t_i = relu(<w, h_i> + b) over the last hidden state.  A text's lexical vector holds, for every
+ * distinct token id it contains except four ids that are left out (<s>, </s>, <pad>, <unk>), the maximum of t_i over the id's
+ * occurrences, where that is > 0; lex(q, d) = sum over the ids both hold of q_w * d_w.  Passages are encoded once, when they are
+ * indexed, into CSR arrays in device memory; a query costs one short forward and a scoring kernel.  All pointers are device
+ * memory unless named _host.
+ *
+ * tt_lexical_weights: hidden [n_rows][ld] (ld >= H, even; row stride in elements) and w [H] are bf16 -- fp16 for the `_f16` twin,
+ *   fp32 for `_f32` (the reference-precision paths' hidden states); ids int32 [n_rows]: the token id of every row; seq_start,
+ *   seq_len int32 [n_seq] (tt_encoder_forward's arrays).  For sequence b, with s = seq_start[b]:
+ *     out_nnz[b]                     the number of distinct kept ids: ids other than skip0..3_host (a value that is no id, e.g. -1,
+ *                                    leaves nothing out) and not negative, whose maximum weight is > 0
+ *     out_terms[s .. s+out_nnz[b])   those ids in ascending order
+ *     out_weights[s .. s+out_nnz[b]) their weights, max over the id's rows of <w, hidden[row]> + bias_host
+ *     slots s+out_nnz[b] .. s+seq_len[b]-1 hold term -1 and weight 0.
+ *   Rows of no sequence are not written (out_terms [n_rows] int32, out_weights [n_rows] fp32; out_weights also carries the
+ *   pre-activations between the entry point's two launches).  The dot product is accumulated in fp32 -- products of the operands
+ *   converted to fp32, fmaf -- in an order that depends on H alone (lane l of a wave takes elements 128 c + 2 l and + 1 for
+ *   ascending c, then a butterfly over the 64 lanes), and the bias is added last: a sequence's output is the same bits alone or in
+ *   any batch, at any start row.  The maximum is exact (a sort of (id, weight) pairs in LDS).  H a multiple of 128 up to 1024,
+ *   max_len (>= every seq_len) 1 .. 8192, n_seq up to 65535: anything else is refused before a launch.  The sort's LDS image is
+ *   sized by max_len (64, 512, 2048 or 8192 pairs of 8 bytes); a seq_len beyond that class is clamped to it, a sequence is cut at
+ *   n_rows, and one with a negative start writes out_nnz 0 only.
+ * tt_lexical_score: for query q and candidate c, doc = cand[q * n_cand + c] (cand NULL: doc = c for every query),
+ *     out_lex[q][c]    = sum over ids in both entries of q_w * d_w
+ *     out_dense[q][c]  = <q_dense[q], d_dense[doc]>
+ *     out_hybrid[q][c] = (w_dense * out_dense + w_lex * out_lex) / (w_dense + w_lex)
+ *   all fp32 [n_q][n_cand].  Query q's entry is q_terms / q_weights [q_start[q] .. + q_nnz[q]), document doc's entry d_terms /
+ *   d_weights [d_start[doc] .. + d_nnz[doc]); terms int32, weights fp32, ASCENDING and distinct by term within an entry -- a
+ *   precondition (the output of tt_lexical_weights has it).  q_dense [n_q][dim], d_dense [n_docs][dim] bf16, indexed by document
+ *   number.  q_dense NULL: lexical only, out_dense and out_hybrid are not written (and dim, w_dense, w_lex not read).  One wave
+ *   per pair: lane l adds the products of the document's entries l, l + 64, ... that the query holds, in that order, in fp32
+ *   (fmaf), then a butterfly over the lanes; the dense part likewise over dim (bf16 operands converted to fp32, fmaf, lane l
+ *   elements 128 c + 2 l and + 1).  A pair scores the same bits wherever it sits in cand, with or without cand, in any batch.  A
+ *   negative candidate and a document with d_nnz < 0 (a tombstone) write -inf to every output that is written; d_nnz == 0 or no
+ *   shared id gives lex = 0.  dim a multiple of 128 up to 1024, w_dense, w_lex >= 0 and not both 0 (refused before a launch
+ *   otherwise).  q_nnz 0 .. 512, d_nnz -1 .. 8192: the kernel clamps a length into its range, and the host wrapper (lexical.py),
+ *   which holds the lengths, refuses one outside it.  Document numbers in cand must be < the number of documents (the wrapper
+ *   checks).
+ * tt_lexical_scan_topk: the exact lexical top-k over documents 0 .. n_docs-1 for n_q (1 .. 64) queries, k 1 .. 1024.  Scores are
+ *   tt_lexical_score's bits with cand NULL, written to the workspace (tt_lexical_scan_workspace_bytes: n_q rows of n_docs rounded
+ *   up to 32 floats); a tombstone's slot holds NaN there, which the selection never returns (what a deleted row of the dense
+ *   index scores).  Selection: tt_scan_topk_exact's.  out_scores / out_idx [n_q][k], ordered by (score descending, document
+ *   number ascending), padded with (-inf, -1); a document that shares no id with the query scores 0 and is a valid result. */
+int tt_lexical_weights(const void* hidden, int n_rows, int ld, int H, const void* w, float bias_host, const int32_t* ids,
+                       const int32_t* seq_start, const int32_t* seq_len, int n_seq, int max_len, int skip0_host, int skip1_host,
+                       int skip2_host, int skip3_host, int32_t* out_terms, float* out_weights, int32_t* out_nnz, void* stream);
+int tt_lexical_weights_f16(const void* hidden, int n_rows, int ld, int H, const void* w, float bias_host, const int32_t* ids,
+                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int max_len, int skip0_host, int skip1_host,
+                           int skip2_host, int skip3_host, int32_t* out_terms, float* out_weights, int32_t* out_nnz, void* stream);
+int tt_lexical_weights_f32(const float* hidden, int n_rows, int ld, int H, const float* w, float bias_host, const int32_t* ids,
+                           const int32_t* seq_start, const int32_t* seq_len, int n_seq, int max_len, int skip0_host, int skip1_host,
+                           int skip2_host, int skip3_host, int32_t* out_terms, float* out_weights, int32_t* out_nnz, void* stream);
+int tt_lexical_score(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                     const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, const int32_t* cand,
+                     int n_cand, const void* q_dense, const void* d_dense, int dim, float w_dense, float w_lex, float* out_lex,
+                     float* out_dense, float* out_hybrid, void* stream);
+size_t tt_lexical_scan_workspace_bytes(int64_t n_docs, int n_q);
+int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                         const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, int64_t n_docs,
+                         int k, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

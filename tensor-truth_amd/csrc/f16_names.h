@@ -75,3 +75,5 @@
 #define tt_maxsim tt_maxsim_f16
 #define tt_colbert_project tt_colbert_project_f16
 #define tt_attention_keylimit tt_attention_keylimit_f16
+// lexical.hip a second time: the lexical weights of an fp16 hidden state (the scores are fp32 / bf16 by definition: compiled once)
+#define tt_lexical_weights tt_lexical_weights_f16

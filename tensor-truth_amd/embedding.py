@@ -75,6 +75,7 @@ class HipHuggingFaceEmbedding:
         cfg, state, mdir = _weights.resolve(model_name, model_kwargs, dev, want_head=False)
         _report_unused_kwargs(model_name, model_kwargs, tokenizer_kwargs, decoder=cfg.arch == "qwen3")
         self.config = cfg
+        self.model_dir = mdir                 # the checkpoint directory (None: synthetic / state_dict weights); lexical.M3Encoder reads it
         if cfg.arch == "deberta-v2":
             raise NotImplementedError(f"{model_name}: DeBERTa-v2 / v3 checkpoints are served as cross-encoders only "
                                       "(HipSentenceTransformerRerank); a DebertaV2Model embedder is out of scope")

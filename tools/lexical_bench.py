@@ -1,0 +1,171 @@
+"""Hybrid (dense + lexical) retrieval timing, for the record: BAAI/bge-m3's geometry (XLM-R large: 24 layers,
+1024) with seeded weights, a seeded lexical head and the hashing tokenizer, one MI355X, HIP events, warm-up, median of ``--repeat``.
+
+    python tools/lexical_bench.py [--repeat 20] [--dtype bfloat16] [--scan-docs 1000000] [--out profiles/lexical_bench.jsonl]
+
+One JSON line per leg, appended to ``--out``:
+  lone_caller_stored   one query against 50 candidates that sit in the ``LexicalStore``: query encode + ``tt_lexical_score`` (lexical,
+                       dense and hybrid) between one event pair, and the wall time of ``postprocess_nodes`` (tokenise, encode,
+                       score, read back, sort)
+  cross_encoder        the cross-encoder reranker of the same box for the same job: BAAI/bge-reranker-v2-m3's geometry, one caller,
+                       50 pairs, wall time of ``predict`` -- the number the leg above stands beside (tools/colbert_bench.py's leg)
+  lexical_scan         ``tt_lexical_scan_topk`` (k = 50, one query of 8 ids) over ``--scan-docs`` documents of about 150 ids each, and
+                       its scoring kernel alone (``tt_lexical_score``, every document): bytes = n_docs * 12 + nnz * 8 against the
+                       8 TB/s of the part
+  dense_scan           the dense exact-order scan of the same box over ``--scan-docs`` x 1024 bf16 rows, k = 50, one query
+  ingest               ``M3Encoder.encode`` against ``embed_token_batches`` on the same 256 passages: the lexical ingest runs the full
+                       last layer and the head, CLS pooling runs the last layer for the CLS rows only
+with the shader clock sampled (amdsmi, read only) while the windows ran.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeat", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--candidates", type=int, default=50)
+    ap.add_argument("--passage-words", type=int, default=177)
+    ap.add_argument("--scan-docs", type=int, default=1_000_000)
+    ap.add_argument("--dtype", default="bfloat16", choices=("bfloat16", "float16"))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.dirname(here))
+    sys.path.insert(0, here)
+
+    import numpy as np
+    import torch
+    from modernbert_bench import _clock_sampler
+
+    from tensor_truth_amd import _lib, lexical
+    from tensor_truth_amd import scan as tscan
+    from tensor_truth_amd.embedding import HipHuggingFaceEmbedding
+    from tensor_truth_amd.rerank import HipSentenceTransformerRerank
+    from tensor_truth_amd.schema import NodeWithScore, TextNode
+
+    out_path = args.out or os.path.join(os.path.dirname(here), "profiles", "lexical_bench.jsonl")
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(5)
+    words = [f"w{i}" for i in range(5000)]
+
+    def text(n):
+        return " ".join(words[i] for i in rng.integers(0, len(words), n))
+
+    def emit(**rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        with open(out_path, "a") as f:
+            f.write(line + "\n")
+
+    def timed(fn):
+        """-> (median device ms between an event pair, median wall ms) of ``fn`` over --repeat runs."""
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        ev, wall = [], []
+        for _ in range(args.repeat):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            ev.append(a.elapsed_time(b))
+        return statistics.median(ev), statistics.median(wall)
+
+    emb = HipHuggingFaceEmbedding(model_name="BAAI/bge-m3", device="cuda:0", model_kwargs=dict(synthetic_seed=3, torch_dtype=args.dtype))
+    H = emb.config.hidden
+    g = torch.Generator().manual_seed(11)
+    head = (torch.randn(H, generator=g) * 0.05, -0.2)
+    rr = lexical.HipM3HybridRerank(model="BAAI/bge-m3", top_n=10, model_kwargs=dict(hybrid_weights=(0.4, 0.2), embedder=emb,
+                                                                                     sparse_head=head))
+    query = text(9)
+    passages = [text(args.passage_words) for _ in range(args.candidates)]
+
+    def nodes(prefix):
+        return [NodeWithScore(node=TextNode(text=t, id_=f"{prefix}{i}"), score=0.0) for i, t in enumerate(passages)]
+
+    rr.index_nodes(nodes("s"))
+    stored = rr.store.lookup([f"s{i}" for i in range(args.candidates)])[None]
+    base = dict(dtype=args.dtype, layers=emb.config.layers, hidden=H, candidates=args.candidates,
+                ids_per_passage=int(rr.store.n_terms / args.candidates), repeat=args.repeat)
+
+    def encode_and_score():
+        q_dense, q_lw = rr.encoder.encode([query], is_query=True)
+        return rr.store.score(q_lw, stored, dense=q_dense, hybrid_weights=rr.hybrid_weights)
+
+    clock = _clock_sampler()
+    dev_ms, _ = timed(encode_and_score)
+    _, wall_ms = timed(lambda: rr.postprocess_nodes(nodes("s"), query_str=query))
+    emit(leg="lone_caller_stored", encode_plus_score_ms=round(dev_ms, 3), postprocess_nodes_wall_ms=round(wall_ms, 3),
+         store_bytes=rr.store.nbytes, sclk_mhz=clock(), **base)
+
+    # ingest: the same 256 passages through the lexical encoder and through the embedder's own CLS path
+    batch = emb._tokenize([text(args.passage_words) for _ in range(256)], "")
+    clock = _clock_sampler()
+    m3_ms, _ = timed(lambda: rr.encoder.encode(batch, is_query=False))
+    cls_ms, _ = timed(lambda: emb.embed_token_batches(batch))
+    emit(leg="ingest", passages=len(batch), tokens=int(sum(len(s) for s in batch)), m3_encode_ms=round(m3_ms, 3),
+         embed_token_batches_ms=round(cls_ms, 3), ratio=round(m3_ms / cls_ms, 3), sclk_mhz=clock(), dtype=args.dtype, repeat=args.repeat)
+
+    # the cross-encoder of the same box for the same job (one caller, the coalescing front off: nobody to share a batch with)
+    ce = HipSentenceTransformerRerank(model="BAAI/bge-reranker-v2-m3", top_n=10, device="cuda:0", coalesce=False,
+                                      model_kwargs=dict(synthetic_seed=1, torch_dtype=args.dtype))
+    ce_pairs = [(query, text(280)) for _ in range(args.candidates)]
+    clock = _clock_sampler()
+    dev_ms, wall_ms = timed(lambda: ce.predict(ce_pairs))
+    emit(leg="cross_encoder", model="BAAI/bge-reranker-v2-m3 geometry (24 layers, 1024)", predict_event_ms=round(dev_ms, 3),
+         predict_wall_ms=round(wall_ms, 3), pairs=args.candidates, tokens_per_pair=int(ce.stats["tokens"] / max(ce.stats["pairs"], 1)),
+         sclk_mhz=clock(), dtype=args.dtype, repeat=args.repeat)
+    del ce, rr, emb
+    torch.cuda.empty_cache()
+
+    # the full lexical scan: --scan-docs documents of 100 .. 200 ascending ids below 250 002 (cumulative sums of random gaps)
+    n_docs = args.scan_docs
+    gd = torch.Generator(device=dev).manual_seed(3)
+    nnz = torch.randint(100, 201, (n_docs,), generator=gd, device=dev, dtype=torch.int32)
+    d_start = torch.zeros(n_docs, dtype=torch.int64, device=dev)
+    d_start[1:] = torch.cumsum(nnz[:-1].to(torch.int64), 0)
+    total = int(nnz.sum())
+    gaps = torch.randint(1, 1250, (total,), generator=gd, device=dev, dtype=torch.int64)
+    run = torch.cumsum(gaps, 0)
+    first = torch.repeat_interleave(run[d_start] - gaps[d_start], nnz.to(torch.int64))
+    d_terms = (run - first + 3).to(torch.int32)                    # (ascending inside a document: ids 4 .. 249 803)
+    del gaps, run, first
+    d_weights = torch.rand(total, generator=gd, device=dev) * 2 + 0.01
+    q_terms = torch.sort(torch.randint(4, 250002, (8,), generator=gd, device=dev, dtype=torch.int32)).values
+    q_weights = torch.rand(8, generator=gd, device=dev) + 0.5
+    q_start, q_nnz = np.zeros(1, dtype=np.int32), np.full(1, 8, dtype=np.int32)
+    ws = torch.empty(int(_lib.load_library().tt_lexical_scan_workspace_bytes(n_docs, 1)), dtype=torch.uint8, device=dev)
+    qs_t, qn_t = torch.from_numpy(q_start).to(dev), torch.from_numpy(q_nnz).to(dev)
+    nbytes = n_docs * 12 + total * 8
+    clock = _clock_sampler()
+    scan_ms, _ = timed(lambda: lexical.lexical_scan_topk(q_terms, q_weights, qs_t, qn_t, d_terms, d_weights, d_start, nnz, 50, workspace=ws))
+    score_ms, _ = timed(lambda: lexical.lexical_score(q_terms, q_weights, qs_t, qn_t, d_terms, d_weights, d_start, nnz))
+    emit(leg="lexical_scan", n_docs=n_docs, nnz=total, k=50, query_ids=8, bytes=nbytes, scan_topk_ms=round(scan_ms, 4),
+         score_kernel_ms=round(score_ms, 4), scan_tb_per_s=round(nbytes / scan_ms / 1e9, 3),
+         scan_fraction_of_8_tb_per_s=round(nbytes / scan_ms / 1e9 / 8.0, 4), score_tb_per_s=round(nbytes / score_ms / 1e9, 3),
+         score_fraction_of_8_tb_per_s=round(nbytes / score_ms / 1e9 / 8.0, 4), sclk_mhz=clock(), repeat=args.repeat)
+    del d_terms, d_weights, d_start, nnz, ws
+    torch.cuda.empty_cache()
+
+    # the dense scan of the same box: --scan-docs x 1024 bf16 rows, one query, k = 50
+    corpus = torch.nn.functional.normalize(torch.randn(n_docs, 1024, generator=gd, device=dev), dim=-1).to(torch.bfloat16)
+    qv = torch.nn.functional.normalize(torch.randn(1, 1024, generator=gd, device=dev), dim=-1).to(torch.bfloat16)
+    clock = _clock_sampler()
+    dense_ms, _ = timed(lambda: tscan.scan_topk(corpus, qv, 50))
+    dbytes = corpus.numel() * 2
+    emit(leg="dense_scan", n_docs=n_docs, dim=1024, k=50, bytes=dbytes, scan_topk_ms=round(dense_ms, 4),
+         tb_per_s=round(dbytes / dense_ms / 1e9, 3), fraction_of_8_tb_per_s=round(dbytes / dense_ms / 1e9 / 8.0, 4), sclk_mhz=clock(),
+         repeat=args.repeat)
+
+
+if __name__ == "__main__":
+    main()
