@@ -97,8 +97,9 @@ int tt_scan_topk_segmented(const void* corpus_bf16, int64_t n_rows, int dim,
 /* fp8 shadow of the corpus: an EXACT prefilter for the scan of a lone caller (the reference's own usage: one un-batched
  * retrieve() per query, src/tensortruth/rag_engine.py:420-424, README.md:13), where tt_scan_topk is one full read of the bf16
  * matrix (20.5 GB at 10 M x 1024: 3 ms).  The shadow block holds, for a capacity of cap_rows rows, the rows as e4m3 bytes
- * (x 256) and two floats per row -- the norm of what the rounding took and the norm of what it kept -- so that
- * |q.c - q8.c8| <= ||q|| be + ||q - q8|| dn bounds every row's exact score from above (csrc/shadow.hip).
+ * (x 256) and two floats per row -- be, the norm of what the rounding took, and dn, the norm of what it kept -- so that
+ * with d = shadow / 256 and the bf16 query q itself, q.c <= q.d + ||q|| be bounds every row's exact score from above, and
+ * 2 D 2^-23 ||q|| (dn + be) covers the fp32 accumulation of both passes (csrc/shadow.hip).
  * tt_scan_topk_shadow: threshold = k-th best exact score of a row sample (as tt_scan_topk); one pass over the SHADOW lists
  * the rows whose bound reaches it; those rows are re-scored from the bf16 matrix with tt_scan_topk's own arithmetic and the
  * same exact selection.  Scores and indices are bit-identical to tt_scan_topk's.  n_queries <= 4; rows [0, n_rows) of the

@@ -4,11 +4,12 @@
 // own usage: README.md:13, rag_engine.py:420-424).  Half the bytes carry enough to rule almost every row out:
 //     shadow[n][d] = e4m3(256 c[n][d])          one byte per element, made once when rows are added (tt_scan_shadow_build)
 //     be[n] = || c[n] - shadow[n] / 256 ||_2     what the rounding took, exactly, per row        (rounded UP)
-//     dn[n] = || shadow[n] / 256 ||_2
+//     dn[n] = || shadow[n] / 256 ||_2            what it kept (rounded UP): the scale of the fp32 rounding slack
 // For a query q (bf16, as the bf16 pass reads it):
 //     | q.c - s8 |  <=  ||q|| be            (Cauchy-Schwarz on c = d + e),     s8 = q . d,   d = shadow[n] / 256
 // so with thr = the k-th best EXACT score of a sample of rows (the bf16 pass's own threshold: k distinct rows score >= thr), every
-// true top-k row satisfies s8 + bound >= thr.  Pass 1 streams the shadow: every e4m3 byte is converted to bf16 EXACTLY (e4m3's 4
+// true top-k row satisfies s8 + bound >= thr, and with both passes' fp32 accumulation allowed for (shadow_filter_kernel's epilogue)
+// s8^ + ||q|| be + 2 D 2^-23 ||q|| (dn + be) >= thr.  Pass 1 streams the shadow: every e4m3 byte is converted to bf16 EXACTLY (e4m3's 4
 // significant bits fit bf16's 8: v_cvt_pk_f32_fp8 + one v_perm per pair, ~1 VALU operation per element, a fifth of the chip's VALU rate
 // at HBM speed) and contracted with the bf16 query on v_mfma_f32_16x16x32_bf16 -- exact products, fp32 accumulation, the arithmetic
 // model of the bf16 pass -- and the rows whose upper bound reaches thr are listed (~1 % of random rows at 10 M).  (The block-scaled
@@ -35,7 +36,10 @@ constexpr int kSWaves = 8, kSThreads = 64 * kSWaves;
 __device__ __forceinline__ float bf16_to_f32(uint16_t b) { return __uint_as_float((uint32_t)b << 16); }
 // e4m3 byte of x (saturating at +-448; NaN stays NaN) and its value back in fp32
 __device__ __forceinline__ uint32_t to_e4m3(float x) {
-    const float c = __builtin_amdgcn_fmed3f(x, -448.0f, 448.0f);     // (NaN: fmed3 returns NaN -> the conversion's NaN code)
+    // (v_med3_f32 with a NaN operand does not return NaN -- the ISA gives the minimum of the three, -448 -- and tombstones had finite
+    //  shadow bytes (tests/test_shadow_gpu.py); be was NaN all the same, through e = x - d, so no search changed.  A NaN goes round the
+    //  clamp to the conversion's NaN code.)
+    const float c = x != x ? x : __builtin_amdgcn_fmed3f(x, -448.0f, 448.0f);
     return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false) & 0xFFu;
 }
 __device__ __forceinline__ float from_e4m3(uint32_t byte) { return __builtin_amdgcn_cvt_f32_fp8((int)byte, 0); }
@@ -177,11 +181,23 @@ __global__ __launch_bounds__(kSThreads, 2) void shadow_filter_kernel(ShadowParam
         }
         const int64_t r0 = grp * 16 + g4 * 4;
         const float4 be4 = *reinterpret_cast<const float4*>(p.be + r0);
+        const float4 dn4 = *reinterpret_cast<const float4*>(p.dn + r0);
         const float bes[4] = {be4.x, be4.y, be4.z, be4.w};
+        const float dns[4] = {dn4.x, dn4.y, dn4.z, dn4.w};
+        // Rounding slack, PROPORTIONAL to the norms (an absolute 1e-4 stood here: enough for ||q|| ||c|| <~ 1, but two fp32 evaluations
+        // of a score of 900 differ by 3e-4, and rows of norm 30 that were the best match were dropped: tests/test_shadow_gpu.py).
+        // With u the unit roundoff of the MFMA's fp32 accumulation and gamma = D u (D exact products, summed in any order):
+        //     this pass:       | s8^ - q.d |  <=  gamma sum |q_i d_i|  <=  gamma ||q|| ||d||
+        //     the bf16 pass:   | s^ - q.c |   <=  gamma ||q|| ||c||    <=  gamma ||q|| (||d|| + ||e||)
+        // and thr is an s^ of the bf16 pass, so a row with s^ >= thr has  s8^ + ||q|| be + gamma ||q|| (2 ||d|| + ||e||) >= thr:
+        // the slack is 2 gamma ||q|| (dn + be).  u = 2^-23, not 2^-24: the rounding mode inside the MFMA is not documented (truncation
+        // would give 2^-23); D + 8 instead of D covers the roundings of this epilogue.  qn, be and dn are rounded up (x 1.0005).
+        // The floor is for products below 2^-126, which either pass may flush: 2 * 1024 * 2^-126 < 1e-30.
+        constexpr float kGamma2 = 2.0f * (float)(D + 8) * 1.1920928955078125e-7f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            // s8 = q . (256 d) / 256; + 1e-4: the fp32 accumulation of <= 1024 exact products (<= 1024 * 2^-24 * sum |terms| <= 6e-5)
-            const float ub = acc[r] * (1.0f / kShadowScale) + qn * bes[r] + 1e-4f;
+            // s8 = q . (256 d) / 256
+            const float ub = acc[r] * (1.0f / kShadowScale) + qn * bes[r] + (kGamma2 * qn * (dns[r] + bes[r]) + 1e-30f);
             if (qok && ub >= thr && r0 + r < p.n_rows) {       // (NaN rows: NaN bound, the compare fails)
                 const int pos = atomicAdd(&lcnt[wave * 16 + j], 1);
                 if (pos < p.capw) p.list[((size_t)j * n_waves + wg) * p.capw + pos] = (int32_t)(r0 + r);
