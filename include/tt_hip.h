@@ -246,15 +246,18 @@ int tt_encoder_forward_cls(const tt_encoder_weights* w, const int32_t* ids, cons
                            int n_seq, int n_rows, int max_len, void* cls_out,
                            void* workspace, size_t workspace_bytes, void* stream);
 
-/* sentence-transformers Pooling(cls) + Normalize: out[b] = h[rows[b]] / ||h[rows[b]]||_2.
- * out_bf16 (optional) is the same vector rounded to bf16, ready to be a scan query. */
+/* sentence-transformers Pooling(cls) + Normalize: out[b] = h[rows[b]] / max(||h[rows[b]]||_2, 1e-12): an all-zero row gives
+ * exactly the zero vector.  out_bf16 (optional; NULL: nothing is written) is out_f32 rounded to nearest even in bf16, ready to be
+ * a scan query.  Only the n_seq rows of the outputs are written.  hidden % 8 == 0 and <= 1024, else -2; ld >= hidden, ld % 8 == 0,
+ * else -1; n_seq = 0 returns 0 and writes nothing.  (The same holds for tt_embed_pool_mean and tt_embed_pool_last.) */
 int tt_embed_pool(const void* hidden_bf16, int ld, const int32_t* rows, int n_seq, int hidden,
                   float* out_f32, void* out_bf16, void* stream);
 
 /* sentence-transformers Pooling(mean) + Normalize for checkpoints whose 1_Pooling/config.json says so (e5, all-MiniLM, gte ...;
  * the reference loads any HuggingFace embedding model its config names, services/model_manager.py:188-272):
  * out[b] = mean over the sequence's rows [seq_start[b], seq_start[b] + seq_len[b]) of h, L2-normalised.  hidden: the FULL last
- * hidden state (tt_encoder_forward / _f32 / _x3), bf16 or fp32. */
+ * hidden state (tt_encoder_forward / _f32 / _x3), bf16 or fp32.  out[b] = m / max(||m||_2, 1e-12) with m the fp32 mean summed in the
+ * token order: a mean of exactly zero, and an empty sequence (seq_len[b] <= 0: no row is read), give exactly the zero vector. */
 int tt_embed_pool_mean(const void* hidden_bf16, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden,
                        float* out_f32, void* out_bf16, void* stream);
 int tt_embed_pool_mean_f32(const float* hidden_f32, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden,
@@ -262,7 +265,8 @@ int tt_embed_pool_mean_f32(const float* hidden_f32, int ld, const int32_t* seq_s
 
 /* XLMRobertaClassificationHead + CrossEncoder sigmoid on the CLS rows:
  * scores[b] = sigmoid(out_proj(tanh(dense(h[rows[b]])))) ; logits optional.
- * workspace >= 2 * round_up(n_seq,128) * H * 2 bytes. */
+ * workspace >= 2 * round_up(round_up(n_seq, 128) * H * 2, 256) bytes: the gathered rows zero-padded to
+ * round_up(n_seq, 128), then tanh(dense(.)) of them; nothing behind those bytes is written. */
 int tt_rerank_head(const tt_encoder_weights* w, const void* hidden_bf16, const int32_t* rows, int n_seq,
                    float* scores, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -350,7 +354,8 @@ int tt_encoder_forward_f32(const tt_encoder_weights_f32* w, const int32_t* ids, 
                            const int32_t* type_ids, const int32_t* seq_start, const int32_t* seq_len,
                            int n_seq, int n_rows, int max_len, float* hidden_out,
                            void* workspace, size_t workspace_bytes, void* stream);
-/* tt_embed_pool / tt_rerank_head on an fp32 hidden state (head workspace >= 2 * round_up(n_seq,128) * H * 4 bytes) */
+/* tt_embed_pool / tt_rerank_head on an fp32 hidden state (head workspace >= 2 * round_up(round_up(n_seq, 128) * H * 4, 256) bytes,
+ * laid out as tt_rerank_head's; the pooling takes any hidden > 0 and ld >= hidden, and its out_bf16 is bf16 as well) */
 int tt_embed_pool_f32(const float* hidden_f32, int ld, const int32_t* rows, int n_seq, int hidden,
                       float* out_f32, void* out_bf16, void* stream);
 int tt_rerank_head_f32(const tt_encoder_weights_f32* w, const float* hidden_f32, const int32_t* rows, int n_seq,
@@ -376,6 +381,9 @@ int tt_encoder_forward_cls_f16(const tt_encoder_weights* w, const int32_t* ids, 
                                const int32_t* type_ids, const int32_t* seq_start, const int32_t* seq_len,
                                int n_seq, int n_rows, int max_len, void* cls_out,
                                void* workspace, size_t workspace_bytes, void* stream);
+/* The pooling of an fp16 hidden state: tt_embed_pool's / tt_embed_pool_mean's contract, except that the optional 16-bit output is
+ * out_f32 rounded to nearest even in IEEE fp16 (NOT bf16: a scan query is rounded to bf16 from out_f32 by the caller).  The head's
+ * workspace is tt_rerank_head's (2-byte elements). */
 int tt_embed_pool_f16(const void* hidden_f16, int ld, const int32_t* rows, int n_seq, int hidden, float* out_f32,
                       void* out_f16, void* stream);
 int tt_embed_pool_mean_f16(const void* hidden_f16, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden,
@@ -447,6 +455,8 @@ size_t tt_encoder_x3_cls_workspace_bytes(const tt_encoder_weights_x3* w, int n_r
 int tt_encoder_forward_x3_cls(const tt_encoder_weights_x3* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                               const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len,
                               float* cls_out, void* workspace, size_t workspace_bytes, void* stream);
+/* the head of the fp32-residual paths runs on the fp32 kernels: tt_rerank_head_f32 on these fp32 head weights, bit for bit, with
+ * its workspace (also tt_rerank_head_x3_f16 and tt_rerank_head_f16c) */
 int tt_rerank_head_x3(const tt_encoder_weights_x3* w, const float* hidden_f32, const int32_t* rows, int n_seq,
                       float* scores, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 /* building blocks (parity tests).  tt_split_planes: fp32 [rows][cols] -> planes [rows][2 cols], cols % 4 == 0.
@@ -624,8 +634,10 @@ int tt_decoder_forward_rows(const tt_decoder_weights* w, const int32_t* ids, con
  * aligned; logits optional. */
 int tt_decoder_score(const void* hidden, int ld, const float* score_w, int n_seq, int hidden_size, float* scores, float* logits,
                      void* stream);
-/* sentence-transformers Pooling(lasttoken) + Normalize: out[b] = h[r] / ||h[r]||_2 with r = seq_start[b] + seq_len[b] - 1;
- * out_16 (optional) the same vector in the element type (bf16: ready to be a scan query). */
+/* sentence-transformers Pooling(lasttoken) + Normalize: out[b] = h[r] / max(||h[r]||_2, 1e-12) with r = seq_start[b] + seq_len[b] - 1;
+ * an all-zero row gives exactly the zero vector, and so does an empty sequence (seq_len[b] <= 0), of which no row is read.
+ * out_16 (optional) is out_f32 rounded to nearest even in the element type (bf16: ready to be a scan query; IEEE fp16 from
+ * tt_embed_pool_last_f16).  hidden_size % 8 == 0 and <= 1024, else -2; ld >= hidden_size, ld % 8 == 0, else -1. */
 int tt_embed_pool_last(const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int hidden_size,
                        float* out_f32, void* out_16, void* stream);
 /* building blocks (parity tests; the forward's own kernels).

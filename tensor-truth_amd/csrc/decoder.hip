@@ -112,7 +112,10 @@ __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __re
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n) return;
-    const int64_t r = (int64_t)seq_start[b] + seq_len[b] - 1;
+    // an empty sequence has no last row (the row in front of it belongs to another sequence, or lies in front of the buffer): nothing
+    // is read, and the zero vector comes out as it does for an all-zero row
+    const bool any = seq_len[b] > 0;   // (wave-uniform)
+    const int64_t r = any ? (int64_t)seq_start[b] + seq_len[b] - 1 : 0;
     const uint4* src = reinterpret_cast<const uint4*>(hidden + r * ld);
     const int nc = H / 8;
     uint4 v[2];
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __re
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = lane + 64 * j;
-        v[j] = c < nc ? src[c] : uint4{0u, 0u, 0u, 0u};
+        v[j] = any && c < nc ? src[c] : uint4{0u, 0u, 0u, 0u};
         const uint32_t u[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -465,8 +468,11 @@ int tt_embed_pool_last(const void* hidden, int ld, const int32_t* seq_start, con
     TT_CHECK_ARG(n_seq >= 0, "n_seq=%d", n_seq);
     if (n_seq == 0) return TT_OK;
     TT_CHECK_ARG(hidden && seq_start && seq_len && out_f32, "null pointer");
-    TT_CHECK_ARG(hidden_size > 0 && hidden_size % 8 == 0 && hidden_size <= 1024 && ld >= hidden_size && ld % 8 == 0,
-                 "hidden=%d ld=%d", hidden_size, ld);
+    TT_CHECK_ARG(ld >= hidden_size && ld % 8 == 0, "hidden=%d ld=%d", hidden_size, ld);
+    if (hidden_size <= 0 || hidden_size % 8 || hidden_size > 1024) {   // (the code tt_embed_pool / tt_embed_pool_mean answer with)
+        tt_set_error("tt_embed_pool_last: hidden size %d unsupported (multiple of 8, <= 1024)", hidden_size);
+        return TT_E_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream;
     TtProfScope prof(TT_K_ROWOPS, st);
     hipLaunchKernelGGL(dec_pool_last_kernel, dim3((n_seq + 3) / 4), dim3(256), 0, st, (const uint16_t*)hidden, ld, seq_start, seq_len,
