@@ -229,8 +229,12 @@ typedef struct tt_encoder_weights {
 
 size_t tt_encoder_workspace_bytes(const tt_encoder_weights* w, int n_rows);
 
-/* ids/pos/type_ids: [n_rows] int32 (type_ids may be NULL = all zero); hidden_out:
- * [n_rows][H] bf16 last hidden state.  max_len = longest sequence (host value). */
+/* ids/pos/type_ids: [n_rows] int32 (type_ids may be NULL = all zero: every row reads type row 0); hidden_out:
+ * [n_rows][H] bf16 last hidden state.  max_len = longest sequence (host value).
+ * An id, a position or a type outside its table is clamped to the nearer end (below 0: row 0; vocab, max_pos or type_vocab and
+ * beyond: the last row) -- in every forward of this header (tt_encoder_forward, _f16, _f32, _x3, _f16c and their _cls forms); no
+ * row is read outside a table.  With layers = 0 the forward is the embedding sum (word[id] + pos[p]) + type[t] in fp32 and its
+ * LayerNorm, written straight to hidden_out. */
 int tt_encoder_forward(const tt_encoder_weights* w, const int32_t* ids, const int32_t* pos,
                        const int32_t* type_ids, const int32_t* seq_start, const int32_t* seq_len,
                        int n_seq, int n_rows, int max_len, void* hidden_out,
@@ -280,9 +284,15 @@ int tt_adjacent_cosine(const float* emb_f32, int n, int hidden, float* out_dist,
  * V is passed in the token-blocked transposed layout the QKV GEMM epilogue writes,
  * vt[(row / 8) * ldvt + feature * 8 + row % 8] with ldvt = 8 * heads * head_dim. */
 /* tt_gemm_bf16: m, n multiples of 128 and k of 64 (tiled kernels), or m a multiple of 64 up to 256 with n % 16 == 0 and
- * k % 32 == 0 (weight-streaming skinny kernel; same bits as the tiled kernels for the same rows). */
+ * k % 32 == 0 (weight-streaming skinny kernel; same bits as the tiled kernels for the same rows).
+ * Non-finite pre-activations (a . w + bias): a NaN gives NaN under every epilogue, in bf16 and in fp16 (tt_gemm_f16 saturates
+ * finite values and infinities at +-65504 and keeps a NaN).  The GELU (epilogue 1) of +inf and of -inf is NaN, not +inf and -0:
+ * the fitted form computes |x| 2^Q(|x|), i.e. inf * 0; finite inputs of any size are right (GELU(3e38) = 3e38, GELU(-3e38) = 0).
+ * tanh (epilogue 3) of +-inf is +-1.  GELU and tanh of -0 give +0 or -0. */
 int tt_gemm_bf16(const void* a, const void* w, const float* bias, const void* residual, void* c,
                  int m, int n, int k, int epilogue /*0 bias,1 gelu,2 +residual,3 tanh,7 relu*/, void* stream);
+/* tt_layernorm_bf16: hidden % 8 == 0 and <= 1024, else -2; rows = 0 returns 0 and writes nothing; a row of NaN comes out as NaN
+ * and changes no other row.  (The same holds for tt_layernorm_f16 and tt_layernorm_bf16_fp8.) */
 int tt_layernorm_bf16(const void* in, void* out, const float* gamma, const float* beta, int rows, int hidden,
                       float eps, void* stream);
 int tt_attention_varlen(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out,

@@ -164,7 +164,11 @@ __device__ __forceinline__ float ebits_to_f32(uint16_t h) { return (float)__buil
 #ifndef TT_F16_SAT
 #define TT_F16_SAT 1
 #endif
-__device__ __forceinline__ float e_sat(float f) { return TT_F16_SAT ? __builtin_amdgcn_fmed3f(f, -65504.0f, 65504.0f) : f; }
+// (a NaN stays a NaN: v_med3_f32 alone turns it into -65504 -- tests/test_gemm_edges_gpu.py, test_epilogue_sweep)
+__device__ __forceinline__ float e_sat(float f) {
+    const float c = __builtin_amdgcn_fmed3f(f, -65504.0f, 65504.0f);
+    return TT_F16_SAT ? (f != f ? f : c) : f;
+}
 __device__ __forceinline__ uint16_t f32_to_ebits(float f) { return __builtin_bit_cast(uint16_t, (_Float16)e_sat(f)); }
 __device__ __forceinline__ uint32_t pack_e2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{e_sat(lo), e_sat(hi)}, f16x2_t));

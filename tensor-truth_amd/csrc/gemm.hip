@@ -885,8 +885,10 @@ __device__ __forceinline__ void epilogue_h2(const GemmParams& p, f32x4 (&acc)[2]
 }
 
 // exact-erf GELU to fp32 grade without libm: gelu(x) = max(x, 0) - |x| / 2 * erfc(|x| / sqrt 2), erfc by the Chebyshev fit
-// t exp(-z^2 + P(t)), t = 1 / (1 + z / 2) (fractional error < 1.2e-7 for every z >= 0: the error of the GELU is below
-// 1.2e-7 of the CORRECTION term, i.e. relatively accurate on both tails).  One v_rcp_f32, ten FMAs, one v_exp_f32: the libm
+// t exp(-z^2 + P(t)), t = 1 / (1 + z / 2).  The FIT's fractional error is < 1.2e-7 for every z >= 0; evaluated in fp32 the rounding of
+// the exponent's argument (near -80 at x = -10: one ulp there is 5e-6 of the result) makes it up to 1e-5 of the CORRECTION term --
+// measured against fp64 by an fp32 restatement, tests/test_mid_refs_host.py: 9.5e-7 on [-3, 0], 2.7e-6 on [-6, -3], 6.9e-6 on
+// [-9, -6], 8.4e-6 on [-12, -9] -- and 2.4e-7 absolute: still relatively accurate on both tails.  One v_rcp_f32, ten FMAs, one v_exp_f32: the libm
 // erff of epilogue_x3 made this GEMM's epilogue a quarter of its time (2.48 matrix-time units against the 1.95 of the same K
 // with a bias epilogue, profiles/r04_f16c_gemm_shapes.log).
 __device__ __forceinline__ float gelu_erfc(float x) {
