@@ -478,6 +478,20 @@ int tt_rerank_head_x3(const tt_encoder_weights_x3* w, const float* hidden_f32, c
 int tt_split_planes(const float* in_f32, int64_t rows, int cols, void* out_planes, void* stream);
 int tt_gemm_x3(const void* a_planes, const void* w_planes, const float* bias, const float* residual_f32, void* c_planes,
                float* c_f32, int m, int n, int k, int epilogue, void* stream);
+/* tt_gemm_x3_ex: a test building block, as tt_gemm_fp8_ex is -- tt_gemm_x3 with the layouts and epilogues the forward itself
+ * uses.  Epilogues 0 / 1 write c_planes [m][ldc], hi at column 0 and lo at column c_lo_off (c_lo_off >= n, ldc >= c_lo_off + n;
+ * the forward's Q | K projection: ldc = 4 H, c_lo_off = 2 H); epilogue 2 writes c_f32 [m][ldc] = a.w^T + bias + residual, the
+ * residual EITHER as residual_f32 [m][ldr] OR as residual_planes [m][ldr] (hi at column 0, lo at column res_lo_off: hi + lo is
+ * rebuilt in fp32 -- the forward on fp16 planes: ldr = 2 H, res_lo_off = H); epilogue 5 (V^T) writes the V8 layout of
+ * tt_attention_varlen twice, vt_hi and vt_lo [m / 8][ldvt >= 8 n], element (m, n) at (m / 8) * ldvt + 8 n + m % 8.  Arguments
+ * an epilogue does not use may be NULL / 0.  Shapes as tt_gemm_x3: up to 256 rows m % 64 == 0, n % 16 == 0, k % 32 == 0;
+ * beyond that m % 256 == 0, n % 64 == 0, k % 64 == 0, k >= 128; leading dimensions and offsets keep 16-byte alignment.
+ * Non-finite pre-activations (tests/test_gemm_x3_edges_gpu.py): a NaN stays a NaN in both planes.  Epilogue 0 (and 5: the same
+ * packing) splits +-inf as the host does: bf16 planes hi = +-inf, lo = NaN; fp16 planes hi = lo = +-65504 (both saturate: finite values up to +-131008 are
+ * carried as 65504 + the rest).  The GELU of +inf is that split of +inf; of -inf, NaN in both planes (inf * 0). */
+int tt_gemm_x3_ex(const void* a_planes, const void* w_planes, const float* bias, const float* residual_f32,
+                  const void* residual_planes, int ldr, int res_lo_off, void* c_planes, int ldc, int c_lo_off, float* c_f32,
+                  void* vt_hi, void* vt_lo, int ldvt, int m, int n, int k, int epilogue, void* stream);
 int tt_attention_x3(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi,
                     const void* vt_lo, int ldvt, void* out_planes, int ld_out, int out_lo_off,
                     const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len, void* stream);
@@ -564,7 +578,8 @@ int tt_attention_f16c(const void* qk_f16, int ld_qk, int q_col0, int k_col0, int
 
 /* ---- "f16x3": the split-plane forward above with fp16 planes (csrc/x3_path.hip compiled a second time, round 4) -------
  * Same entry points, same layouts, `_f16` suffix: a value is carried as hi = fp16(x), lo = fp16(x - hi) -- 22 significand
- * bits per operand instead of the two bf16 planes' 16 -- and a product as three v_mfma_*_f16 products.  It is the DEFAULT
+ * bits per operand instead of the two bf16 planes' 16, down to fp16's subnormal grid: |x - hi - lo| <= max(2^-22 |x|, 2^-25)
+ * inside +-65504 (the lo plane is an fp16 subnormal for every |x| < 2^-3) -- and a product as three v_mfma_*_f16 products.  It is the DEFAULT
  * implementation of the reference precision: on weights with trained-model statistics (attention logits of ~100, scores
  * down to 0.005: tests/stress_weights.py) it holds 1e-3 relative with a margin where bf16x3 sits AT the bar and the
  * two-unit f16c path is 7x outside.  Values beyond +-65504 saturate in the hi plane (the lo plane takes what is left). */
@@ -582,6 +597,9 @@ int tt_rerank_head_x3_f16(const tt_encoder_weights_x3* w, const float* hidden_f3
 int tt_split_planes_f16(const float* in_f32, int64_t rows, int cols, void* out_planes, void* stream);
 int tt_gemm_x3_f16(const void* a_planes, const void* w_planes, const float* bias, const float* residual_f32, void* c_planes,
                    float* c_f32, int m, int n, int k, int epilogue, void* stream);
+int tt_gemm_x3_ex_f16(const void* a_planes, const void* w_planes, const float* bias, const float* residual_f32,
+                      const void* residual_planes, int ldr, int res_lo_off, void* c_planes, int ldc, int c_lo_off, float* c_f32,
+                      void* vt_hi, void* vt_lo, int ldvt, int m, int n, int k, int epilogue, void* stream);
 int tt_attention_x3_f16(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi,
                         const void* vt_lo, int ldvt, void* out_planes, int ld_out, int out_lo_off,
                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int heads, int max_len, void* stream);

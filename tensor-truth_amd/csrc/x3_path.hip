@@ -831,6 +831,40 @@ int tt_gemm_x3(const void* a_planes, const void* w_planes, const float* bias, co
     return tt_gemm_launch(g, epilogue, (hipStream_t)stream);
 }
 
+// tt_gemm_x3 with the layouts and epilogues forward_x3_impl uses (test building block): the planes output's own ldc / c_lo_off
+// (Q | K: ldc = 4H, c_lo_off = 2H), the residual as fp32 rows or as the planes of the activation (ldr, res_lo_off), and the V^T
+// epilogue (5) into the V8 hi / lo buffers.  The shape and alignment checks are launch_x3's; what is added here keeps every
+// store inside the rows the caller names (a lo plane that would overlap the hi plane's columns, a V8 row shorter than 8 n).
+int tt_gemm_x3_ex(const void* a_planes, const void* w_planes, const float* bias, const float* residual_f32, const void* residual_planes,
+                  int ldr, int res_lo_off, void* c_planes, int ldc, int c_lo_off, float* c_f32, void* vt_hi, void* vt_lo, int ldvt,
+                  int m, int n, int k, int epilogue, void* stream) {
+    TT_CHECK_ARG(a_planes && w_planes && bias, "null pointer");
+    TT_CHECK_ARG(epilogue == TT_EPI_BIAS || epilogue == TT_EPI_GELU || epilogue == TT_EPI_RESIDUAL || epilogue == TT_EPI_VT,
+                 "epilogue %d (0 bias, 1 GELU, 2 residual, 5 V^T)", epilogue);
+    TT_CHECK_ARG(m > 0 && n > 0 && k > 0, "m=%d n=%d k=%d", m, n, k);
+    GemmParams g = gemm_x3(a_planes, w_planes, bias, m, n, k);
+    if (epilogue == TT_EPI_RESIDUAL) {
+        TT_CHECK_ARG(c_f32 && ldc >= n, "residual epilogue: fp32 output [m][ldc >= n]");
+        TT_CHECK_ARG((residual_f32 != nullptr) != (residual_planes != nullptr), "residual epilogue: the fp32 residual or its planes, not both");
+        g.C32 = c_f32; g.ldc = ldc; g.ldr = ldr;
+        if (residual_planes) {
+            TT_CHECK_ARG(res_lo_off >= n && ldr >= res_lo_off + n, "residual planes: res_lo_off=%d ldr=%d at n=%d", res_lo_off, ldr, n);
+            g.res_planes = (const uint16_t*)residual_planes; g.res_lo_off = res_lo_off;
+        } else {
+            TT_CHECK_ARG(ldr >= n, "fp32 residual: ldr=%d < n=%d", ldr, n);
+            g.res32 = residual_f32;
+        }
+    } else if (epilogue == TT_EPI_VT) {
+        TT_CHECK_ARG(vt_hi && vt_lo && ldvt >= 8 * n && m % 8 == 0, "V^T epilogue: vt_hi, vt_lo [m / 8][ldvt >= 8 n]");
+        g.vt = (uint16_t*)vt_hi; g.vt_lo = (uint16_t*)vt_lo; g.ldvt = ldvt; g.vt_col0 = 0;
+        g.ldc = 2 * n; g.c_lo_off = n;      // (not read by this epilogue)
+    } else {
+        TT_CHECK_ARG(c_planes && c_lo_off >= n && ldc >= c_lo_off + n, "planes output: c_lo_off=%d ldc=%d at n=%d", c_lo_off, ldc, n);
+        g.C = (uint16_t*)c_planes; g.ldc = ldc; g.c_lo_off = c_lo_off;
+    }
+    return tt_gemm_launch(g, epilogue, (hipStream_t)stream);
+}
+
 int tt_attention_x3(const void* qk_planes, int ld_qk, int q_col0, int k_col0, int lo_off, const void* vt_hi, const void* vt_lo,
                     int ldvt, void* out_planes, int ld_out, int out_lo_off, const int32_t* seq_start, const int32_t* seq_len,
                     int n_seq, int heads, int max_len, void* stream) {

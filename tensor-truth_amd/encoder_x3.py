@@ -8,7 +8,8 @@ one meets it at 1/3: every matrix product runs on the bf16 matrix cores with bot
 LayerNorm, softmax, exact-erf GELU, classification head) stays fp32.  Selected by ``precision.resolve()`` -- the process
 setting ``TT_PRECISION=reference``, ``ModelManager``'s ``precision`` config key, or ``model_kwargs={"torch_dtype":
 "float32"}`` -- whenever the model shape fits (``supports``: hidden a multiple of 128 with 64- or 32-wide heads); other
-shapes fall back to ``encoder_f32``.  The planes are bf16 ("bf16x3") or fp16 ("f16x3", the default implementation).
+shapes fall back to ``encoder_f32``.  The planes are bf16 ("bf16x3", 16 significand bits per operand) or fp16 ("f16x3", the
+default implementation: 22 bits down to fp16's subnormal grid, ``|x - hi - lo| <= max(2^-22 |x|, 2^-25)`` inside +-65504).
 ``encoder.Encoder`` runs it (``EncoderX3`` is that class) with the 16-bit path's token packing and surface.
 """
 from __future__ import annotations
@@ -45,7 +46,10 @@ def supports(cfg: EncoderConfig) -> bool:
 
 def split_planes(w: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """fp32 [out][in] -> planes [out][2 in] of ``dtype``: hi = dtype(w), lo = dtype(w - hi) side by side (``GemmParams.x3``).
-    bfloat16: "bf16x3" (16 significand bits per operand); float16: "f16x3" (22; values beyond +-65504 saturate in hi)."""
+    bfloat16: "bf16x3" (16 significand bits per operand); float16: "f16x3" (22, down to fp16's subnormal grid:
+    ``|w - hi - lo| <= max(2^-22 |w|, 2^-25)`` inside +-65504 -- lo is an fp16 subnormal for every ``|w| < 2^-3``; values beyond
+    +-65504 saturate in hi and lo takes what is left, up to +-131008).  The device split of the activations (``tt_split_planes*``,
+    the GEMM and LayerNorm epilogues) gives the same bits: tests/test_gemm_x3_edges_gpu.py."""
     w = w.to(torch.float32)
     if dtype == torch.float16:
         hi = w.clamp(-65504.0, 65504.0).to(torch.float16)
