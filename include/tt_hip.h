@@ -1228,6 +1228,42 @@ int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const i
                          const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, int64_t n_docs,
                          int k, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Multi-vector head: BGE-M3's third head, late interaction at the model's own width (csrc/multivec.hip) ----------------------
+ * BAAI/bge-m3 ships colbert_linear.pt (weight [dim][H], bias [dim]; dim = H = 1024): every token row but the first is projected,
+ * biased and L2-normalised; mv(q, d) is the MEAN over the query's vectors of the maximum dot product with the document's.  The
+ * late-interaction kernels above stop at dim 128, 128 query and 512 document rows, and have no bias; these are their wide forms.
+ * All pointers are device memory; 16-bit operands are bf16 -- or fp16 for the `_f16` twins.
+ *
+ * tt_multivec_project: for n < n_out, y = W hidden[rows[n]] + bias (hidden [n_rows][ld], ld >= H a multiple of 8 elements (4 for
+ *   `_f32`); W [dim][H]; bias fp32 [dim]; fp32 accumulation, the bias added to the fp32 sum), out[n] = y / max(||y||_2, 1e-12) in
+ *   fp32 -- one division, one rounding to the output type; out [n_out][dim].  The squared norm is summed in fp32 in an order that
+ *   depends on dim alone, so a row's bits depend neither on n_out, nor on its place in rows, nor on what else the launch holds.
+ *   A row number outside [0, n_rows) gives a zero row (no bias); y = 0 gives 0.  H and dim each a multiple of 128 up to 1024
+ *   (anything else is refused before a launch).  `_f32`: fp32 hidden states and fp32 W (the reference-precision paths) on the fp32
+ *   MFMA, out in fp16 -- unit vectors fit fp16's range, and tt_maxsim_wide_f16 scores them.
+ * tt_maxsim_wide: tt_maxsim's arguments and contract -- scores[q][c] = sum over i < q_len[q] of max over j < d_len[doc] of
+ *   <Q[q_start[q] + i], D[d_start[doc] + j]>, doc = cand[q * n_cand + c] (cand NULL: doc = c); fp32 accumulation of exact 16-bit
+ *   products; a token's maximum starts at -inf and rows past d_len are masked to -inf; the q_len maxima are added in index order
+ *   in fp32; a negative candidate writes -inf, a document of length 0 scores 0; a score depends on its own pair alone -- plus
+ *   `mean`: non-zero divides the sum by (float)q_len, one more rounding.  dim a multiple of 128 up to 1024 (refused otherwise);
+ *   q_len 1 .. 512, d_len 0 .. 8192: the kernel clamps a length into its range, and the host wrapper (multivec.py), which holds
+ *   the lengths, refuses one outside it.
+ * tt_m3_mix: out[i] = (w_dense dense[i] + w_lex lex[i] + w_mv mv[i]) / (w_dense + w_lex + w_mv) for i < n, fp32; -inf in any input
+ *   gives -inf.  Weights >= 0, finite and not all 0 (refused otherwise). */
+int tt_multivec_project(const void* hidden, int n_rows, int ld, int H, const void* w, const float* bias, int dim, const int32_t* rows,
+                        int n_out, void* out, void* stream);
+int tt_multivec_project_f16(const void* hidden, int n_rows, int ld, int H, const void* w, const float* bias, int dim,
+                            const int32_t* rows, int n_out, void* out, void* stream);
+int tt_multivec_project_f32(const float* hidden, int n_rows, int ld, int H, const float* w, const float* bias, int dim,
+                            const int32_t* rows, int n_out, void* out, void* stream);
+int tt_maxsim_wide(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs, const int64_t* d_start,
+                   const int32_t* d_len, const int32_t* cand, int n_cand, int dim, int mean, float* scores, void* stream);
+int tt_maxsim_wide_f16(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs,
+                       const int64_t* d_start, const int32_t* d_len, const int32_t* cand, int n_cand, int dim, int mean, float* scores,
+                       void* stream);
+int tt_m3_mix(const float* dense, const float* lex, const float* mv, int64_t n, float w_dense, float w_lex, float w_mv, float* out,
+              void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

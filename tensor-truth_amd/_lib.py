@@ -304,6 +304,17 @@ SIGNATURES = {
     "tt_lexical_scan_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "tt_lexical_scan_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # BGE-M3's multi-vector head (csrc/multivec.hip): the wide projection (bf16 / fp16 / fp32 in), the wide MaxSim, the three-way mix
+    "tt_multivec_project": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "tt_multivec_project_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                        c_void_p]),
+    "tt_multivec_project_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                        c_void_p]),
+    "tt_maxsim_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                               c_void_p, c_void_p]),
+    "tt_maxsim_wide_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_void_p, c_void_p]),
+    "tt_m3_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

@@ -625,12 +625,16 @@ class TokenVectorStore:
     id only -- the rows stay where they are and are NOT reclaimed (there is no compaction in this version; re-adding an id
     appends a new copy).  No persistence."""
 
+    # the limits of the kernel that scores the store (``tt_maxsim``); ``multivec.MultiVectorStore`` carries ``tt_maxsim_wide``'s
+    DIM_STEP, DIM_LIMIT, DOC_LIMIT = 32, MAX_DIM, MAX_DOC_LEN
+
     def __init__(self, dim: int, dtype: torch.dtype, device: torch.device, capacity_tokens: int = 1 << 16, capacity_docs: int = 1 << 10):
         _suffix(dtype)
-        if dim <= 0 or dim % 32 or dim > MAX_DIM:
-            raise ValueError(f"TokenVectorStore: dim={dim} (a multiple of 32 up to {MAX_DIM})")
+        name = type(self).__name__
+        if dim <= 0 or dim % self.DIM_STEP or dim > self.DIM_LIMIT:
+            raise ValueError(f"{name}: dim={dim} (a multiple of {self.DIM_STEP} up to {self.DIM_LIMIT})")
         if device.type != "cuda":
-            raise RuntimeError("TokenVectorStore lives on a HIP device; tensor_truth_amd has no CPU path")
+            raise RuntimeError(f"{name} lives on a HIP device; tensor_truth_amd has no CPU path")
         self.dim, self.dtype, self.device = dim, dtype, device
         self.vectors = torch.empty((max(capacity_tokens, 1), dim), dtype=dtype, device=device)
         self.d_start = torch.zeros(max(capacity_docs, 1), dtype=torch.int64, device=device)
@@ -658,7 +662,7 @@ class TokenVectorStore:
         lens = np.ascontiguousarray(lens, dtype=np.int32)
         if len(node_ids) != len(lens):
             raise ValueError("add: one length per node id is needed")
-        _check_range("lens", lens, 0, MAX_DOC_LEN)
+        _check_range("lens", lens, 0, self.DOC_LIMIT)
         total = int(lens.sum())
         if vectors.dtype != self.dtype or vectors.dim() != 2 or tuple(vectors.shape) != (total, self.dim):
             raise ValueError(f"add: vectors {tuple(vectors.shape)} {vectors.dtype} do not match [{total}][{self.dim}] {self.dtype}")

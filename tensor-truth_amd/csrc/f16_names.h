@@ -79,3 +79,6 @@
 #define tt_attention_keylimit tt_attention_keylimit_f16
 // lexical.hip a second time: the lexical weights of an fp16 hidden state (the scores are fp32 / bf16 by definition: compiled once)
 #define tt_lexical_weights tt_lexical_weights_f16
+// multivec.hip a second time: the wide projection and the wide MaxSim on fp16 vectors (the _f32 projection and the mix: compiled once)
+#define tt_multivec_project tt_multivec_project_f16
+#define tt_maxsim_wide tt_maxsim_wide_f16

@@ -12,7 +12,7 @@ lexical score is the sum over shared ids of the two weights, and the hybrid scor
 [1][H] and ``bias`` [1]; ``_process_token_weights``: the maximum per id, the four special ids and weights <= 0 left out;
 ``compute_lexical_matching_score``; "dense+sparse" in ``compute_score``), which is not installed here and cannot be checked offline.
 The loader is therefore strict: a key or a shape it does not know is refused by name, and the two mixing weights are never
-defaulted.  ``colbert_linear.pt`` (the model's multi-vector head) may be present and is not read.
+defaulted.  ``colbert_linear.pt`` (the model's multi-vector head) may be present and is not read here: ``multivec.py`` reads it.
 
 The dot product is accumulated in fp32 and the weight kept in fp32; upstream's fp16 mode rounds it to fp16.
 """
@@ -352,7 +352,12 @@ class M3Encoder:
         _lib.check(rc, p.pool)
         ids = torch.from_numpy(batch.ids).to(dev)
         terms, weights, nnz = lexical_weights(hidden, self.w, self.bias, ids, starts, lens, self.skip, max_len=batch.max_len)
+        self._after_forward(hidden, batch)
         return dense, terms, weights, batch.seq_start, nnz
+
+    def _after_forward(self, hidden: torch.Tensor, batch) -> None:
+        """What a subclass reads from a batch's hidden state beside the two heads here (``multivec.M3MultiVectorEncoder``: the
+        token vectors).  Nothing in this class."""
 
     def encode(self, items, is_query: bool = False) -> Tuple[torch.Tensor, LexicalWeights]:
         """``items``: strings (the embedder's query / text instruction is put in front, as its own methods do), or token-id
