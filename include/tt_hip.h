@@ -1264,6 +1264,44 @@ int tt_maxsim_wide_f16(const void* q_vecs, const int32_t* q_start, const int32_t
 int tt_m3_mix(const float* dense, const float* lex, const float* mv, int64_t n, float w_dense, float w_lex, float w_mv, float* out,
               void* stream);
 
+/* ---- SPLADE: learned sparse vectors from a masked-language-model head (csrc/splade.hip) ------------------------------------------
+ * A SPLADE checkpoint is a BertForMaskedLM; a text's weight for vocabulary id v is max over its tokens t of
+ * log1p(relu(logit[t][v])), so a text activates ids it does not contain.  The logits ([rows][vocabulary]: 61 KB per token for
+ * BERT-base in bf16) are never written: the vocabulary projection and the maximum over a sequence's rows are one kernel.  What comes
+ * out is what the lexical kernels above take: ascending (id, weight) entries.  All pointers are device memory; 16-bit operands are
+ * bf16 -- or fp16 for the `_f16` twin.
+ *
+ * tt_splade_pool: t [n_rows][ld] (ld >= H, a multiple of 8 elements) holds the TRANSFORMED hidden states -- the rows after the head's
+ *   dense -> GELU -> LayerNorm, which the caller computes with tt_gemm_* (epilogue 1) and tt_layernorm_* -- E [Vp][H] the decoder
+ *   matrix in the same type, bias fp32 [Vp], out fp32 [n_seq][ldo] with ldo >= Vp.  For sequence b and column v < Vp, with
+ *     m = max over the rows r in [seq_start[b], seq_start[b] + seq_len[b]) and in [0, n_rows) of (fp32 sum_k t[r][k] E[v][k]),
+ *     activation 0:  out[b][v] = m + bias[v]
+ *     activation 1:  out[b][v] = log1pf(max(0, m + bias[v]))
+ *   (columns Vp .. ldo-1 are not written).  The bias is added after the maximum, and relu and log1p applied once per column: fp32
+ *   rounding, relu and log1p are monotone, so these are the bits of applying them to every row first.  A sequence with no rows
+ *   (length <= 0, a negative start, a start >= n_rows) writes -inf under activation 0 and 0 under activation 1; a seq_len beyond
+ *   max_len is clamped to it.  A row's fp32 sum is ONE chain of mfma_f32_16x16x32 over k = 0, 32, .. H-32 from a zero accumulator: it
+ *   depends on H alone -- not on the row's place in its sequence, nor on whether the sequence fills one pass of 64 rows or several --
+ *   and the maximum is exact, associative and commutative.  A sequence's output is therefore the same bits alone or in any batch,
+ *   at any start row, in any launch geometry.  Non-finite hidden states, as built: the maximum is fmaxf's, which passes over a NaN,
+ *   so a row whose sum for a column is NaN takes no part in that column (if every row's is, the column is that of a sequence with no
+ *   rows); a sum of +inf wins and gives +inf under either activation; a NaN never reaches another sequence.  A NaN bias gives NaN
+ *   under activation 0 and 0 under activation 1.  H a multiple of 128 up to 1024, Vp a multiple of 128 up to 65536, max_len
+ *   1 .. 8192, n_seq up to 65535: anything else is refused before a launch (TT_E_UNSUPPORTED).
+ * tt_sparse_compact: w fp32 [n_seq][ldw], V <= ldw the true vocabulary size (ids >= V -- a loader's padding -- are never read).  Row
+ *   b's entries with w > 0 are kept (decided on the bits: a denormal is kept, a NaN, a zero of either sign and a negative are not);
+ *   if more than max_terms qualify, the max_terms largest by (weight descending, id ascending) -- sentence-transformers'
+ *   max_active_dims.  out_terms[b * max_terms ..] holds the kept ids in ASCENDING order, out_weights their weights (unchanged bits),
+ *   out_nnz[b] their number; the slots behind them hold (-1, 0).  That is tt_lexical_score's precondition.  Deterministic: the only
+ *   atomics are integer histogram counts, whose order of arrival does not show.  V 1 .. 65536, max_terms 1 .. 8192 (refused
+ *   otherwise). */
+int tt_splade_pool(const void* t, int n_rows, int ld, int H, const void* E, const float* bias, int Vp, const int32_t* seq_start,
+                   const int32_t* seq_len, int n_seq, int max_len, int activation, float* out, int ldo, void* stream);
+int tt_splade_pool_f16(const void* t, int n_rows, int ld, int H, const void* E, const float* bias, int Vp, const int32_t* seq_start,
+                       const int32_t* seq_len, int n_seq, int max_len, int activation, float* out, int ldo, void* stream);
+int tt_sparse_compact(const float* w, int ldw, int V, int n_seq, int max_terms, int32_t* out_terms, float* out_weights, int32_t* out_nnz,
+                      void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream), for bench.py's roofline leg.
  * tt_prof_enable(1) (or a mask of 1 << id, to time only some kernels) starts recording one event pair per launch of the tracked kernels on the
  * calling thread; tt_prof_read() synchronises those events and returns total milliseconds

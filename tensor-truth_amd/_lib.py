@@ -315,6 +315,12 @@ SIGNATURES = {
     "tt_maxsim_wide_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_void_p, c_void_p]),
     "tt_m3_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_void_p]),
+    # SPLADE (csrc/splade.hip): the vocabulary projection with its segmented maximum (bf16 / fp16), the sparse compaction
+    "tt_splade_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                               c_void_p, c_int, c_void_p]),
+    "tt_splade_pool_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_void_p, c_int, c_void_p]),
+    "tt_sparse_compact": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tt_prof_enable": (c_int, [c_int]),
     "tt_prof_read": (c_int, [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)]),
 }

@@ -82,3 +82,5 @@
 // multivec.hip a second time: the wide projection and the wide MaxSim on fp16 vectors (the _f32 projection and the mix: compiled once)
 #define tt_multivec_project tt_multivec_project_f16
 #define tt_maxsim_wide tt_maxsim_wide_f16
+// splade.hip a second time: the vocabulary projection with its segmented maximum on fp16 operands (the compaction is fp32: compiled once)
+#define tt_splade_pool tt_splade_pool_f16
