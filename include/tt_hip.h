@@ -1228,6 +1228,59 @@ int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const i
                          const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, int64_t n_docs,
                          int k, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Posting lists: an exact candidate generator for the lexical scan (csrc/postings.hip) --------------------------------------
+ * tt_lexical_scan_topk scores every document for every query.  A document that shares no id with a query scores +0 (or is a
+ * tombstone), so the only documents that can score above zero are those on the posting lists of the query's own ids.  These
+ * entry points build such lists from the stores' CSR arrays and run the scan's own scoring kernel and the scan's own selection
+ * over the union of chosen lists: what they return for a document is tt_lexical_scan_topk's bits.  WHICH lists to take, and whether
+ * the candidates are known to hold the whole top-k, is the caller's decision (postings.py: thr_out > 0; MaxScore bounds from
+ * term_ub) -- nothing here prunes.  All pointers are device memory.
+ *
+ * tt_postings_build: documents 0 .. n_sealed-1 of d_terms / d_weights / d_start (int64) / d_nnz (tt_lexical_score's arrays; d_nnz
+ *   < 0: a tombstone, skipped whole; d_nnz clamped to 8192 as the scoring kernel clamps it) and a vocabulary size give
+ *     post_off int64 [vocab + 1]   list t is post_doc[post_off[t] .. post_off[t + 1]); post_off[vocab] = the number of entries
+ *     post_doc int32 [post_cap]    the documents holding id t, each once per occurrence, in NO specified order inside a list
+ *     term_ub  fp32  [vocab]       the maximum over list t of the stored weights that are finite and >= 0; 0 for an empty list
+ *     flags    int32 [1]           bit 0: a term outside [0, vocab) was met; bit 1: a weight that is negative, NaN or infinite;
+ *                                  bit 2: a document whose ids are not strictly ascending (tt_lexical_score's precondition; a
+ *                                  repeated id is scored once per occurrence, so term_ub would not bound its contribution)
+ *   Histogram (integer atomicAdd per entry), exclusive scan, fill (the counts run back down: a slot per entry), per-term maximum
+ *   (integer atomicMax on the bits of a non-negative float).  post_cap must be >= the live entries; the number of stored entries,
+ *   live or dead, is such a bound.  The call synchronises the stream ONCE, after the scan, to read flags and the total: bit 0 or a
+ *   total beyond post_cap fails it (TT_E_INVALID, tt_last_error) before anything is filled, and the fill writes no slot at or
+ *   behind post_cap whatever the counters hold.  Bits 1 and 2 do not fail the build: either says term_ub bounds nothing (the caller
+ *   must not prune; the lists themselves are complete, a repeated id lists its document once per occurrence).  Workspace: tt_postings_build_workspace_bytes (vocab counters).  vocab >= 1, n_sealed 0 .. INT_MAX - 64.
+ * tt_lexical_topk_postings: for each of n_q (1 .. 64) queries, k 1 .. 1024 (anything else is refused before a launch, as
+ *   tt_lexical_scan_topk refuses it), the caller lists ranges of post_doc: query q owns ranges r in [range_start[q],
+ *   range_start[q + 1]) (int32 [n_q + 1]), range r is post_doc[range_lo[r] .. range_hi[r]) (int64, cut to [0, post_len); a listed
+ *   document number outside [0, n_sealed) is ignored).  Per query:
+ *     1. a bitmap of n_sealed bits is ORed from the ranges (integer atomicOr);
+ *     2. it is compacted to an ASCENDING int32 list -- popcounts per span of TT_POSTINGS_SPAN documents, an exclusive scan, then
+ *        every span writes from its own offset: no atomic decides a position, the list is a function of the bitmap alone;
+ *     3. documents n_sealed .. n_docs-1 (the unsealed tail) are appended whole; cand_cnt_out[q] = the list's length;
+ *     4. the list is scored by tt_lexical_score's kernel (a tombstone: NaN, as in the scan's workspace) and tt_lexical_scan_topk's
+ *        selection picks the top k: out_scores / out_idx [n_q][k] ordered by (score descending, document number ascending),
+ *        padded with (-inf, -1); thr_out[q] = the k-th best score or -inf when fewer than k candidates rank; cnt_out[q] = how
+ *        many rank.
+ *   The result equals tt_lexical_scan_topk's restricted to the listed documents and the tail, bit for bit; it equals the
+ *   unrestricted one whenever every document outside the list scores below thr_out[q] (with ranges covering all of a query's
+ *   ids: whenever thr_out[q] > 0).  grid_entries sizes the grids only (the longest sum of range lengths of any query, as far as
+ *   the caller knows it; every walk is grid-strided, so any value gives the same output).  Workspace per query
+ *   (tt_lexical_topk_postings_workspace_bytes): the bitmap, n_docs int32 candidates and n_docs fp32 scores.  n_docs 0 ..
+ *   INT_MAX - 64, n_sealed 0 .. n_docs; n_docs == 0 writes the padding and thr_out -inf. */
+#define TT_POSTINGS_SPAN 8192
+size_t tt_postings_build_workspace_bytes(int vocab);
+int tt_postings_build(const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, int64_t n_sealed,
+                      int vocab, int64_t* post_off, int32_t* post_doc, int64_t post_cap, float* term_ub, int32_t* flags,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t tt_lexical_topk_postings_workspace_bytes(int64_t n_docs, int64_t n_sealed, int n_q);
+int tt_lexical_topk_postings(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                             const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, int64_t n_docs,
+                             const int32_t* post_doc, int64_t post_len, int64_t n_sealed, const int64_t* range_lo,
+                             const int64_t* range_hi, const int32_t* range_start, int64_t grid_entries, int k, float* out_scores,
+                             int32_t* out_idx, float* thr_out, int32_t* cnt_out, int32_t* cand_cnt_out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- Multi-vector head: BGE-M3's third head, late interaction at the model's own width (csrc/multivec.hip) ----------------------
  * BAAI/bge-m3 ships colbert_linear.pt (weight [dim][H], bias [dim]; dim = H = 1024): every token row but the first is projected,
  * biased and L2-normalised; mv(q, d) is the MEAN over the query's vectors of the maximum dot product with the document's.  The

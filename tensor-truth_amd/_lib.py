@@ -304,6 +304,14 @@ SIGNATURES = {
     "tt_lexical_scan_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "tt_lexical_scan_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # posting lists over the lexical / SPLADE stores (csrc/postings.hip): the build, and the scan's top-k over a query's lists
+    "tt_postings_build_workspace_bytes": (c_size_t, [c_int]),
+    "tt_postings_build": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_lexical_topk_postings_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "tt_lexical_topk_postings": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # BGE-M3's multi-vector head (csrc/multivec.hip): the wide projection (bf16 / fp16 / fp32 in), the wide MaxSim, the three-way mix
     "tt_multivec_project": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "tt_multivec_project_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,

@@ -4,6 +4,7 @@
 //   tt_lexical_score               lex[q][c] = sum over shared ids of q_w * d_w, the dense dot product and their weighted mean, over
 //                                  entries that already sit in device memory
 //   tt_lexical_scan_topk           that lexical score for every stored document, then the library's exact selection (select.hip)
+//   tt_lexical_score_lists         (internal, scan.h) the scan's lexical scores over per-query candidate lists, for postings.hip
 //
 // Compiled twice like the encoder path (common.h TT_F16): the bf16 object holds everything; the fp16 object only
 // tt_lexical_weights (as tt_lexical_weights_f16, f16_names.h), the one entry point whose operands are 16-bit hidden states.
@@ -176,9 +177,10 @@ constexpr int kMaxQueryNnz = 512, kMaxDocNnz = 8192;
 __global__ __launch_bounds__(64 * kScoreWaves) void lexical_score_kernel(
     const int32_t* __restrict__ q_terms, const float* __restrict__ q_weights, const int32_t* __restrict__ q_start,
     const int32_t* __restrict__ q_nnz, const int32_t* __restrict__ d_terms, const float* __restrict__ d_weights,
-    const int64_t* __restrict__ d_start, const int32_t* __restrict__ d_nnz, const int32_t* __restrict__ cand, int n_cand,
-    int64_t out_stride, const uint16_t* __restrict__ q_dense, const uint16_t* __restrict__ d_dense, int dim, float w_dense, float w_lex,
-    float dead, float* __restrict__ out_lex, float* __restrict__ out_dense, float* __restrict__ out_hybrid) {
+    const int64_t* __restrict__ d_start, const int32_t* __restrict__ d_nnz, const int32_t* __restrict__ cand,
+    const int32_t* __restrict__ cand_cnt, int64_t cand_stride, int n_cand, int64_t out_stride, const uint16_t* __restrict__ q_dense,
+    const uint16_t* __restrict__ d_dense, int dim, float w_dense, float w_lex, float dead, float* __restrict__ out_lex,
+    float* __restrict__ out_dense, float* __restrict__ out_hybrid) {
     __shared__ int32_t qt[kMaxQueryNnz];
     __shared__ float qw[kMaxQueryNnz];
     const int q = blockIdx.y;
@@ -195,8 +197,11 @@ __global__ __launch_bounds__(64 * kScoreWaves) void lexical_score_kernel(
 #pragma unroll
     for (int c = 0; c < kMaxH / 128; ++c)
         qd[c] = (q_dense && c < chunks) ? load_pair<false>(q_dense, (size_t)q * dim + 128 * c + 2 * lane) : f32x2{0.f, 0.f};
-    for (int ci = blockIdx.x * kScoreWaves + wave; ci < n_cand; ci += gridDim.x * kScoreWaves) {   // (wave-uniform)
-        const int doc = cand ? cand[(size_t)q * n_cand + ci] : ci;
+    // cand_cnt (postings.hip: a query's own list length, known on the device only) cuts the walk short; it changes which pairs are
+    // scored, never a pair's bits
+    const int n_mine = cand_cnt ? min(max(cand_cnt[q], 0), n_cand) : n_cand;
+    for (int ci = blockIdx.x * kScoreWaves + wave; ci < n_mine; ci += gridDim.x * kScoreWaves) {   // (wave-uniform)
+        const int doc = cand ? cand[(size_t)q * cand_stride + ci] : ci;
         const size_t o = (size_t)q * out_stride + ci;
         const int dn_raw = doc >= 0 ? d_nnz[doc] : -1;
         if (dn_raw < 0) {
@@ -252,17 +257,19 @@ __global__ void lexical_pad_kernel(float* s, int32_t* ix, int64_t n) {
     }
 }
 
+// `grid_cand`: how many candidates the grid is sized for (the walk is grid-strided, so any value >= 1 scores every pair)
 int score_launch(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
                  const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, const int32_t* cand,
-                 int n_cand, int64_t out_stride, const void* q_dense, const void* d_dense, int dim, float w_dense, float w_lex,
-                 float dead, float* out_lex, float* out_dense, float* out_hybrid, hipStream_t st) {
-    const int groups = (n_cand + kScoreWaves - 1) / kScoreWaves;
+                 const int32_t* cand_cnt, int64_t cand_stride, int grid_cand, int n_cand, int64_t out_stride, const void* q_dense,
+                 const void* d_dense, int dim, float w_dense, float w_lex, float dead, float* out_lex, float* out_dense,
+                 float* out_hybrid, hipStream_t st) {
+    const int groups = (std::max(std::min(grid_cand, n_cand), 1) + kScoreWaves - 1) / kScoreWaves;
     // enough workgroups to fill every CU several times over; a wave walks the candidates behind its first one
     const dim3 grid((unsigned)std::min(groups, 8192), (unsigned)n_q);
     TtProfScope prof(TT_K_ROWOPS, st);
     hipLaunchKernelGGL(lexical_score_kernel, grid, dim3(64 * kScoreWaves), 0, st, q_terms, q_weights, q_start, q_nnz, d_terms,
-                       d_weights, d_start, d_nnz, cand, n_cand, out_stride, (const uint16_t*)q_dense, (const uint16_t*)d_dense, dim,
-                       w_dense, w_lex, dead, out_lex, out_dense, out_hybrid);
+                       d_weights, d_start, d_nnz, cand, cand_cnt, cand_stride, n_cand, out_stride, (const uint16_t*)q_dense,
+                       (const uint16_t*)d_dense, dim, w_dense, w_lex, dead, out_lex, out_dense, out_hybrid);
     TT_CHECK_LAUNCH();
     return TT_OK;
 }
@@ -351,8 +358,9 @@ int tt_lexical_score(const int32_t* q_terms, const float* q_weights, const int32
                               d_dense, dim, w_dense, w_lex);
     if (rc) return rc;
     TT_CHECK_ARG(out_lex && (!q_dense || (out_dense && out_hybrid)), "tt_lexical_score: null output");
-    return score_launch(q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, cand, n_cand, n_cand, q_dense,
-                        d_dense, dim, w_dense, w_lex, -INFINITY, out_lex, out_dense, out_hybrid, (hipStream_t)stream);
+    return score_launch(q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, cand, nullptr, n_cand, n_cand,
+                        n_cand, n_cand, q_dense, d_dense, dim, w_dense, w_lex, -INFINITY, out_lex, out_dense, out_hybrid,
+                        (hipStream_t)stream);
 }
 
 size_t tt_lexical_scan_workspace_bytes(int64_t n_docs, int n_q) {
@@ -388,8 +396,8 @@ int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const i
     const int64_t stride = (n_docs + 31) / 32 * 32;
     float* dense = (float*)workspace;
     // a tombstone's slot holds NaN, what a deleted row of the dense index scores (vector_index.py): the selection's key rejects it
-    rc = score_launch(q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, nullptr, (int)n_docs, stride, nullptr,
-                      nullptr, 0, 0.f, 0.f, __builtin_nanf(""), dense, nullptr, nullptr, st);
+    rc = score_launch(q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, nullptr, nullptr, 0, (int)n_docs,
+                      (int)n_docs, stride, nullptr, nullptr, 0, 0.f, 0.f, __builtin_nanf(""), dense, nullptr, nullptr, st);
     if (rc) return rc;
     SelectParams se{};
     se.scores = dense;
@@ -408,3 +416,15 @@ int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const i
 #endif  // !TT_F16
 
 }  // extern "C"
+
+#if !TT_F16
+// scan.h: the lexical scores of per-query candidate lists for postings.hip -- lexical_score_kernel as tt_lexical_scan_topk launches
+// it (no dense part, `dead` for a tombstone), over cand[q * stride .. + min(cand_cnt[q], stride)), scores at the same positions
+int tt_lexical_score_lists(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                           const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz,
+                           const int32_t* cand, const int32_t* cand_cnt, int64_t stride, int grid_cand, float dead, float* out_lex,
+                           hipStream_t st) {
+    return score_launch(q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, cand, cand_cnt, stride, grid_cand,
+                        (int)stride, stride, nullptr, nullptr, 0, 0.f, 0.f, dead, out_lex, nullptr, nullptr, st);
+}
+#endif

@@ -87,5 +87,13 @@ struct SelectParams {
 };
 
 int tt_select_launch(const SelectParams& p, int n_queries, hipStream_t stream);
+
+// lexical.hip, for postings.hip: lexical_score_kernel over per-query candidate lists.  Query q's list is cand[q * stride .. +
+// min(cand_cnt[q], stride)) (document numbers); its scores -- tt_lexical_score's bits, `dead` for a tombstone -- go to out_lex at
+// the same positions.  grid_cand sizes the grid only (the walk is grid-strided): any value >= 1 scores every listed pair.
+int tt_lexical_score_lists(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                           const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz,
+                           const int32_t* cand, const int32_t* cand_cnt, int64_t stride, int grid_cand, float dead, float* out_lex,
+                           hipStream_t stream);
 // true when a selection with this k runs on the k <= 64 kernel, i.e. thr_relax / zero_cnt / n_real are available
 bool tt_select_fused_outputs(int k);

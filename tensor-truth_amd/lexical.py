@@ -408,9 +408,16 @@ class LexicalStore:
     document; ``terms`` int32 and ``weights`` fp32 per distinct token: 8 bytes) plus one bf16 dense row of ``dim`` values per
     document number.  ``add`` appends and grows by doubling; ``remove`` frees the id and writes ``d_nnz = -1`` on the device, so
     that neither ``score`` nor ``search`` returns the document -- its entries stay where they are and are NOT reclaimed (there
-    is no compaction in this version; re-adding an id appends a new copy).  No persistence."""
+    is no compaction in this version; re-adding an id appends a new copy).  No persistence.
 
-    def __init__(self, dim: int, device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10):
+    ``postings=True`` (with ``vocab_size``, the ids' range): ``seal()`` builds posting lists over the documents stored so far
+    (``postings.py``: 4 bytes per entry + 12 per vocabulary id), and ``search`` then scores only the documents on the query's own
+    lists plus the unsealed tail -- the same scores and document numbers as the full scan, bit for bit.  ``add`` leaves new
+    documents in the tail and re-seals once the tail exceeds ``max(65536, n_sealed / 4)`` documents; ``remove`` leaves the lists
+    alone (a tombstone on a list scores NaN and is never selected).  ``stats``: the last search's figures."""
+
+    def __init__(self, dim: int, device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10,
+                 postings: bool = False, vocab_size: Optional[int] = None):
         if dim <= 0 or dim % 128 or dim > MAX_HIDDEN:
             raise ValueError(f"LexicalStore: dim={dim} (a multiple of 128 up to {MAX_HIDDEN})")
         if device.type != "cuda":
@@ -426,6 +433,41 @@ class LexicalStore:
         self._doc_of: Dict[Any, int] = {}
         self._id_of: List[Any] = []          # document number -> node id (None once removed)
         self._ws: Optional[torch.Tensor] = None
+        self._init_postings(postings, vocab_size)
+
+    def _init_postings(self, postings: bool, vocab_size: Optional[int]) -> None:
+        self.postings = bool(postings)
+        if self.postings and (vocab_size is None or int(vocab_size) < 1):
+            raise ValueError(f"postings=True needs vocab_size (every stored id lies in [0, vocab_size)), not {vocab_size!r}")
+        self.vocab_size = None if vocab_size is None else int(vocab_size)
+        self.index = None                    # postings.PostingsIndex over documents [0, index.n_sealed)
+        self._pws: Optional[torch.Tensor] = None
+        self.stats: Dict[str, int] = {}
+
+    @property
+    def n_sealed(self) -> int:
+        return 0 if self.index is None else self.index.n_sealed
+
+    def seal(self) -> None:
+        """Build the posting lists over every document stored so far (live or tombstoned); ``search`` uses them from now on."""
+        from . import postings as _postings
+
+        if not self.postings:
+            raise RuntimeError("seal: the store was made without postings=True")
+        self.index = None                    # (the old lists are freed before the new ones are allocated)
+        self.index = _postings.postings_build(self.terms, self.weights, self.d_start, self.d_nnz, self.n_docs, self.vocab_size,
+                                              self.n_terms)
+
+    def _check_vocab(self, lexical: "LexicalWeights") -> None:
+        """With postings on, an id outside the vocabulary is refused when it is added, not when a later re-seal meets it."""
+        if self.postings and lexical.terms.numel():
+            lo, hi = int(lexical.terms.min()), int(lexical.terms.max())
+            if lo < 0 or hi >= self.vocab_size:
+                raise ValueError(f"add: id {lo if lo < 0 else hi} is outside the vocabulary [0, {self.vocab_size})")
+
+    def _after_add(self) -> None:
+        if self.postings and self.n_docs - self.n_sealed > max(65536, self.n_sealed // 4):
+            self.seal()
 
     def __len__(self) -> int:
         return len(self._doc_of)
@@ -459,6 +501,7 @@ class LexicalStore:
             raise ValueError("add: packed lexical vectors are needed (text i right behind text i-1)")
         if n == 0:
             return np.zeros(0, dtype=np.int32)
+        self._check_vocab(lexical)
         self.terms = self._grown(self.terms, self.n_terms, self.n_terms + total)
         self.weights = self._grown(self.weights, self.n_terms, self.n_terms + total)
         self.d_start = self._grown(self.d_start, self.n_docs, self.n_docs + n)
@@ -478,6 +521,7 @@ class LexicalStore:
             self._id_of.append(nid)
         self.n_terms += total
         self.n_docs += n
+        self._after_add()
         return docs
 
     def _bury(self, doc: int) -> None:
@@ -503,7 +547,8 @@ class LexicalStore:
     @property
     def nbytes(self) -> int:
         """Bytes the store holds in HBM (capacity, not fill)."""
-        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz, self.dense))
+        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz, self.dense)) \
+            + (0 if self.index is None else self.index.nbytes)
 
     @staticmethod
     def _check_query(lexical: LexicalWeights) -> np.ndarray:
@@ -526,7 +571,13 @@ class LexicalStore:
     def search(self, lexical: LexicalWeights, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """The exact lexical top-k over every stored document -> (scores fp32 [n_q][k], document numbers int32 [n_q][k]) on the
         device, ordered by (score descending, document number ascending), padded with (-inf, -1).  Removed documents are never
-        returned; a document that shares no id with the query scores 0 and is a valid result."""
+        returned; a document that shares no id with the query scores 0 and is a valid result.  With posting lists built
+        (``seal``), only the documents on the query's lists and the unsealed tail are scored -- the same result, bit for bit
+        (``postings.search``); ``stats`` then holds the search's figures."""
+        if self.index is not None and self.n_docs > 0:
+            from . import postings as _postings
+
+            return _postings.search(self, lexical, k)
         need = int(_lib.load_library().tt_lexical_scan_workspace_bytes(self.n_docs, len(lexical)))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
@@ -559,7 +610,8 @@ class HipM3HybridRerank:
     ``(w_dense * <q, d> + w_lex * lex(q, d)) / (w_dense + w_lex)`` with ``model_kwargs["hybrid_weights"] = (w_dense, w_lex)``
     (required; ``(0, 1)``: pure lexical scores, ``(1, 0)``: the dense ranking).
 
-    ``model_kwargs["embedder"]``: an existing ``HipHuggingFaceEmbedding`` to share (its weights are not loaded a second time)."""
+    ``model_kwargs["embedder"]``: an existing ``HipHuggingFaceEmbedding`` to share (its weights are not loaded a second time).
+    ``model_kwargs["postings"] = True``: the store searches through posting lists (``LexicalStore``; the same results, bit for bit)."""
 
     def __init__(self, model: str = "BAAI/bge-m3", top_n: int = 2, device: Optional[str] = None, keep_retrieval_score: bool = False,
                  model_kwargs: Optional[Dict[str, Any]] = None, **_ignored):
@@ -568,6 +620,7 @@ class HipM3HybridRerank:
         mk.pop("hybrid_weights")
         embedder = mk.pop("embedder", None)
         head = mk.pop("sparse_head", None)
+        postings = bool(mk.pop("postings", False))
         if embedder is None:
             from .embedding import HipHuggingFaceEmbedding
 
@@ -576,7 +629,8 @@ class HipM3HybridRerank:
         self.embedder, self.device, self.config = embedder, embedder.device, embedder.config
         self.encoder = M3Encoder(embedder, head=head)
         self.model = _M3Model(embedder, self.encoder)
-        self.store = LexicalStore(self.config.hidden, self.device)
+        # model_kwargs["postings"]: the store searches through posting lists (HipLexicalRetriever builds them before its first query)
+        self.store = LexicalStore(self.config.hidden, self.device, postings=postings, vocab_size=self.config.vocab_size)
         self.precision = embedder.precision
         self.nodes: Dict[Any, Any] = {}      # node id -> the indexed node (what HipLexicalRetriever returns)
         self.stats = {"queries": 0, "stored": 0, "encoded": 0}
@@ -700,6 +754,8 @@ class HipLexicalRetriever:
             from .schema import NodeWithScore as node_type
         rr = self.reranker
         _, lw = rr.encoder.encode([query_bundle.query_str], is_query=True)
+        if rr.store.postings and rr.store.index is None:
+            rr.store.seal()
         scores, idx = rr.store.search(lw, self.similarity_top_k)
         out = []
         for s, d in zip(scores[0].cpu().tolist(), idx[0].cpu().tolist()):

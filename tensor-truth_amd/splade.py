@@ -430,9 +430,11 @@ class SpladeStore(LexicalStore):
     """Sparse vectors of indexed passages, in HBM on one device: ``LexicalStore``'s CSR arrays (``d_start`` int64, ``d_nnz`` int32
     per document; ``terms`` int32 and ``weights`` fp32 per kept id: 8 bytes) WITHOUT dense rows.  ``add`` appends and grows by
     doubling; ``remove`` writes ``d_nnz = -1`` (a tombstone: neither ``score`` nor ``search`` returns the document; its entries
-    are not reclaimed).  ``search`` is ``LexicalStore.search``: the exact top-k over every stored passage.  No persistence."""
+    are not reclaimed).  ``search`` is ``LexicalStore.search``: the exact top-k over every stored passage -- through posting lists
+    with ``postings=True`` and ``vocab_size``, as ``LexicalStore`` describes.  No persistence."""
 
-    def __init__(self, device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10):
+    def __init__(self, device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10, postings: bool = False,
+                 vocab_size: Optional[int] = None):
         if device.type != "cuda":
             raise RuntimeError("SpladeStore lives on a HIP device; tensor_truth_amd has no CPU path")
         self.dim, self.device = 0, device
@@ -446,6 +448,7 @@ class SpladeStore(LexicalStore):
         self._doc_of: Dict[Any, int] = {}
         self._id_of: List[Any] = []
         self._ws: Optional[torch.Tensor] = None
+        self._init_postings(postings, vocab_size)
 
     def add(self, node_ids: Sequence[Any], lexical: LexicalWeights) -> np.ndarray:   # noqa: D102 (no dense rows here)
         """Append the passages' sparse vectors -> their document numbers."""
@@ -463,6 +466,7 @@ class SpladeStore(LexicalStore):
             raise ValueError("add: packed sparse vectors are needed (text i right behind text i-1)")
         if n == 0:
             return np.zeros(0, dtype=np.int32)
+        self._check_vocab(lexical)
         self.terms = self._grown(self.terms, self.n_terms, self.n_terms + total)
         self.weights = self._grown(self.weights, self.n_terms, self.n_terms + total)
         self.d_start = self._grown(self.d_start, self.n_docs, self.n_docs + n)
@@ -480,12 +484,14 @@ class SpladeStore(LexicalStore):
             self._id_of.append(nid)
         self.n_terms += total
         self.n_docs += n
+        self._after_add()
         return docs
 
     @property
     def nbytes(self) -> int:
         """Bytes the store holds in HBM (capacity, not fill)."""
-        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz))
+        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz)) \
+            + (0 if self.index is None else self.index.nbytes)
 
     def score(self, lexical: LexicalWeights, cand) -> torch.Tensor:   # noqa: D102 (no dense part here)
         """Every query against its row of ``cand`` (document numbers, -1 = none) -> fp32 [n_q][n_cand] on the device.  A removed
@@ -505,7 +511,7 @@ class HipSpladeRetriever:
 
     ``model_kwargs``: ``torch_dtype`` (bfloat16, the default, or float16), ``model_dir``, ``max_length``, ``query_max_terms`` /
     ``document_max_terms`` (sentence-transformers' ``max_active_dims``; default 512 / 8192), ``embed_batch_size``,
-    ``forward_tokens``; ``state_dict`` or ``synthetic_seed`` with ``encoder_config`` (and optionally ``tokenizer``) instead of a
+    ``forward_tokens``, ``postings`` (True: the store searches through posting lists; the same results); ``state_dict`` or ``synthetic_seed`` with ``encoder_config`` (and optionally ``tokenizer``) instead of a
     directory."""
 
     def __init__(self, model: str, similarity_top_k: int = 10, device: Optional[str] = None,
@@ -544,7 +550,8 @@ class HipSpladeRetriever:
                                      forward_tokens=int(mk.get("forward_tokens", 131072)))
         self.query_max_terms = mk.get("query_max_terms")
         self.document_max_terms = mk.get("document_max_terms")
-        self.store = SpladeStore(dev)
+        # model_kwargs["postings"]: search through posting lists (built at the first query after an ingest that left none)
+        self.store = SpladeStore(dev, postings=bool(mk.get("postings", False)), vocab_size=cfg.vocab_size)
         self.precision = "fp16 (fp32 accumulate)" if dtype == torch.float16 else "bf16 (fp32 accumulate)"
         self.nodes: Dict[Any, Any] = {}
         self.stats = {"queries": 0, "indexed": 0}
@@ -579,6 +586,8 @@ class HipSpladeRetriever:
         if self.store.n_docs == 0:
             return []
         lw = self.encoder.encode([query_bundle.query_str], is_query=True, max_terms=self.query_max_terms)
+        if self.store.postings and self.store.index is None:
+            self.store.seal()
         scores, idx = self.store.search(lw, self.similarity_top_k)
         self.stats["queries"] += 1
         out = []

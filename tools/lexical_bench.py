@@ -2,6 +2,7 @@
 1024) with seeded weights, a seeded lexical head and the hashing tokenizer, one MI355X, HIP events, warm-up, median of ``--repeat``.
 
     python tools/lexical_bench.py [--repeat 20] [--dtype bfloat16] [--scan-docs 1000000] [--out profiles/lexical_bench.jsonl]
+    python tools/lexical_bench.py --postings-only [--out profiles/lexical_postings_bench.jsonl]
 
 One JSON line per leg, appended to ``--out``:
   lone_caller_stored   one query against 50 candidates that sit in the ``LexicalStore``: query encode + ``tt_lexical_score`` (lexical,
@@ -15,7 +16,19 @@ One JSON line per leg, appended to ``--out``:
   dense_scan           the dense exact-order scan of the same box over ``--scan-docs`` x 1024 bf16 rows, k = 50, one query
   ingest               ``M3Encoder.encode`` against ``embed_token_batches`` on the same 256 passages: the lexical ingest runs the full
                        last layer and the head, CLS pooling runs the last layer for the CLS rows only
-with the shader clock sampled (amdsmi, read only) while the windows ran.
+  lexical_postings     the same ``--scan-docs`` arrays through both paths of a store in one process: the full
+                       scan (``tt_lexical_scan_topk``) and the posting-list path (``postings.search``: host planning, readbacks
+                       and all), for one query of 8 ids and for a batch of 64, k = 50, and the one-off ``tt_postings_build``; with
+                       the share of the documents that were scored.  The ids are NOT uniform: a document's ids are 3 + the
+                       running sum of 100 .. 200 gaps drawn from 1 .. 1249 (mean 625), so every document starts at the low ids and
+                       ends between about 62 000 and 125 000 -- lists are about n_docs / 625 long below 62 000, taper to nothing
+                       by about 147 000 and are EMPTY above, 45 % of the id range in all; the query ids alone are uniform in 4 ..
+                       250 001, so about half of a query's 8 ids have no list; a second pair of lines draws them below 60 000,
+                       where every id has a list.  The leg records the profile it met (list length
+                       by decile of the id range, the share of ids without a list, the query ids that had one).  Real
+                       vocabularies have stopword-like ids whose lists are far longer than any here
+with the shader clock sampled (amdsmi, read only) while the windows ran.  ``--postings-only`` runs the last leg alone (no model is
+built) and writes to ``profiles/lexical_postings_bench.jsonl`` unless ``--out`` says otherwise.
 """
 import argparse
 import json
@@ -34,6 +47,7 @@ def main():
     ap.add_argument("--scan-docs", type=int, default=1_000_000)
     ap.add_argument("--dtype", default="bfloat16", choices=("bfloat16", "float16"))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--postings-only", action="store_true")
     args = ap.parse_args()
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.dirname(here))
@@ -49,7 +63,8 @@ def main():
     from tensor_truth_amd.rerank import HipSentenceTransformerRerank
     from tensor_truth_amd.schema import NodeWithScore, TextNode
 
-    out_path = args.out or os.path.join(os.path.dirname(here), "profiles", "lexical_bench.jsonl")
+    out_path = args.out or os.path.join(os.path.dirname(here), "profiles",
+                                        "lexical_postings_bench.jsonl" if args.postings_only else "lexical_bench.jsonl")
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(5)
     words = [f"w{i}" for i in range(5000)]
@@ -79,6 +94,76 @@ def main():
             wall.append((time.perf_counter() - t0) * 1e3)
             ev.append(a.elapsed_time(b))
         return statistics.median(ev), statistics.median(wall)
+
+    def scan_corpus(n_docs, gd):
+        """--scan-docs documents of 100 .. 200 ascending ids: 3 + the cumulative sums of gaps drawn from 1 .. 1249, so ids run from 4
+        to at most 249 803 and crowd at the low end (every document starts there); weights in 0.01 .. 2.01."""
+        nnz = torch.randint(100, 201, (n_docs,), generator=gd, device=dev, dtype=torch.int32)
+        d_start = torch.zeros(n_docs, dtype=torch.int64, device=dev)
+        d_start[1:] = torch.cumsum(nnz[:-1].to(torch.int64), 0)
+        total = int(nnz.sum())
+        gaps = torch.randint(1, 1250, (total,), generator=gd, device=dev, dtype=torch.int64)
+        run = torch.cumsum(gaps, 0)
+        first = torch.repeat_interleave(run[d_start] - gaps[d_start], nnz.to(torch.int64))
+        d_terms = (run - first + 3).to(torch.int32)                    # (ascending inside a document: ids 4 .. 249 803)
+        del gaps, run, first
+        d_weights = torch.rand(total, generator=gd, device=dev) * 2 + 0.01
+        return d_terms, d_weights, d_start, nnz, total
+
+    def postings_leg():
+        from types import SimpleNamespace
+
+        from tensor_truth_amd import postings
+
+        n_docs, vocab, k = args.scan_docs, 250002, 50
+        gd = torch.Generator(device=dev).manual_seed(3)
+        d_terms, d_weights, d_start, nnz, total = scan_corpus(n_docs, gd)
+        clock = _clock_sampler()
+        built = []
+
+        def build():
+            built[:] = [postings.postings_build(d_terms, d_weights, d_start, nnz, n_docs, vocab, total)]
+
+        build_ms, _ = timed(build)
+        ix = built[0]
+        lens = np.diff(ix.off_host)
+        deciles = np.array_split(lens, 10)
+        profile = dict(list_len_mean_by_id_decile=[round(float(d.mean()), 1) for d in deciles], list_len_max=int(lens.max()),
+                       ids_without_list_share=round(float((lens == 0).mean()), 4),
+                       highest_id_with_list=int(np.flatnonzero(lens)[-1]) if lens.any() else -1)
+        store = SimpleNamespace(terms=d_terms, weights=d_weights, d_start=d_start, d_nnz=nnz, n_docs=n_docs, index=ix, _pws=None, _ws=None,
+                                _check_query=lexical.LexicalStore._check_query, stats={})
+        # query ids over the whole id range (section 4.17's query: about half of its ids have no list), then below 60 000, where
+        # every id has a list of about n_docs / 625
+        for n_q, q_hi in ((1, 250002), (64, 250002), (1, 60000), (64, 60000)):
+            q_terms = torch.sort(torch.randint(4, q_hi, (n_q, 8), generator=gd, device=dev, dtype=torch.int32), dim=1).values.reshape(-1)
+            q_weights = torch.rand(n_q * 8, generator=gd, device=dev) + 0.5
+            lw = lexical.LexicalWeights(q_terms.contiguous(), q_weights, np.arange(n_q, dtype=np.int64) * 8, np.full(n_q, 8, dtype=np.int32))
+            ws = torch.empty(int(_lib.load_library().tt_lexical_scan_workspace_bytes(n_docs, n_q)), dtype=torch.uint8, device=dev)
+            qs = lw.starts.astype(np.int32)
+            scan = lambda: lexical.lexical_scan_topk(lw.terms, lw.weights, qs, lw.nnz, d_terms, d_weights, d_start, nnz, k, workspace=ws)  # noqa: E731
+            want, got = scan(), postings.search(store, lw, k)
+            same = bool(torch.equal(want[1], got[1]) and torch.equal(want[0].view(torch.int32), got[0].view(torch.int32)))
+            scan_ms, scan_wall = timed(scan)
+            post_ms, post_wall = timed(lambda: postings.search(store, lw, k))
+            st = dict(store.stats)
+            q_lens = lens[q_terms.cpu().numpy().astype(np.int64)].reshape(n_q, 8)
+            emit(leg="lexical_postings", n_docs=n_docs, nnz=total, vocab=vocab,
+                 ids="document ids: 3 + cumulative sums of 100..200 gaps uniform in 1..1249 (crowded below 62k, thinning out to none by ~147k); "
+                     f"query ids: uniform in 4..{q_hi - 1}", query_id_below=q_hi, k=k, queries=n_q, query_ids=8,
+                 scan_topk_ms=round(scan_ms, 4), scan_topk_wall_ms=round(scan_wall, 4), postings_ms=round(post_ms, 4),
+                 postings_wall_ms=round(post_wall, 4), build_ms=round(build_ms, 3), index_bytes=ix.nbytes, prunable=ix.prunable,
+                 same_bits_as_scan=same, candidates=st["candidates"], passes=st["passes"], fallbacks=st["fallbacks"],
+                 query_ids_with_list_mean=round(float((q_lens > 0).sum(1).mean()), 3),
+                 query_list_len_sum_mean=round(float(q_lens.sum(1).mean()), 1),
+                 query_list_lens=q_lens[0].tolist() if n_q == 1 else None, **profile,
+                 candidate_share=round(st["candidates"] / (n_q * n_docs), 6), sclk_mhz=clock(), repeat=args.repeat,
+                 warmup=args.warmup)
+            del ws
+
+    if args.postings_only:
+        postings_leg()
+        return
 
     emb = HipHuggingFaceEmbedding(model_name="BAAI/bge-m3", device="cuda:0", model_kwargs=dict(synthetic_seed=3, torch_dtype=args.dtype))
     H = emb.config.hidden
@@ -127,19 +212,10 @@ def main():
     del ce, rr, emb
     torch.cuda.empty_cache()
 
-    # the full lexical scan: --scan-docs documents of 100 .. 200 ascending ids below 250 002 (cumulative sums of random gaps)
+    # the full lexical scan
     n_docs = args.scan_docs
     gd = torch.Generator(device=dev).manual_seed(3)
-    nnz = torch.randint(100, 201, (n_docs,), generator=gd, device=dev, dtype=torch.int32)
-    d_start = torch.zeros(n_docs, dtype=torch.int64, device=dev)
-    d_start[1:] = torch.cumsum(nnz[:-1].to(torch.int64), 0)
-    total = int(nnz.sum())
-    gaps = torch.randint(1, 1250, (total,), generator=gd, device=dev, dtype=torch.int64)
-    run = torch.cumsum(gaps, 0)
-    first = torch.repeat_interleave(run[d_start] - gaps[d_start], nnz.to(torch.int64))
-    d_terms = (run - first + 3).to(torch.int32)                    # (ascending inside a document: ids 4 .. 249 803)
-    del gaps, run, first
-    d_weights = torch.rand(total, generator=gd, device=dev) * 2 + 0.01
+    d_terms, d_weights, d_start, nnz, total = scan_corpus(n_docs, gd)
     q_terms = torch.sort(torch.randint(4, 250002, (8,), generator=gd, device=dev, dtype=torch.int32)).values
     q_weights = torch.rand(8, generator=gd, device=dev) + 0.5
     q_start, q_nnz = np.zeros(1, dtype=np.int32), np.full(1, 8, dtype=np.int32)
@@ -165,6 +241,9 @@ def main():
     emit(leg="dense_scan", n_docs=n_docs, dim=1024, k=50, bytes=dbytes, scan_topk_ms=round(dense_ms, 4),
          tb_per_s=round(dbytes / dense_ms / 1e9, 3), fraction_of_8_tb_per_s=round(dbytes / dense_ms / 1e9 / 8.0, 4), sclk_mhz=clock(),
          repeat=args.repeat)
+    del corpus, qv
+    torch.cuda.empty_cache()
+    postings_leg()
 
 
 if __name__ == "__main__":
