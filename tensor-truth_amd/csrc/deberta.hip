@@ -23,7 +23,7 @@
 // the embedding kernel's position and type rows are one row of zeros in the workspace.
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "varlen.h"
+#include "postln.h"
 
 namespace {
 
@@ -173,18 +173,7 @@ int check_tables(int n_pos, int max_pos) {
 int check_weights(const tt_deberta_weights* w) {
     TT_CHECK_ARG(w != nullptr, "null weights");
     const tt_encoder_weights& e = w->enc;
-    if (e.hidden <= 0 || e.hidden % 128 || e.hidden > 1024) {
-        tt_set_error("deberta: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", e.hidden);
-        return TT_E_UNSUPPORTED;
-    }
-    if (e.heads <= 0 || e.hidden != 64 * e.heads) {
-        tt_set_error("deberta: hidden=%d heads=%d: head_dim must be 64", e.hidden, e.heads);
-        return TT_E_UNSUPPORTED;
-    }
-    if (e.ffn <= 0 || e.ffn % 128) {
-        tt_set_error("deberta: ffn=%d must be a multiple of 128", e.ffn);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_postln_shape("deberta", e.hidden, e.heads, e.ffn, 128)) return rc;
     if (int rc = check_tables(w->n_pos, w->max_pos)) return rc;
     TT_CHECK_ARG(e.layers >= 0 && (e.layers == 0 || e.layer != nullptr), "layer array missing");
     TT_CHECK_ARG(e.word_emb && e.emb_ln_g && e.emb_ln_b && e.vocab > 0, "embedding tables missing");
@@ -201,109 +190,45 @@ int check_weights(const tt_deberta_weights* w) {
     return TT_OK;
 }
 
-struct DbWs {
-    size_t off_xa, off_xb, off_y, off_qk, off_vt, off_ctx, off_ffn, off_zero, zero_bytes, off_c, off_p, total;
-    bool fits;
+// the forward's shape for postln.h; the zeros are the embedding kernel's position and token-type row, the tail the two score tables
+// of *tb bytes each (n_rows * heads * n_pos * 8 bytes together).  false: the tables do not fit in size_t, and the tail is left out
+bool db_dims(const tt_deberta_weights* w, int n_rows, PostLnDims* d, size_t* tb) {
+    const tt_encoder_weights& e = w->enc;
+    *d = {e.hidden, e.heads, e.ffn, e.layers, e.ln_eps, QkvForm::SplitV8, false, (size_t)e.hidden * 2, 0};
+    *tb = 0;
+    const bool fits = table_bytes(n_rows, e.heads, w->n_pos, tb) && *tb <= (SIZE_MAX - postln_plan(*d, n_rows).total) / 2;
+    if (fits && e.layers > 0) d->tail_bytes = 2 * *tb;
+    return fits;
+}
+
+// what postln.h's driver asks of a family
+struct DbFamily {
+    const tt_deberta_weights* w;
+    const int32_t *ids, *pos;
+    size_t tb;   // bytes of one score table in the workspace's tail
+
+    int embed(const float* zero, uint16_t* out, int T, hipStream_t st) const {
+        const tt_encoder_weights& ew = w->enc;
+        EmbedParams ep{};
+        // no absolute positions, no token types: position 0 and type 0 of a one-row table of zeros (max_pos 1 clamps whatever pos holds)
+        ep.ids = ids; ep.pos = pos; ep.type = nullptr;
+        ep.word = (const uint16_t*)ew.word_emb;
+        ep.posemb = (const uint16_t*)zero;
+        ep.typeemb = (const uint16_t*)zero;
+        ep.gamma = ew.emb_ln_g; ep.beta = ew.emb_ln_b;
+        ep.T = T; ep.H = ew.hidden; ep.vocab = ew.vocab; ep.max_pos = 1; ep.type_vocab = 1;
+        ep.eps = ew.ln_eps;
+        ep.out = out;
+        return tt_embed_ln_launch(ep, st);
+    }
+    PostLnLayer layer(int l, const float*) const { return postln_layer_of(w->enc.layer[l]); }
+    int attention(int l, const PostLnBufs& b, const PackedSeqs& s, hipStream_t st) const {
+        const int H = w->enc.hidden;
+        return disentangled_attention_launch(b.qkv, 2 * H, 0, H, b.vt, 8 * H, b.ctx, H, s.seq_start, s.seq_len, s.n_seq, s.n_rows,
+                                             w->enc.heads, s.max_len, (const uint16_t*)w->pos_key[l], (const uint16_t*)w->pos_query[l],
+                                             w->n_pos, w->dist_index, w->max_pos, (float*)b.tail, (float*)(b.tail + tb), st);
+    }
 };
-
-DbWs db_plan(const tt_deberta_weights* w, int n_rows) {
-    DbWs e{};
-    // buffers are sized for a multiple of 256 rows: the attention tile reads whole key blocks
-    const size_t H = (size_t)w->enc.hidden, F = (size_t)w->enc.ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    WsPlanner ws;
-    e.off_xa = ws.take(T * H * 2);
-    e.off_xb = ws.take(T * H * 2);
-    e.off_y = ws.take(T * H * 2);
-    e.off_qk = ws.take(T * 2 * H * 2);
-    e.off_vt = ws.take(H * T * 2);
-    e.off_ctx = ws.take(T * H * 2);
-    e.off_ffn = ws.take(T * F * 2);
-    e.zero_bytes = H * 2;            // the embedding kernel's position and token-type row
-    e.off_zero = ws.take(e.zero_bytes);
-    size_t tb = 0;                   // the two score tables: n_rows * heads * n_pos * 8 bytes
-    e.fits = table_bytes(n_rows, w->enc.heads, w->n_pos, &tb) && tb <= (SIZE_MAX - ws.off) / 2;
-    if (e.fits && w->enc.layers > 0) {
-        e.off_c = ws.take(tb);
-        e.off_p = ws.take(tb);
-    }
-    e.total = ws.off;
-    return e;
-}
-
-// one layer on T rows: x -> out (x1 and y are scratch; out may be x)
-int db_layer(const tt_deberta_weights* w, int l, int T, const uint16_t* x, uint16_t* qk, uint16_t* vt, uint16_t* ctx, uint16_t* y,
-             uint16_t* x1, uint16_t* ffn, uint16_t* out, float* c_tab, float* p_tab, const int32_t* seq_start, const int32_t* seq_len,
-             int n_seq, int max_len, hipStream_t st) {
-    const tt_layer_weights& lw = w->enc.layer[l];
-    const int H = w->enc.hidden, F = w->enc.ffn;
-    const float eps = w->enc.ln_eps;
-    GemmParams g = gemm_16(x, lw.qkv_w, lw.qkv_b, T, 3 * H, H);
-    g.C = qk; g.ldc = 2 * H; g.vt = vt; g.ldvt = 8 * H; g.vt_col0 = 2 * H;
-    if (int rc = tt_gemm_launch(g, TT_EPI_QKV, st)) return rc;
-    if (int rc = disentangled_attention_launch(qk, 2 * H, 0, H, vt, 8 * H, ctx, H, seq_start, seq_len, n_seq, T, w->enc.heads, max_len,
-                                               (const uint16_t*)w->pos_key[l], (const uint16_t*)w->pos_query[l], w->n_pos,
-                                               w->dist_index, w->max_pos, c_tab, p_tab, st))
-        return rc;
-    GemmParams go = gemm_16(ctx, lw.o_w, lw.o_b, T, H, H);
-    go.residual = x; go.ldr = H; go.C = y; go.ldc = H;
-    if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-    {
-        TtProfScope prof(TT_K_ROWOPS, st);
-        if (int rc = tt_layernorm_launch(y, x1, lw.ln1_g, lw.ln1_b, T, H, eps, st)) return rc;
-    }
-    GemmParams g1 = gemm_16(x1, lw.ffn1_w, lw.ffn1_b, T, F, H);
-    g1.C = ffn; g1.ldc = F;
-    if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-    GemmParams g2 = gemm_16(ffn, lw.ffn2_w, lw.ffn2_b, T, H, F);
-    g2.residual = x1; g2.ldr = H; g2.C = y; g2.ldc = H;
-    if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-    TtProfScope prof(TT_K_ROWOPS, st);
-    return tt_layernorm_launch(y, out, lw.ln2_g, lw.ln2_b, T, H, eps, st);
-}
-
-int db_run(const tt_deberta_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
-           int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const DbWs e = db_plan(w, n_rows);
-    char* ws = (char*)workspace;
-    const tt_encoder_weights& ew = w->enc;
-    const int H = ew.hidden, T = n_rows;
-    uint16_t* xa = (uint16_t*)(ws + e.off_xa);
-    uint16_t* xb = (uint16_t*)(ws + e.off_xb);
-    uint16_t* y = (uint16_t*)(ws + e.off_y);
-    uint16_t* qk = (uint16_t*)(ws + e.off_qk);
-    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
-    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
-    uint16_t* ffn = (uint16_t*)(ws + e.off_ffn);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
-    // rows that belong to no sequence are never written by the attention kernel: keep them finite
-    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * H * 2, st));
-
-    EmbedParams ep{};
-    // no absolute positions, no token types: position 0 and type 0 of a one-row table of zeros (max_pos 1 clamps whatever pos holds)
-    ep.ids = ids; ep.pos = pos; ep.type = nullptr;
-    ep.word = (const uint16_t*)ew.word_emb;
-    ep.posemb = (const uint16_t*)(ws + e.off_zero);
-    ep.typeemb = (const uint16_t*)(ws + e.off_zero);
-    ep.gamma = ew.emb_ln_g; ep.beta = ew.emb_ln_b;
-    ep.T = T; ep.H = H; ep.vocab = ew.vocab; ep.max_pos = 1; ep.type_vocab = 1;
-    ep.eps = ew.ln_eps;
-    uint16_t* x = ew.layers == 0 ? (uint16_t*)hidden_out : xa;
-    ep.out = x;
-    {
-        TtProfScope prof(TT_K_ROWOPS, st);
-        if (int rc = tt_embed_ln_launch(ep, st)) return rc;
-    }
-    for (int l = 0; l < ew.layers; ++l) {
-        // x1 is free again after the FFN-down GEMM has consumed it as residual; the second LayerNorm's output goes back to x (or
-        // straight to hidden_out on the last layer)
-        uint16_t* dst = (l == ew.layers - 1) ? (uint16_t*)hidden_out : x;
-        if (int rc = db_layer(w, l, T, x, qk, vt, ctx, y, xb, ffn, dst, (float*)(ws + e.off_c), (float*)(ws + e.off_p), seq_start,
-                              seq_len, n_seq, max_len, st))
-            return rc;
-        x = dst;
-    }
-    return TT_OK;
-}
 
 }  // namespace
 
@@ -311,18 +236,21 @@ extern "C" {
 
 size_t tt_deberta_workspace_bytes(const tt_deberta_weights* w, int n_rows) {
     if (!w || n_rows <= 0 || check_weights(w) != TT_OK) return 0;
-    const DbWs e = db_plan(w, n_rows);
-    return e.fits ? e.total : 0;
+    PostLnDims d;
+    size_t tb;
+    return db_dims(w, n_rows, &d, &tb) ? postln_plan(d, n_rows).total : 0;
 }
 
 int tt_deberta_forward(const tt_deberta_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                        void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_weights(w)) return rc;
-    const DbWs e = db_plan(w, n_rows > 0 ? n_rows : 1);
-    TT_CHECK_ARG(e.fits, "n_rows=%d heads=%d n_pos=%d: the score tables do not fit in size_t", n_rows, w->enc.heads, w->n_pos);
+    PostLnDims d;
+    size_t tb;
+    TT_CHECK_ARG(db_dims(w, n_rows > 0 ? n_rows : 1, &d, &tb), "n_rows=%d heads=%d n_pos=%d: the score tables do not fit in size_t",
+                 n_rows, w->enc.heads, w->n_pos);
     if (int rc = check_packed_forward_args("tt_deberta_forward", "DeBERTa", ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len,
-                                           hidden_out, workspace, workspace_bytes, e.total))
+                                           hidden_out, workspace, workspace_bytes, postln_plan(d, n_rows > 0 ? n_rows : 1).total))
         return rc;
     TT_CHECK_ARG(max_len <= w->max_pos, "max_len=%d exceeds max_pos=%d", max_len, w->max_pos);
     for (int l = 0; l < w->enc.layers; ++l) {
@@ -331,7 +259,8 @@ int tt_deberta_forward(const tt_deberta_weights* w, const int32_t* ids, const in
                          lw.ffn2_b && lw.ln2_g && lw.ln2_b,
                      "layer %d has a null weight pointer", l);
     }
-    return db_run(w, ids, pos, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+    return postln_run<void>(d, DbFamily{w, ids, pos, tb}, PackedSeqs{seq_start, seq_len, n_seq, n_rows, max_len}, hidden_out, workspace,
+                            (hipStream_t)stream);
 }
 
 int tt_deberta_head(const tt_deberta_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
@@ -355,18 +284,11 @@ int tt_attention_disentangled(const void* qkv, int ld, int q_col0, int k_col0, c
                               const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
                               int max_len, const void* pos_key, const void* pos_query, int n_pos, const int32_t* dist_index,
                               int max_pos, void* workspace, size_t workspace_bytes, void* stream) {
-    if (head_dim != 64) {
-        tt_set_error("disentangled attention: head_dim=%d (supported: 64)", head_dim);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_attention_layout("disentangled attention", pos_key && pos_query && dist_index, qkv, ld, q_col0, k_col0, vt, ldvt,
+                                        out, ld_out, seq_start, seq_len, n_seq, n_rows, heads, head_dim, max_len))
+        return rc;
     if (int rc = check_tables(n_pos, max_pos)) return rc;
-    TT_CHECK_ARG(qkv && vt && out && seq_start && seq_len && pos_key && pos_query && dist_index, "null pointer");
-    TT_CHECK_ARG(heads > 0 && n_seq > 0 && max_len > 0 && n_rows > 0 && n_rows % 8 == 0 && max_len <= n_rows,
-                 "heads=%d n_seq=%d n_rows=%d max_len=%d", heads, n_seq, n_rows, max_len);
     TT_CHECK_ARG(max_len <= max_pos, "max_len=%d exceeds max_pos=%d", max_len, max_pos);
-    TT_CHECK_ARG(ld % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && q_col0 >= 0 && k_col0 >= 0 && ld_out % 4 == 0 &&
-                     ld >= std::max(q_col0, k_col0) + heads * 64 && ld_out >= heads * 64 && ldvt >= 8 * heads * 64 && ldvt % 8 == 0,
-                 "ld=%d q_col0=%d k_col0=%d ld_out=%d ldvt=%d", ld, q_col0, k_col0, ld_out, ldvt);
     TT_CHECK_ARG(((uintptr_t)pos_key % 16) == 0 && ((uintptr_t)pos_query % 16) == 0, "pos_key / pos_query must be 16-byte aligned");
     size_t tb = 0;
     TT_CHECK_ARG(table_bytes(n_rows, heads, n_pos, &tb), "n_rows=%d heads=%d n_pos=%d: the score tables do not fit in size_t", n_rows,

@@ -100,11 +100,6 @@ __global__ __launch_bounds__(256) void dec_qknorm_rope_kernel(uint16_t* __restri
     }
 }
 
-// ---- SiLU(gate) * up through varlen.h's gated_act_kernel: gu [T][2F] (gate columns, then up columns) -> out [T][F] ------------
-struct Silu {
-    static __device__ __forceinline__ float f(float x) { return x / (1.0f + expf(-x)); }
-};
-
 // ---- last-token pooling + L2 norm: out[b] = h[r] / max(||h[r]||, 1e-12), r = seq_start[b] + seq_len[b] - 1; one wave per sequence
 __global__ __launch_bounds__(256) void dec_pool_last_kernel(const uint16_t* __restrict__ hidden, int ld, const int32_t* __restrict__ seq_start,
                                                             const int32_t* __restrict__ seq_len, int n, int H, float* __restrict__ out,

@@ -18,7 +18,7 @@
 // arithmetic there does not depend on the batch it travels in.
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "varlen.h"
+#include "postln.h"
 
 namespace {
 
@@ -54,18 +54,7 @@ int alibi_attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
 int check_weights(const tt_jinabert_weights* w) {
     TT_CHECK_ARG(w != nullptr, "null weights");
-    if (w->hidden <= 0 || w->hidden % 128 || w->hidden > 1024) {
-        tt_set_error("jinabert: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", w->hidden);
-        return TT_E_UNSUPPORTED;
-    }
-    if (w->heads <= 0 || w->hidden != 64 * w->heads) {
-        tt_set_error("jinabert: hidden=%d heads=%d: head_dim must be 64", w->hidden, w->heads);
-        return TT_E_UNSUPPORTED;
-    }
-    if (w->ffn <= 0 || w->ffn % 128) {
-        tt_set_error("jinabert: ffn=%d must be a multiple of 128", w->ffn);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_postln_shape("jinabert", w->hidden, w->heads, w->ffn, 128)) return rc;
     TT_CHECK_ARG(w->layers >= 0 && (w->layers == 0 || w->layer != nullptr), "layer array missing");
     TT_CHECK_ARG(w->word_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b && w->vocab > 0 && w->type_vocab > 0,
                  "embedding tables / embedding LayerNorm missing");
@@ -74,83 +63,32 @@ int check_weights(const tt_jinabert_weights* w) {
     return TT_OK;
 }
 
-struct JbWs {
-    size_t off_x, off_y, off_x1, off_qk, off_vt, off_ctx, off_gu, off_act, off_zero, zero_bytes, total;
-};
-
-JbWs jb_plan(const tt_jinabert_weights* w, int n_rows) {
-    JbWs e{};
-    // buffers are sized for a multiple of 256 rows: the attention tile reads whole key blocks
-    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    WsPlanner ws;
-    e.off_x = ws.take(T * H * 2);
-    e.off_y = ws.take(T * H * 2);
-    e.off_x1 = ws.take(T * H * 2);
-    e.off_qk = ws.take(T * 2 * H * 2);
-    e.off_vt = ws.take(T * H * 2);
-    e.off_ctx = ws.take(T * H * 2);
-    e.off_gu = ws.take(T * 2 * F * 2);
-    e.off_act = ws.take(T * F * 2);
-    e.zero_bytes = 2 * F * 4;        // the bias operand of the gate projection, which has none
-    e.off_zero = ws.take(e.zero_bytes);
-    e.total = ws.off;
-    return e;
+// the zeros are the bias operand of the gate projection, which has none
+PostLnDims jb_dims(const tt_jinabert_weights* w) {
+    return {w->hidden, w->heads, w->ffn, w->layers, w->ln_eps, QkvForm::SplitV8, true, (size_t)2 * w->ffn * 4, 0};
 }
 
-int jb_layernorm(const uint16_t* in, uint16_t* out, const float* g, const float* b, int rows, int H, float eps, hipStream_t st) {
-    TtProfScope prof(TT_K_ROWOPS, st);
-    return tt_layernorm_launch(in, out, g, b, rows, H, eps, st);
-}
+// what postln.h's driver asks of a family
+struct JbFamily {
+    const tt_jinabert_weights* w;
+    const int32_t* ids;
 
-int jb_run(const tt_jinabert_weights* w, const int32_t* ids, const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows,
-           int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const JbWs e = jb_plan(w, n_rows);
-    char* ws = (char*)workspace;
-    const int H = w->hidden, F = w->ffn, nh = w->heads, T = n_rows;
-    uint16_t* xa = (uint16_t*)(ws + e.off_x);
-    uint16_t* y = (uint16_t*)(ws + e.off_y);
-    uint16_t* x1 = (uint16_t*)(ws + e.off_x1);
-    uint16_t* qk = (uint16_t*)(ws + e.off_qk);
-    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
-    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
-    uint16_t* gu = (uint16_t*)(ws + e.off_gu);
-    uint16_t* act = (uint16_t*)(ws + e.off_act);
-    const float* zero = (const float*)(ws + e.off_zero);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
-    // rows that belong to no sequence are never written by the attention kernel: keep them finite
-    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * H * 2, st));
-    uint16_t* x = w->layers == 0 ? (uint16_t*)hidden_out : xa;
-    {
-        TtProfScope prof(TT_K_ROWOPS, st);
+    int embed(const float*, uint16_t* out, int T, hipStream_t st) const {
         hipLaunchKernelGGL(rb_embed_ln_kernel, dim3((T + 3) / 4), dim3(kRbRowThreads), 0, st, ids, (const uint16_t*)w->word_emb,
-                           (const uint16_t*)w->type_emb, w->emb_ln_g, w->emb_ln_b, x, T, H, w->vocab, w->ln_eps);
+                           (const uint16_t*)w->type_emb, w->emb_ln_g, w->emb_ln_b, out, T, w->hidden, w->vocab, w->ln_eps);
         TT_CHECK_LAUNCH();
+        return TT_OK;
     }
-    for (int l = 0; l < w->layers; ++l) {
+    PostLnLayer layer(int l, const float* zero) const {
         const tt_jinabert_layer_weights& lw = w->layer[l];
-        uint16_t* dst = (l == w->layers - 1) ? (uint16_t*)hidden_out : x;
-        GemmParams g = gemm_16(x, lw.qkv_w, lw.qkv_b, T, 3 * H, H);
-        g.C = qk; g.ldc = 2 * H; g.vt = vt; g.ldvt = 8 * H; g.vt_col0 = 2 * H;
-        if (int rc = tt_gemm_launch(g, TT_EPI_QKV, st)) return rc;
-        if (int rc = alibi_attention_launch(qk, 2 * H, 0, H, vt, 8 * H, ctx, H, seq_start, seq_len, n_seq, T, nh, max_len,
-                                            w->alibi_slope_log2, st))
-            return rc;
-        GemmParams go = gemm_16(ctx, lw.o_w, lw.o_b, T, H, H);
-        go.residual = x; go.ldr = H; go.C = y; go.ldc = H;
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = jb_layernorm(y, x1, lw.ln1_g, lw.ln1_b, T, H, w->ln_eps, st)) return rc;
-        GemmParams g1 = gemm_16(x1, lw.gate_w, zero, T, 2 * F, H);
-        g1.C = gu; g1.ldc = 2 * F;
-        if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        if (int rc = gated_act_launch<GeluErf>(gu, act, T, F, st)) return rc;
-        GemmParams g2 = gemm_16(act, lw.down_w, lw.down_b, T, H, F);
-        g2.residual = x1; g2.ldr = H; g2.C = y; g2.ldc = H;
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = jb_layernorm(y, dst, lw.ln2_g, lw.ln2_b, T, H, w->ln_eps, st)) return rc;
-        x = dst;
+        return {lw.qkv_w, lw.qkv_b, lw.o_w, lw.o_b, lw.ln1_g, lw.ln1_b, lw.gate_w, zero, lw.down_w, lw.down_b, lw.ln2_g, lw.ln2_b};
     }
-    return TT_OK;
-}
+    int attention(int, const PostLnBufs& b, const PackedSeqs& s, hipStream_t st) const {
+        const int H = w->hidden;
+        return alibi_attention_launch(b.qkv, 2 * H, 0, H, b.vt, 8 * H, b.ctx, H, s.seq_start, s.seq_len, s.n_seq, s.n_rows, w->heads,
+                                      s.max_len, w->alibi_slope_log2, st);
+    }
+};
 
 }  // namespace
 
@@ -158,15 +96,16 @@ extern "C" {
 
 size_t tt_jinabert_workspace_bytes(const tt_jinabert_weights* w, int n_rows) {
     if (!w || n_rows <= 0 || check_weights(w) != TT_OK) return 0;
-    return jb_plan(w, n_rows).total;
+    return postln_plan(jb_dims(w), n_rows).total;
 }
 
 int tt_jinabert_forward(const tt_jinabert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_weights(w)) return rc;
+    const PostLnDims d = jb_dims(w);
     if (int rc = check_packed_forward_args("tt_jinabert_forward", "a JinaBERT embedder call", ids, pos, type_ids, seq_start, seq_len,
-                                           n_seq, n_rows, max_len, hidden_out, workspace, workspace_bytes, jb_plan(w, n_rows).total))
+                                           n_seq, n_rows, max_len, hidden_out, workspace, workspace_bytes, postln_plan(d, n_rows).total))
         return rc;
     for (int l = 0; l < w->layers; ++l) {
         const tt_jinabert_layer_weights& lw = w->layer[l];
@@ -175,22 +114,16 @@ int tt_jinabert_forward(const tt_jinabert_weights* w, const int32_t* ids, const 
                      "layer %d has a null weight pointer", l);
     }
     // (`pos` is part of the packed-batch contract and is not read: the bias is a function of the row numbers)
-    return jb_run(w, ids, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+    return postln_run<GeluErf>(d, JbFamily{w, ids}, PackedSeqs{seq_start, seq_len, n_seq, n_rows, max_len}, hidden_out, workspace,
+                               (hipStream_t)stream);
 }
 
 int tt_attention_alibi(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim, int max_len,
                        const float* slope_log2, void* stream) {
-    if (head_dim != 64) {
-        tt_set_error("ALiBi attention: head_dim=%d (supported: 64)", head_dim);
-        return TT_E_UNSUPPORTED;
-    }
-    TT_CHECK_ARG(qkv && vt && out && seq_start && seq_len && slope_log2, "null pointer");
-    TT_CHECK_ARG(heads > 0 && n_seq > 0 && max_len > 0 && n_rows > 0 && n_rows % 8 == 0 && max_len <= n_rows,
-                 "heads=%d n_seq=%d n_rows=%d max_len=%d", heads, n_seq, n_rows, max_len);
-    TT_CHECK_ARG(ld % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && q_col0 >= 0 && k_col0 >= 0 && ld_out % 4 == 0 &&
-                     ld >= std::max(q_col0, k_col0) + heads * 64 && ld_out >= heads * 64 && ldvt >= 8 * heads * 64 && ldvt % 8 == 0,
-                 "ld=%d q_col0=%d k_col0=%d ld_out=%d ldvt=%d", ld, q_col0, k_col0, ld_out, ldvt);
+    if (int rc = check_attention_layout("ALiBi attention", slope_log2 != nullptr, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out,
+                                        seq_start, seq_len, n_seq, n_rows, heads, head_dim, max_len))
+        return rc;
     return alibi_attention_launch((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out, seq_start,
                                   seq_len, n_seq, n_rows, heads, max_len, slope_log2, (hipStream_t)stream);
 }

@@ -349,16 +349,9 @@ int tt_rope_v8(void* qkv, int ld, const int32_t* pos, int n_rows, int heads, int
 int tt_attention_window(const void* qkv, int ld, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int head_dim,
                         int max_len, int window, void* stream) {
-    if (head_dim != 64) {
-        tt_set_error("windowed attention: head_dim=%d (supported: 64)", head_dim);
-        return TT_E_UNSUPPORTED;
-    }
-    TT_CHECK_ARG(qkv && vt && out && seq_start && seq_len, "null pointer");
-    TT_CHECK_ARG(heads > 0 && n_seq > 0 && max_len > 0 && n_rows > 0 && n_rows % 8 == 0 && max_len <= n_rows,
-                 "heads=%d n_seq=%d n_rows=%d max_len=%d", heads, n_seq, n_rows, max_len);
-    TT_CHECK_ARG(ld % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && q_col0 >= 0 && k_col0 >= 0 && ld_out % 4 == 0 &&
-                     ld >= std::max(q_col0, k_col0) + heads * 64 && ld_out >= heads * 64 && ldvt >= 8 * heads * 64 && ldvt % 8 == 0,
-                 "ld=%d q_col0=%d k_col0=%d ld_out=%d ldvt=%d", ld, q_col0, k_col0, ld_out, ldvt);
+    if (int rc = check_attention_layout("windowed attention", true, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len,
+                                        n_seq, n_rows, heads, head_dim, max_len))
+        return rc;
     return window_attention_launch((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out, seq_start,
                                    seq_len, n_seq, n_rows, heads, max_len, window, (hipStream_t)stream);
 }

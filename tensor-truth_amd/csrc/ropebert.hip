@@ -22,38 +22,21 @@
 // layers; a row's arithmetic there does not depend on the batch it travels in.
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "varlen.h"
+#include "postln.h"
 
 namespace {
 
-// SiLU(gate) * up through varlen.h's gated_act_kernel, as decoder.hip: gu [T][2F] (gate columns, then up columns) -> out [T][F]
-struct Silu {
-    static __device__ __forceinline__ float f(float x) { return x / (1.0f + expf(-x)); }
-};
-
-// (the embedding row op, rb_embed_ln_kernel, is varlen.h's: the JinaBERT path uses it too)
+// (no kernel of its own: the embedding row op, rb_embed_ln_kernel, and the SiLU gate are varlen.h's)
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
 int check_weights(const tt_ropebert_weights* w) {
     TT_CHECK_ARG(w != nullptr, "null weights");
-    if (w->hidden <= 0 || w->hidden % 128 || w->hidden > 1024) {
-        tt_set_error("ropebert: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", w->hidden);
-        return TT_E_UNSUPPORTED;
-    }
-    if (w->heads <= 0 || w->hidden != 64 * w->heads) {
-        tt_set_error("ropebert: hidden=%d heads=%d: head_dim must be 64", w->hidden, w->heads);
-        return TT_E_UNSUPPORTED;
-    }
     if (w->mlp_kind != 0 && w->mlp_kind != 1) {
         tt_set_error("ropebert: mlp_kind=%d (0: GELU, 1: SwiGLU)", w->mlp_kind);
         return TT_E_UNSUPPORTED;
     }
     // the GELU MLP's up-projection is F columns wide and the GEMM tiles are 128 columns; SwiGLU's is 2F
-    const int fmul = w->mlp_kind == 1 ? 64 : 128;
-    if (w->ffn <= 0 || w->ffn % fmul) {
-        tt_set_error("ropebert: ffn=%d must be a multiple of %d (mlp_kind %d)", w->ffn, fmul, w->mlp_kind);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_postln_shape("ropebert", w->hidden, w->heads, w->ffn, w->mlp_kind == 1 ? 64 : 128)) return rc;
     TT_CHECK_ARG(w->layers >= 0 && (w->layers == 0 || w->layer != nullptr), "layer array missing");
     TT_CHECK_ARG(w->word_emb && w->type_emb && w->emb_ln_g && w->emb_ln_b && w->vocab > 0 && w->type_vocab > 0,
                  "embedding tables / embedding LayerNorm missing");
@@ -61,93 +44,42 @@ int check_weights(const tt_ropebert_weights* w) {
     return TT_OK;
 }
 
-struct RbWs {
-    size_t off_x, off_y, off_x1, off_qkv, off_vt, off_ctx, off_gu, off_act, off_zero, zero_bytes, total;
-};
-
-RbWs rb_plan(const tt_ropebert_weights* w, int n_rows) {
-    RbWs e{};
-    // buffers are sized for a multiple of 256 rows: the attention kernel reads whole key blocks
-    const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, T = ((size_t)n_rows + 255) / 256 * 256;
-    WsPlanner ws;
-    e.off_x = ws.take(T * H * 2);
-    e.off_y = ws.take(T * H * 2);
-    e.off_x1 = ws.take(T * H * 2);
-    e.off_qkv = ws.take(T * 3 * H * 2);
-    e.off_vt = ws.take(T * H * 2);
-    e.off_ctx = ws.take(T * H * 2);
-    e.off_gu = ws.take(w->mlp_kind == 1 ? T * 2 * F * 2 : 0);
-    e.off_act = ws.take(T * F * 2);
-    e.zero_bytes = std::max(3 * H, 2 * F) * 4;   // the bias operand of a projection without one
-    e.off_zero = ws.take(e.zero_bytes);
-    e.total = ws.off;
-    return e;
+// the zeros are the bias operand of a projection without one: the widest is 3H or 2F
+PostLnDims rb_dims(const tt_ropebert_weights* w) {
+    return {w->hidden, w->heads, w->ffn, w->layers, w->ln_eps, QkvForm::Packed, w->mlp_kind == 1,
+            (size_t)std::max(3 * w->hidden, 2 * w->ffn) * 4, 0};
 }
 
-int rb_layernorm(const uint16_t* in, uint16_t* out, const float* g, const float* b, int rows, int H, float eps, hipStream_t st) {
-    TtProfScope prof(TT_K_ROWOPS, st);
-    return tt_layernorm_launch(in, out, g, b, rows, H, eps, st);
-}
+// what postln.h's driver asks of a family
+struct RbFamily {
+    const tt_ropebert_weights* w;
+    const int32_t *ids, *pos;
 
-int rb_run(const tt_ropebert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
-           int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const RbWs e = rb_plan(w, n_rows);
-    char* ws = (char*)workspace;
-    const int H = w->hidden, F = w->ffn, nh = w->heads, T = n_rows;
-    uint16_t* xa = (uint16_t*)(ws + e.off_x);
-    uint16_t* y = (uint16_t*)(ws + e.off_y);
-    uint16_t* x1 = (uint16_t*)(ws + e.off_x1);
-    uint16_t* qkv = (uint16_t*)(ws + e.off_qkv);
-    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
-    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
-    uint16_t* gu = (uint16_t*)(ws + e.off_gu);
-    uint16_t* act = (uint16_t*)(ws + e.off_act);
-    const float* zero = (const float*)(ws + e.off_zero);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
-    // rows that belong to no sequence are never written by the attention kernel: keep them finite
-    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * H * 2, st));
-    uint16_t* x = w->layers == 0 ? (uint16_t*)hidden_out : xa;
-    {
-        TtProfScope prof(TT_K_ROWOPS, st);
+    int embed(const float*, uint16_t* out, int T, hipStream_t st) const {
         hipLaunchKernelGGL(rb_embed_ln_kernel, dim3((T + 3) / 4), dim3(kRbRowThreads), 0, st, ids, (const uint16_t*)w->word_emb,
-                           (const uint16_t*)w->type_emb, w->emb_ln_g, w->emb_ln_b, x, T, H, w->vocab, w->ln_eps);
+                           (const uint16_t*)w->type_emb, w->emb_ln_g, w->emb_ln_b, out, T, w->hidden, w->vocab, w->ln_eps);
         TT_CHECK_LAUNCH();
+        return TT_OK;
     }
-    for (int l = 0; l < w->layers; ++l) {
+    PostLnLayer layer(int l, const float* zero) const {
         const tt_ropebert_layer_weights& lw = w->layer[l];
-        uint16_t* dst = (l == w->layers - 1) ? (uint16_t*)hidden_out : x;
-        GemmParams g = gemm_16(x, lw.qkv_w, lw.qkv_b ? lw.qkv_b : zero, T, 3 * H, H);
-        g.C = qkv; g.ldc = 3 * H;
-        if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
-        if (int rc = tt_rope_v8(qkv, 3 * H, pos, T, nh, 64, w->rope_theta, vt, 8 * H, st)) return rc;
-        AttnParams a{};
-        a.qk = qkv; a.ld_qk = 3 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = vt; a.ldvt = 8 * H;
-        a.out = ctx; a.ld_out = H; a.seq_start = seq_start; a.seq_len = seq_len;
-        a.n_seq = n_seq; a.heads = nh; a.head_dim = 64; a.max_len = max_len; a.total_rows = T;
-        a.scale = 0.125f;
-        if (int rc = tt_attention_launch(a, st)) return rc;
-        GemmParams go = gemm_16(ctx, lw.o_w, lw.o_b ? lw.o_b : zero, T, H, H);
-        go.residual = x; go.ldr = H; go.C = y; go.ldc = H;
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = rb_layernorm(y, x1, lw.ln1_g, lw.ln1_b, T, H, w->ln_eps, st)) return rc;
-        if (w->mlp_kind == 1) {
-            GemmParams g1 = gemm_16(x1, lw.up_w, zero, T, 2 * F, H);
-            g1.C = gu; g1.ldc = 2 * F;
-            if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-            if (int rc = gated_act_launch<Silu>(gu, act, T, F, st)) return rc;
-        } else {
-            GemmParams g1 = gemm_16(x1, lw.up_w, lw.up_b ? lw.up_b : zero, T, F, H);
-            g1.C = act; g1.ldc = F;
-            if (int rc = tt_gemm_launch(g1, TT_EPI_GELU, st)) return rc;
-        }
-        GemmParams g2 = gemm_16(act, lw.down_w, lw.down_b ? lw.down_b : zero, T, H, F);
-        g2.residual = x1; g2.ldr = H; g2.C = y; g2.ldc = H;
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = rb_layernorm(y, dst, lw.ln2_g, lw.ln2_b, T, H, w->ln_eps, st)) return rc;
-        x = dst;
+        const auto or_zero = [zero](const float* b) { return b ? b : zero; };
+        // (SwiGLU takes no MLP biases: the forward has refused them, so both are the zeros)
+        return {lw.qkv_w, or_zero(lw.qkv_b), lw.o_w,    or_zero(lw.o_b),    lw.ln1_g, lw.ln1_b,
+                lw.up_w,  or_zero(lw.up_b),  lw.down_w, or_zero(lw.down_b), lw.ln2_g, lw.ln2_b};
     }
-    return TT_OK;
-}
+    // q and k rotated in place and V copied to the V8 layout, then the encoder's whole-sequence kernel
+    int attention(int, const PostLnBufs& b, const PackedSeqs& s, hipStream_t st) const {
+        const int H = w->hidden, nh = w->heads;
+        if (int rc = tt_rope_v8(b.qkv, 3 * H, pos, s.n_rows, nh, 64, w->rope_theta, b.vt, 8 * H, st)) return rc;
+        AttnParams a{};
+        a.qk = b.qkv; a.ld_qk = 3 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = b.vt; a.ldvt = 8 * H;
+        a.out = b.ctx; a.ld_out = H; a.seq_start = s.seq_start; a.seq_len = s.seq_len;
+        a.n_seq = s.n_seq; a.heads = nh; a.head_dim = 64; a.max_len = s.max_len; a.total_rows = s.n_rows;
+        a.scale = 0.125f;
+        return tt_attention_launch(a, st);
+    }
+};
 
 }  // namespace
 
@@ -155,15 +87,16 @@ extern "C" {
 
 size_t tt_ropebert_workspace_bytes(const tt_ropebert_weights* w, int n_rows) {
     if (!w || n_rows <= 0 || check_weights(w) != TT_OK) return 0;
-    return rb_plan(w, n_rows).total;
+    return postln_plan(rb_dims(w), n_rows).total;
 }
 
 int tt_ropebert_forward(const tt_ropebert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
                         const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int max_len, void* hidden_out,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_weights(w)) return rc;
+    const PostLnDims d = rb_dims(w);
     if (int rc = check_packed_forward_args("tt_ropebert_forward", "a RoPE-BERT embedder call", ids, pos, type_ids, seq_start, seq_len,
-                                           n_seq, n_rows, max_len, hidden_out, workspace, workspace_bytes, rb_plan(w, n_rows).total))
+                                           n_seq, n_rows, max_len, hidden_out, workspace, workspace_bytes, postln_plan(d, n_rows).total))
         return rc;
     for (int l = 0; l < w->layers; ++l) {
         const tt_ropebert_layer_weights& lw = w->layer[l];
@@ -171,7 +104,10 @@ int tt_ropebert_forward(const tt_ropebert_weights* w, const int32_t* ids, const 
                      "layer %d has a null weight pointer", l);
         TT_CHECK_ARG(w->mlp_kind == 0 || (!lw.up_b && !lw.down_b), "layer %d: the SwiGLU MLP (mlp_kind 1) takes no biases", l);
     }
-    return rb_run(w, ids, pos, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+    const RbFamily fam{w, ids, pos};
+    const PackedSeqs s{seq_start, seq_len, n_seq, n_rows, max_len};
+    return d.gated ? postln_run<Silu>(d, fam, s, hidden_out, workspace, (hipStream_t)stream)
+                   : postln_run<void>(d, fam, s, hidden_out, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

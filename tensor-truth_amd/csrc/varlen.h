@@ -2,6 +2,7 @@
 // for the attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias, and deberta.hip:
 // DeBERTa-v2/v3's post-LN layer with disentangled attention; jinabert.hip: JinaBERT's post-LN layer with ALiBi): the attention
 // tile over the V8 layout, the embedding gather, the gated activation, the workspace plan and the forwards' argument checks.
+// The post-LN families' shared block is postln.h, on top of this header.
 // Device code sits in an anonymous namespace or is a template: one copy per translation unit and element type (common.h TT_F16).
 #pragma once
 #include "common.h"
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(128) void embed_gather_kernel(const int32_t* __rest
 }
 
 // ---- gated activation: gu [T][2F] (activated columns, then the columns that multiply them) -> out [T][F] ---------------------
-// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (decoder.hip Silu, GeluErf below)
+// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (GeluErf and Silu below)
 template <class Act>
 __global__ __launch_bounds__(256) void gated_act_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
                                                         int F) {
@@ -70,6 +71,10 @@ __device__ __forceinline__ float mb_gelu_erf(float x) {
 // GELU_erf(input) * gate through varlen.h's gated_act_kernel: gu [T][2F] (input columns, then gate columns) -> out [T][F]
 struct GeluErf {
     static __device__ __forceinline__ float f(float x) { return mb_gelu_erf(x); }
+};
+// SiLU(gate) * up through gated_act_kernel: gu [T][2F] (gate columns, then up columns) -> out [T][F]
+struct Silu {
+    static __device__ __forceinline__ float f(float x) { return x / (1.0f + expf(-x)); }
 };
 
 // ---- embeddings: out[r] = LayerNorm(word[ids[r]] + type[0]) * gamma + beta ------------------------------------------------------
@@ -402,6 +407,25 @@ inline int check_packed_forward_args(const char* what, const char* family, const
     TT_CHECK_ARG(n_seq > 0 && max_len > 0 && max_len <= n_rows, "n_seq=%d max_len=%d", n_seq, max_len);
     TT_CHECK_ARG(ids && pos && seq_start && seq_len && hidden_out, "null pointer");
     return tt_check_workspace(what, workspace, workspace_bytes, need);
+}
+
+// the operands of the attention building blocks on the one-wave tile with as many KV heads as query heads (`what`: "windowed
+// attention", "ALiBi attention"; `operands`: the entry point's own pointers are present): heads of 64, 16-byte Q / K / V reads,
+// 8-byte output stores, every head's columns inside a row
+inline int check_attention_layout(const char* what, bool operands, const void* qkv, int ld, int q_col0, int k_col0, const void* vt,
+                                  int ldvt, const void* out, int ld_out, const int32_t* seq_start, const int32_t* seq_len, int n_seq,
+                                  int n_rows, int heads, int head_dim, int max_len) {
+    if (head_dim != 64) {
+        tt_set_error("%s: head_dim=%d (supported: 64)", what, head_dim);
+        return TT_E_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(qkv && vt && out && seq_start && seq_len && operands, "null pointer");
+    TT_CHECK_ARG(heads > 0 && n_seq > 0 && max_len > 0 && n_rows > 0 && n_rows % 8 == 0 && max_len <= n_rows,
+                 "heads=%d n_seq=%d n_rows=%d max_len=%d", heads, n_seq, n_rows, max_len);
+    TT_CHECK_ARG(ld % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && q_col0 >= 0 && k_col0 >= 0 && ld_out % 4 == 0 &&
+                     ld >= std::max(q_col0, k_col0) + heads * 64 && ld_out >= heads * 64 && ldvt >= 8 * heads * 64 && ldvt % 8 == 0,
+                 "ld=%d q_col0=%d k_col0=%d ld_out=%d ldvt=%d", ld, q_col0, k_col0, ld_out, ldvt);
+    return TT_OK;
 }
 
 }  // namespace

@@ -21,11 +21,11 @@ from __future__ import annotations
 import ctypes
 from ctypes import POINTER, Structure, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional
+from typing import Dict, List, Optional
 
 import torch
 
-from .encoder import DEBERTA_BF16_PATH, DEBERTA_FP16_PATH, EncoderConfig, _EncW, _LayerW
+from .encoder import DEBERTA_BF16_PATH, DEBERTA_FP16_PATH, EncoderConfig, _EncW, _FamilyWeights, _LayerW
 
 MAX_POSITIONS = 512      # the index table a workgroup stages (csrc/varlen.h Disentangled::MAX_POS)
 
@@ -136,37 +136,20 @@ def check_state(cfg: EncoderConfig, state: Dict[str, torch.Tensor]) -> Dict[str,
     return sd
 
 
-class DebertaWeights:
+class DebertaWeights(_FamilyWeights):
     """Device-resident DeBERTa weights for ``tt_deberta_forward`` (bf16) or ``tt_deberta_forward_f16`` (fp16): the projections
     (query, key, value rows concatenated to [3H][H]) and the word table in the element type; biases, LayerNorm parameters and the
     head in fp32; per layer PK / PQ = key_proj / query_proj of the normalised relative embeddings (fp32 torch on the device,
     rounded once to the element type) and the distance table -- all built here, once."""
 
+    _paths, _path_name = (DEBERTA_BF16_PATH, DEBERTA_FP16_PATH), "the DeBERTa path"
+
     def __init__(self, cfg: EncoderConfig, state: Dict[str, torch.Tensor], device: torch.device, dtype: torch.dtype = torch.bfloat16):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("DebertaWeights: the DeBERTa path computes in bfloat16 or float16")
-        if device.type != "cuda":
-            raise RuntimeError("DebertaWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype)
         check_config(cfg)
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = DEBERTA_FP16_PATH if dtype == torch.float16 else DEBERTA_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
+        mat, vec = self._loaders(sd, flatten=True)       # classifier.weight is a [1][H] row
         H, F, n_pos = cfg.hidden, cfg.ffn, 2 * cfg.position_buckets
-
-        def mat(names, shape):
-            t = torch.cat([sd[n] for n in names], 0)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device, dtype=dtype).contiguous()).data_ptr()
-
-        def vec(names, n):
-            t = torch.cat([sd[x].reshape(-1) for x in names], 0)
-            if tuple(t.shape) != (n,):
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(device=device, dtype=torch.float32).contiguous()).data_ptr()
-
         enc = _EncW(hidden=H, layers=cfg.layers, heads=cfg.heads, ffn=F, vocab=cfg.vocab_size, max_pos=cfg.max_pos, type_vocab=1,
                     ln_eps=cfg.ln_eps, word_emb=mat(["embeddings.word_embeddings.weight"], (cfg.vocab_size, H)),
                     emb_ln_g=vec(["embeddings.LayerNorm.weight"], H), emb_ln_b=vec(["embeddings.LayerNorm.bias"], H))
@@ -207,17 +190,6 @@ class DebertaWeights:
         self.struct.pooler_dense_wt = dense_t.data_ptr()
         self.struct.pooler_dense_b = vec(["pooler.dense.bias"], H)
         self.struct.cls_w, self.struct.cls_b = vec(["classifier.weight"], H), vec(["classifier.bias"], 1)
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: EncoderConfig, seed: int = 0) -> Dict[str, torch.Tensor]:

@@ -317,6 +317,55 @@ class _CheckpointWeights:
         return sum(t.numel() * t.element_size() for t in self._keep)
 
 
+class _FamilyWeights:
+    """What the weight holders of the post-LN packed-varlen families share (mpnet.py, deberta.py, jinabert.py, ropebert.py): the
+    dtype / device checks, the resident tensors and the two loaders of checkpoint entries.  A subclass names its two paths
+    (``_paths``: bf16, fp16) and what the dtype error calls them (``_path_name``), and builds its own ctypes struct."""
+
+    _paths: Tuple[EncoderPath, EncoderPath]
+    _path_name: str
+
+    def _begin(self, cfg: EncoderConfig, device: torch.device, dtype: torch.dtype) -> None:
+        name = type(self).__name__
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"{name}: {self._path_name} computes in bfloat16 or float16")
+        if device.type != "cuda":
+            raise RuntimeError(f"{name} need a HIP device; tensor_truth_amd has no CPU path")
+        self.cfg, self.device, self.dtype = cfg, device, dtype
+        self.path = self._paths[dtype == torch.float16]
+        self.gemm_dtype = dtype
+        self._keep: List[torch.Tensor] = []
+
+    def _loaders(self, sd: Dict[str, torch.Tensor], flatten: bool = False):
+        """``(mat, vec)``: ``mat(names, shape)`` keeps the checkpoint entries ``names`` of ``sd``, concatenated along dim 0, in the
+        element type and ``vec(names, n)`` in fp32; both return the device address and refuse a shape other than the one given.
+        ``flatten``: ``vec`` takes entries of any shape (a [1][H] classifier row) and reads them as vectors."""
+        def mat(names, shape):
+            t = torch.cat([sd[n] for n in names], 0)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {self.cfg} (expected {shape})")
+            return self._kept(t.to(device=self.device, dtype=self.dtype).contiguous()).data_ptr()
+
+        def vec(names, n):
+            t = torch.cat([sd[x].reshape(-1) if flatten else sd[x] for x in names], 0)
+            if tuple(t.shape) != (n,):
+                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {self.cfg}")
+            return self._kept(t.to(device=self.device, dtype=torch.float32).contiguous()).data_ptr()
+
+        return mat, vec
+
+    def _kept(self, t: torch.Tensor) -> torch.Tensor:
+        self._keep.append(t)
+        return t
+
+    def parameters(self) -> Iterable[torch.Tensor]:
+        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
+        return iter(self._keep)
+
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self._keep)
+
+
 class EncoderWeights(_CheckpointWeights):
     """The 16-bit path (``tt_encoder_forward``): matrices and embedding tables in bf16, or fp16 (the library's ``*_f16``
     entry points); biases and LayerNorm parameters fp32."""

@@ -24,11 +24,11 @@ import math
 import re
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List
+from typing import Dict, List
 
 import torch
 
-from .encoder import JINABERT_BF16_PATH, JINABERT_FP16_PATH, EncoderConfig
+from .encoder import JINABERT_BF16_PATH, JINABERT_FP16_PATH, EncoderConfig, _FamilyWeights
 
 logger = logging.getLogger(__name__)
 
@@ -164,37 +164,20 @@ def check_state(cfg: JinaBertConfig, state: Dict[str, torch.Tensor]) -> Dict[str
     return {n: sd[n] for n in names}
 
 
-class JinaBertWeights:
+class JinaBertWeights(_FamilyWeights):
     """Device-resident weights for ``tt_jinabert_forward`` (bf16) or ``tt_jinabert_forward_f16`` (fp16): the projections (query, key,
     value rows concatenated to [3H][H]; ``gated_layers`` as stored, [2F][H]: the rows GELU is applied to, then the rows that
     multiply them -- the order ``gated_act_kernel`` reads) and the embedding tables in the element type; biases, LayerNorm
     parameters and the ALiBi slopes (times log2(e), from double, one rounding) in fp32."""
 
+    _paths, _path_name = (JINABERT_BF16_PATH, JINABERT_FP16_PATH), "the path"
+
     def __init__(self, cfg: JinaBertConfig, state: Dict[str, torch.Tensor], device: torch.device, dtype: torch.dtype = torch.bfloat16):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("JinaBertWeights: the path computes in bfloat16 or float16")
-        if device.type != "cuda":
-            raise RuntimeError("JinaBertWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype)
         check_config(cfg)
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = JINABERT_FP16_PATH if dtype == torch.float16 else JINABERT_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
+        mat, vec = self._loaders(sd)
         H, F = cfg.hidden, cfg.ffn
-
-        def mat(names, shape):
-            t = torch.cat([sd[n] for n in names], 0)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device, dtype=dtype).contiguous()).data_ptr()
-
-        def vec(names, n):
-            t = torch.cat([sd[x] for x in names], 0)
-            if tuple(t.shape) != (n,):
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(device=device, dtype=torch.float32).contiguous()).data_ptr()
-
         self._layers = (_JbLayerW * max(cfg.layers, 1))()
         for i in range(cfg.layers):
             p, L = f"encoder.layer.{i}.", self._layers[i]
@@ -213,17 +196,6 @@ class JinaBertWeights:
                            emb_ln_g=vec(["embeddings.LayerNorm.weight"], H), emb_ln_b=vec(["embeddings.LayerNorm.bias"], H),
                            alibi_slope_log2=self._kept(slopes.to(device).contiguous()).data_ptr(),
                            layer=ctypes.cast(self._layers, POINTER(_JbLayerW)))
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: JinaBertConfig, seed: int = 0) -> Dict[str, torch.Tensor]:

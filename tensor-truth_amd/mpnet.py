@@ -15,12 +15,12 @@ from __future__ import annotations
 import ctypes
 import math
 from ctypes import POINTER, Structure, c_void_p
-from typing import Dict, Iterable, List
+from typing import Dict, List
 
 import numpy as np
 import torch
 
-from .encoder import MPNET_BF16_PATH, MPNET_FP16_PATH, EncoderConfig, _EncW, _LayerW
+from .encoder import MPNET_BF16_PATH, MPNET_FP16_PATH, EncoderConfig, _EncW, _FamilyWeights, _LayerW
 
 NUM_BUCKETS = 32       # MPNetEncoder.compute_position_bias / relative_position_bucket: both hard-coded at the call site
 MAX_DISTANCE = 128
@@ -116,36 +116,19 @@ def check_state(cfg: EncoderConfig, state: Dict[str, torch.Tensor]) -> Dict[str,
     return sd
 
 
-class MpnetWeights:
+class MpnetWeights(_FamilyWeights):
     """Device-resident MPNet weights for ``tt_mpnet_forward`` (bf16) or ``tt_mpnet_forward_f16`` (fp16): the projections (q, k, v
     rows concatenated to [3H][H]) and the embedding tables in the element type; biases, LayerNorm parameters, the checkpoint's
     bias table and the per-head distance table built from it in fp32."""
 
+    _paths, _path_name = (MPNET_BF16_PATH, MPNET_FP16_PATH), "the MPNet path"
+
     def __init__(self, cfg: EncoderConfig, state: Dict[str, torch.Tensor], device: torch.device, dtype: torch.dtype = torch.bfloat16):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("MpnetWeights: the MPNet path computes in bfloat16 or float16")
-        if device.type != "cuda":
-            raise RuntimeError("MpnetWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype)
         check_config(cfg)
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = MPNET_FP16_PATH if dtype == torch.float16 else MPNET_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
+        mat, vec = self._loaders(sd)
         H, F = cfg.hidden, cfg.ffn
-
-        def mat(names, shape):
-            t = torch.cat([sd[n] for n in names], 0)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device, dtype=dtype).contiguous()).data_ptr()
-
-        def vec(names, n):
-            t = torch.cat([sd[x] for x in names], 0)
-            if tuple(t.shape) != (n,):
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(device=device, dtype=torch.float32).contiguous()).data_ptr()
-
         enc = _EncW(hidden=H, layers=cfg.layers, heads=cfg.heads, ffn=F, vocab=cfg.vocab_size, max_pos=cfg.max_pos, type_vocab=1,
                     ln_eps=cfg.ln_eps, word_emb=mat(["embeddings.word_embeddings.weight"], (cfg.vocab_size, H)),
                     pos_emb=mat(["embeddings.position_embeddings.weight"], (cfg.max_pos, H)),
@@ -168,17 +151,6 @@ class MpnetWeights:
         rel = self._kept(rel.to(device=device, dtype=torch.float32).contiguous())
         self.bias_table = self._kept(distance_table(rel))
         self.struct = _MpW(enc=enc, rel_bias=rel.data_ptr(), bias_table=self.bias_table.data_ptr())
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: EncoderConfig, seed: int = 0) -> Dict[str, torch.Tensor]:

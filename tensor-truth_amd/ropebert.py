@@ -21,11 +21,11 @@ import ctypes
 import re
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List
+from typing import Dict, List
 
 import torch
 
-from .encoder import ROPEBERT_BF16_PATH, ROPEBERT_FP16_PATH, EncoderConfig
+from .encoder import ROPEBERT_BF16_PATH, ROPEBERT_FP16_PATH, EncoderConfig, _FamilyWeights
 
 MODEL_TYPES = ("nomic_bert", "jina_embeddings_v3")
 # what the installed NomicBertConfig / JinaEmbeddingsV3Config default to
@@ -209,35 +209,19 @@ def check_state(cfg: RopeBertConfig, state: Dict[str, torch.Tensor]) -> Dict[str
     return sd
 
 
-class RopeBertWeights:
+class RopeBertWeights(_FamilyWeights):
     """Device-resident weights for ``tt_ropebert_forward`` (bf16) or ``tt_ropebert_forward_f16`` (fp16): the projections (q, k, v
     rows concatenated to [3H][H]; SwiGLU: gate rows then up rows, [2F][H], the order ``gated_act_kernel`` reads) and the embedding
     tables in the element type; biases and LayerNorm parameters in fp32."""
 
+    _paths, _path_name = (ROPEBERT_BF16_PATH, ROPEBERT_FP16_PATH), "the path"
+
     def __init__(self, cfg: RopeBertConfig, state: Dict[str, torch.Tensor], device: torch.device, dtype: torch.dtype = torch.bfloat16):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("RopeBertWeights: the path computes in bfloat16 or float16")
-        if device.type != "cuda":
-            raise RuntimeError("RopeBertWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype)
         check_config(cfg)
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = ROPEBERT_FP16_PATH if dtype == torch.float16 else ROPEBERT_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
+        mat, vec = self._loaders(sd)
         H, F = cfg.hidden, cfg.ffn
-
-        def mat(names, shape):
-            t = torch.cat([sd[n] for n in names], 0)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device, dtype=dtype).contiguous()).data_ptr()
-
-        def vec(names, n):
-            t = torch.cat([sd[x] for x in names], 0)
-            if tuple(t.shape) != (n,):
-                raise ValueError(f"{names[0]} ... {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(device=device, dtype=torch.float32).contiguous()).data_ptr()
 
         def bias(names, n):
             return vec(names, n) if cfg.biases else None
@@ -262,17 +246,6 @@ class RopeBertWeights:
                            type_emb=mat(["embeddings.token_type_embeddings.weight"], (cfg.type_vocab, H)),
                            emb_ln_g=vec(["embeddings.LayerNorm.weight"], H), emb_ln_b=vec(["embeddings.LayerNorm.bias"], H),
                            layer=ctypes.cast(self._layers, POINTER(_RbLayerW)))
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: RopeBertConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
