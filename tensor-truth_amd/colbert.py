@@ -24,6 +24,7 @@ a tensor or a setting it does not know is refused by name, and a setting it need
 from __future__ import annotations
 
 import ctypes
+import functools
 import json
 import logging
 import os
@@ -36,6 +37,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._hostargs import _check_range, _dev_i, _need_device, _stream, _suffix, grown, read_json, resolve_device
+from ._hostargs import resolve_dtype as _resolve_dtype
+from ._stored import IdTable, _StoredRerank
 from .encoder import Encoder, EncoderConfig, EncoderWeights, _scratch, pack_tokens
 
 logger = logging.getLogger(__name__)
@@ -74,14 +78,6 @@ _PYLATE_READ = frozenset(("query_prefix", "document_prefix", "query_length", "do
                           "skiplist_words", "similarity_fn_name", "do_query_expansion"))
 # model_kwargs names: the PyLate spelling, and the stanford one as an alias
 _ALIASES = {"query_length": "query_maxlen", "document_length": "doc_maxlen", "attend_to_expansion_tokens": "attend_to_mask_tokens"}
-
-
-def _read_json(path: str) -> dict:
-    with open(path, encoding="utf-8") as f:
-        d = json.load(f)
-    if not isinstance(d, dict):
-        raise ValueError(f"{path}: a JSON object is expected")
-    return d
 
 
 def detect_layout(model_dir: Optional[str]) -> Optional[str]:
@@ -155,7 +151,7 @@ def parse_settings(model_dir: Optional[str], vocab: "_Vocabulary", model_kwargs:
     files: Dict[str, Any] = {}
     if layout == "stanford":
         where = "artifact.metadata"
-        files = _read_json(os.path.join(model_dir, where))
+        files = read_json(os.path.join(model_dir, where))
         unknown = sorted(set(files) - _STANFORD_READ - _STANFORD_UNUSED)
         if unknown:
             raise NotImplementedError(f"artifact.metadata carries fields the ColBERT path does not know: {unknown[:6]}")
@@ -164,7 +160,7 @@ def parse_settings(model_dir: Optional[str], vocab: "_Vocabulary", model_kwargs:
     elif layout == "pylate":
         where = "config_sentence_transformers.json"
         p = os.path.join(model_dir, where)
-        files = _read_json(p) if os.path.exists(p) else {}
+        files = read_json(p) if os.path.exists(p) else {}
         unknown = sorted(set(files) - _PYLATE_READ - _PYLATE_UNUSED)
         if unknown:
             raise NotImplementedError(f"{where} carries fields the ColBERT path does not know: {unknown[:6]}")
@@ -309,7 +305,7 @@ def _dense_module(model_dir: str) -> Tuple[str, dict]:
     if mods[0].get("path", "") not in ("", "."):
         raise NotImplementedError(f"modules.json: Transformer module at path {mods[0].get('path')!r} (expected the directory itself)")
     dpath = os.path.join(model_dir, str(mods[1].get("path", "1_Dense")))
-    dc = _read_json(os.path.join(dpath, "config.json"))
+    dc = read_json(os.path.join(dpath, "config.json"))
     unknown = sorted(set(dc) - {"in_features", "out_features", "bias", "activation_function", "use_residual"})
     if unknown:
         raise NotImplementedError(f"1_Dense/config.json carries fields the ColBERT path does not know: {unknown[:6]}")
@@ -323,20 +319,7 @@ def _dense_module(model_dir: str) -> Tuple[str, dict]:
     return dpath, dc
 
 
-def resolve_dtype(model_kwargs: Optional[dict]) -> torch.dtype:
-    mk = model_kwargs or {}
-    td = mk.get("torch_dtype")
-    name = str(td).replace("torch.", "") if td is not None else None
-    if name is None and mk.get("precision") is not None:
-        name = {"bf16": "bfloat16", "fp16": "float16"}.get(str(mk["precision"]).lower(), str(mk["precision"]))
-        if name not in ("bfloat16", "float16"):
-            raise NotImplementedError(f"precision={mk['precision']!r} is not available for ColBERT checkpoints: torch_dtype bfloat16 "
-                                      "(the default) or float16")
-    if name is None or name in ("bfloat16", "bf16"):
-        return torch.bfloat16
-    if name in ("float16", "fp16", "half"):
-        return torch.float16
-    raise NotImplementedError(f"torch_dtype={td!r} is not available for ColBERT checkpoints: bfloat16 (the default) or float16")
+resolve_dtype = functools.partial(_resolve_dtype, family="ColBERT")
 
 
 def load_checkpoint(model_dir: str, model_kwargs: Optional[dict] = None):
@@ -349,7 +332,7 @@ def load_checkpoint(model_dir: str, model_kwargs: Optional[dict] = None):
     if layout is None:
         raise ValueError(f"{model_dir} is not a ColBERT directory (no artifact.metadata, no PyLate Dense module)")
     resolve_dtype(model_kwargs)
-    hf = _read_json(os.path.join(model_dir, "config.json"))
+    hf = read_json(os.path.join(model_dir, "config.json"))
     mt = hf.get("model_type")
     if mt != "bert" or hf.get("position_embedding_type", "absolute") != "absolute":
         raise NotImplementedError(f"config.json model_type={mt!r} position_embedding_type={hf.get('position_embedding_type')!r}: the "
@@ -384,35 +367,6 @@ def load_checkpoint(model_dir: str, model_kwargs: Optional[dict] = None):
 
 
 # ---- host wrappers of the kernels ------------------------------------------------------------------------------------------------
-def _suffix(dtype: torch.dtype) -> str:
-    if dtype == torch.bfloat16:
-        return ""
-    if dtype == torch.float16:
-        return "_f16"
-    raise ValueError(f"16-bit operands are bfloat16 or float16, not {dtype}")
-
-
-def _stream(dev: torch.device):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _check_range(name: str, a: np.ndarray, lo: int, hi) -> None:
-    a = np.asarray(a)
-    bad = (a < lo) | (a > hi)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"{name}[{i}]={int(a.flat[i])} is outside {lo} .. {int(np.asarray(hi).flat[i]) if np.ndim(hi) else hi}")
-
-
-def _dev_i(a, dtype, dev: torch.device) -> torch.Tensor:
-    if isinstance(a, torch.Tensor):
-        if a.device.type != dev.type or (dev.index is not None and a.device.index != dev.index) or a.dtype != dtype \
-                or not a.is_contiguous():
-            raise ValueError(f"a contiguous device array of {dtype} on {dev} is expected")
-        return a
-    return torch.from_numpy(np.ascontiguousarray(a, dtype={torch.int32: np.int32, torch.int64: np.int64}[dtype])).to(dev)
-
-
 def maxsim(q_vecs: torch.Tensor, q_start, q_len, d_vecs: torch.Tensor, d_start, d_len, cand=None,
            n_cand: Optional[int] = None) -> torch.Tensor:
     """``tt_maxsim`` -> scores fp32 [n_q][n_cand] (device).  ``q_vecs`` [*, dim], ``d_vecs`` [*, dim]: 16-bit device tensors of
@@ -420,32 +374,41 @@ def maxsim(q_vecs: torch.Tensor, q_start, q_len, d_vecs: torch.Tensor, d_start, 
     numbers, < 0 = none; None: documents 0 .. n_cand-1 for every query): host arrays are checked against the kernel's limits
     (q_len 1 .. 128, d_len 0 .. 512, rows inside the buffers) and uploaded; device tensors are taken as they are -- their owner
     (``TokenVectorStore``, ``ColbertEncoder``) checked them when it made them, and the kernel clamps a length into its range."""
-    dev = q_vecs.device
-    if dev.type != "cuda" or d_vecs.device != dev:
-        raise RuntimeError("maxsim: device tensors are needed; tensor_truth_amd has no CPU path")
+    _need_device("maxsim", q_vecs, d_vecs)                # (this wrapper looks at the device first, ``maxsim_wide`` last)
+    return _maxsim("maxsim", "tt_maxsim", MAX_QUERY_LEN, MAX_DOC_LEN, None, (), q_vecs, q_start, q_len, d_vecs, d_start, d_len, cand, n_cand)
+
+
+def _maxsim(name: str, entry: str, max_q: int, max_d: int, check_dim, trailing: tuple, q_vecs: torch.Tensor, q_start, q_len,
+            d_vecs: torch.Tensor, d_start, d_len, cand, n_cand: Optional[int]) -> torch.Tensor:
+    """The body of ``maxsim`` and ``multivec.maxsim_wide``: library entry ``entry[_f16]`` with the kernel's limits ``max_q`` query
+    and ``max_d`` document rows, ``check_dim(name, dim)`` (None: the library's own refusal) and ``trailing``, the entry's integer
+    arguments behind ``dim``.  Bad host arguments are refused before the device is looked at."""
     if q_vecs.dtype != d_vecs.dtype or q_vecs.dim() != 2 or d_vecs.dim() != 2 or q_vecs.shape[1] != d_vecs.shape[1]:
-        raise ValueError("maxsim: query and document vectors must be [*, dim] of one 16-bit type")
-    sfx, dim = _suffix(q_vecs.dtype), int(q_vecs.shape[1])
+        raise ValueError(f"{name}: query and document vectors must be [*, dim] of one 16-bit type")
+    entry, dim = entry + _suffix(q_vecs.dtype), int(q_vecs.shape[1])
+    if check_dim is not None:
+        check_dim(name, dim)
     if not (q_vecs.is_contiguous() and d_vecs.is_contiguous()):
-        raise ValueError("maxsim: row-major vectors with a row stride of dim are needed")
+        raise ValueError(f"{name}: row-major vectors with a row stride of dim are needed")
     n_q = len(q_len)
     if not isinstance(q_len, torch.Tensor):
-        _check_range("q_len", q_len, 1, MAX_QUERY_LEN)
+        _check_range("q_len", q_len, 1, max_q)
         _check_range("q_start", q_start, 0, q_vecs.shape[0] - np.asarray(q_len))
     if not isinstance(d_len, torch.Tensor):
-        _check_range("d_len", d_len, 0, MAX_DOC_LEN)
+        _check_range("d_len", d_len, 0, max_d)
         _check_range("d_start", d_start, 0, d_vecs.shape[0] - np.asarray(d_len))
     n_docs = len(d_len)
     if cand is None:
         n_cand = n_docs if n_cand is None else int(n_cand)
         if not 0 <= n_cand <= n_docs:
             raise ValueError(f"n_cand={n_cand} with {n_docs} documents")
-        cand_t = None
-    else:
-        if not isinstance(cand, torch.Tensor):
-            cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(n_q, -1)
-            if cand.size and cand.max() >= n_docs:
-                raise ValueError(f"cand holds document number {int(cand.max())} with {n_docs} documents")
+    elif not isinstance(cand, torch.Tensor):
+        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(n_q, -1)
+        if cand.size and cand.max() >= n_docs:
+            raise ValueError(f"cand holds document number {int(cand.max())} with {n_docs} documents")
+    dev = _need_device(name, q_vecs, d_vecs)
+    cand_t = None
+    if cand is not None:
         cand_t = _dev_i(cand, torch.int32, dev)
         n_cand = int(cand_t.shape[1]) if cand_t.dim() == 2 else int(cand_t.numel() // max(n_q, 1))
     qs, ql = _dev_i(q_start, torch.int32, dev), _dev_i(q_len, torch.int32, dev)
@@ -453,10 +416,10 @@ def maxsim(q_vecs: torch.Tensor, q_start, q_len, d_vecs: torch.Tensor, d_start, 
     scores = torch.empty((n_q, n_cand), dtype=torch.float32, device=dev)
     lib = _lib.load_library()
     with torch.cuda.device(dev):
-        rc = getattr(lib, "tt_maxsim" + sfx)(q_vecs.data_ptr(), qs.data_ptr(), ql.data_ptr(), n_q, d_vecs.data_ptr(), ds.data_ptr(),
-                                             dl.data_ptr(), cand_t.data_ptr() if cand_t is not None else None, n_cand, dim,
-                                             scores.data_ptr(), _stream(dev))
-    _lib.check(rc, "tt_maxsim" + sfx)
+        rc = getattr(lib, entry)(q_vecs.data_ptr(), qs.data_ptr(), ql.data_ptr(), n_q, d_vecs.data_ptr(), ds.data_ptr(), dl.data_ptr(),
+                                 cand_t.data_ptr() if cand_t is not None else None, n_cand, dim, *trailing, scores.data_ptr(),
+                                 _stream(dev))
+    _lib.check(rc, entry)
     return scores
 
 
@@ -623,7 +586,9 @@ class TokenVectorStore:
     """Token vectors of indexed passages, in HBM on one device: 2 * dim bytes per kept token (about 46 KB for a 180-token passage
     at dim 128), plus 12 bytes per passage for its start and length.  ``add`` appends and grows by doubling; ``remove`` frees the
     id only -- the rows stay where they are and are NOT reclaimed (there is no compaction in this version; re-adding an id
-    appends a new copy).  No persistence."""
+    appends a new copy).  No persistence.  Unlike ``LexicalStore`` it writes no tombstone on the device, on ``remove`` or on a
+    re-add: the shared id table forgets the older document number all the same, and nothing here searches the whole store, so a
+    document number no id leads to is never scored."""
 
     # the limits of the kernel that scores the store (``tt_maxsim``); ``multivec.MultiVectorStore`` carries ``tt_maxsim_wide``'s
     DIM_STEP, DIM_LIMIT, DOC_LIMIT = 32, MAX_DIM, MAX_DOC_LEN
@@ -641,21 +606,10 @@ class TokenVectorStore:
         self.d_len = torch.zeros(max(capacity_docs, 1), dtype=torch.int32, device=device)
         self.n_tokens = 0
         self.n_docs = 0
-        self._doc_of: Dict[Any, int] = {}
+        self._ids = IdTable()
 
     def __len__(self) -> int:
-        return len(self._doc_of)
-
-    @staticmethod
-    def _grown(t: torch.Tensor, used: int, need: int) -> torch.Tensor:
-        cap = t.shape[0]
-        if need <= cap:
-            return t
-        while cap < need:
-            cap *= 2
-        new = torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-        new[:used].copy_(t[:used])
-        return new
+        return len(self._ids)
 
     def add(self, node_ids: Sequence[Any], vectors: torch.Tensor, lens) -> np.ndarray:
         """Append the passages' vectors (packed in order: passage i owns the next ``lens[i]`` rows) -> their document numbers."""
@@ -669,9 +623,9 @@ class TokenVectorStore:
         n = len(lens)
         if n == 0:
             return np.zeros(0, dtype=np.int32)
-        self.vectors = self._grown(self.vectors, self.n_tokens, self.n_tokens + total)
-        self.d_start = self._grown(self.d_start, self.n_docs, self.n_docs + n)
-        self.d_len = self._grown(self.d_len, self.n_docs, self.n_docs + n)
+        self.vectors = grown(self.vectors, self.n_tokens, self.n_tokens + total)
+        self.d_start = grown(self.d_start, self.n_docs, self.n_docs + n)
+        self.d_len = grown(self.d_len, self.n_docs, self.n_docs + n)
         starts = np.zeros(n, dtype=np.int64)
         np.cumsum(lens[:-1], out=starts[1:])
         starts += self.n_tokens
@@ -679,19 +633,18 @@ class TokenVectorStore:
         self.d_start[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(starts))
         self.d_len[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(lens))
         docs = np.arange(self.n_docs, self.n_docs + n, dtype=np.int32)
-        for nid, d in zip(node_ids, docs):
-            self._doc_of[nid] = int(d)
+        self._ids.assign(node_ids)
         self.n_tokens += total
         self.n_docs += n
         return docs
 
     def remove(self, node_id: Any) -> bool:
         """Forget ``node_id`` -> whether it was stored.  Its rows are not reclaimed."""
-        return self._doc_of.pop(node_id, None) is not None
+        return self._ids.pop(node_id) is not None
 
     def lookup(self, node_ids: Sequence[Any]) -> np.ndarray:
         """-> document numbers (int32), -1 for an id that is not stored."""
-        return np.fromiter((self._doc_of.get(n, -1) for n in node_ids), dtype=np.int32, count=len(node_ids))
+        return self._ids.lookup(node_ids)
 
     @property
     def nbytes(self) -> int:
@@ -708,7 +661,7 @@ class TokenVectorStore:
 
 
 # ---- postprocessor ---------------------------------------------------------------------------------------------------------------
-class HipColbertRerank:
+class HipColbertRerank(_StoredRerank):
     """Late-interaction rerank postprocessor with the surface of ``HipSentenceTransformerRerank``: ``postprocess_nodes`` (keyword
     or positional), ``rerank``, ``predict``, ``.model`` (the weights, with ``.parameters()``) -- plus ``index_nodes``, which
     encodes nodes' EMBED-mode content into the instance's ``TokenVectorStore``.  At query time a stored node is scored from the
@@ -720,11 +673,7 @@ class HipColbertRerank:
         from . import weights as _weights
         from .tokenization import load_tokenizer
 
-        dev = torch.device("cuda" if device in (None, "cuda") else device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"device '{device}': tensor_truth_amd runs on HIP devices only (no CPU path)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = resolve_device(device)
         mk = dict(model_kwargs or {})
         self.model_name, self.top_n, self.device, self.keep_retrieval_score = model, top_n, dev, keep_retrieval_score
         dtype = resolve_dtype(mk)
@@ -749,94 +698,24 @@ class HipColbertRerank:
         self.precision = "fp16 (fp32 accumulate)" if dtype == torch.float16 else "bf16 (fp32 accumulate)"
         self.stats = {"queries": 0, "stored": 0, "encoded": 0}
 
-    # ---- ingest -----------------------------------------------------------------------------------------------------
-    def index_nodes(self, nodes) -> int:
-        """Encode the nodes' EMBED-mode content into the store (a ``NodeWithScore`` or a bare node) -> how many were added."""
-        from .schema import MetadataMode
+    # ---- what _StoredRerank asks for --------------------------------------------------------------------------------
+    def encode_queries(self, texts) -> TokenVectors:
+        return self.encoder.encode_queries(texts)
 
-        bare = [getattr(n, "node", n) for n in nodes]
-        if not bare:
-            return 0
-        tv = self.encoder.encode_documents([n.get_content(metadata_mode=MetadataMode.EMBED) for n in bare])
-        self.store.add([n.id_ for n in bare], tv.vectors, tv.lens)
-        return len(bare)
+    def encode_documents(self, texts) -> TokenVectors:
+        return self.encoder.encode_documents(texts)
 
-    # ---- scoring ----------------------------------------------------------------------------------------------------
-    def _score(self, queries: List[str], docs: List[Any], pairs: List[Tuple[int, int]], stored: Optional[np.ndarray] = None) -> List[float]:
-        """Scores of ``pairs`` (query number, document number).  ``stored[d]`` >= 0: document d is that entry of the store; else
-        ``docs[d]`` (text) is encoded here."""
-        qv = self.encoder.encode_queries(queries)
-        n_q = len(queries)
-        stored = np.full(len(docs), -1, dtype=np.int32) if stored is None else stored
-        per_q: List[List[int]] = [[] for _ in range(n_q)]
-        for q, d in pairs:
-            per_q[q].append(d)
-        width = max(len(p) for p in per_q)
-        fresh = [d for d in range(len(docs)) if stored[d] < 0]
-        out: Dict[Tuple[int, int], float] = {}
-        if len(fresh) < len(docs):
-            cand = np.full((n_q, width), -1, dtype=np.int32)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    cand[q, j] = stored[d]
-            s = self.store.score(qv, cand).cpu().numpy()
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    if stored[d] >= 0:
-                        out[(q, d)] = float(s[q, j])
-        if fresh:
-            tv = self.encoder.encode_documents([docs[d] for d in fresh])
-            slot = {d: i for i, d in enumerate(fresh)}
-            cand = np.full((n_q, width), -1, dtype=np.int32)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    cand[q, j] = slot.get(d, -1)
-            s = maxsim(qv.vectors, qv.starts.astype(np.int32), qv.lens, tv.vectors, tv.starts, tv.lens, cand=cand).cpu().numpy()
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    if stored[d] < 0:
-                        out[(q, d)] = float(s[q, j])
-        st = self.stats
-        st["queries"] += n_q
-        st["stored"] += len(docs) - len(fresh)
-        st["encoded"] += len(fresh)
-        return [out[p] for p in pairs]
+    def add_documents(self, nodes, tv: TokenVectors) -> None:
+        self.store.add([n.id_ for n in nodes], tv.vectors, tv.lens)
 
-    def predict(self, pairs: Sequence[Sequence[str]]) -> List[float]:
-        """[(query, passage), ...] -> MaxSim scores; every passage is encoded in the call."""
-        pairs = list(pairs)
-        if not pairs:
-            return []
-        q_no: Dict[str, int] = {}
-        d_no: Dict[str, int] = {}
-        idx = [(q_no.setdefault(q, len(q_no)), d_no.setdefault(d, len(d_no))) for q, d in pairs]
-        return self._score(list(q_no), list(d_no), idx)
+    def lookup(self, ids) -> np.ndarray:
+        return self.store.lookup(ids)
 
-    def postprocess_nodes(self, nodes, query_bundle=None, query_str: Optional[str] = None):
-        from .schema import MetadataMode
+    def score_stored(self, qv: TokenVectors, cands) -> np.ndarray:
+        return self.store.score(qv, cands[0]).cpu().numpy()
 
-        if query_bundle is None and query_str is None:
-            raise ValueError("Missing query bundle in extra info.")
-        q = query_str if query_bundle is None else query_bundle.query_str
-        if len(nodes) == 0:
-            return []
-        stored = self.store.lookup([n.node.id_ for n in nodes])
-        docs = [None if s >= 0 else n.node.get_content(metadata_mode=MetadataMode.EMBED) for n, s in zip(nodes, stored)]
-        scores = self._score([q], docs, [(0, d) for d in range(len(nodes))], stored)
-        for n, s in zip(nodes, scores):
-            if self.keep_retrieval_score:
-                n.node.metadata["retrieval_score"] = n.score
-            n.score = float(s)
-        return sorted(nodes, key=lambda x: -x.score)[: self.top_n]
-
-    _postprocess_nodes = postprocess_nodes
-
-    def rerank(self, query: str, documents: Sequence[str], top_n: Optional[int] = None):
-        scores = self.predict([(query, d) for d in documents])
-        order = sorted(range(len(documents)), key=lambda i: -scores[i])
-        if top_n is not None:
-            order = order[:top_n]
-        return [{"index": i, "relevance_score": float(scores[i])} for i in order]
+    def score_fresh(self, qv: TokenVectors, tv: TokenVectors, cand) -> np.ndarray:
+        return maxsim(qv.vectors, qv.starts.astype(np.int32), qv.lens, tv.vectors, tv.starts, tv.lens, cand=cand).cpu().numpy()
 
 
 def synthetic_state(cfg: EncoderConfig, dim: int, seed: int = 0) -> Dict[str, torch.Tensor]:

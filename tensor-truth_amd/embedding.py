@@ -18,6 +18,7 @@ import torch
 
 from . import weights as _weights
 from . import precision as _precision
+from ._hostargs import resolve_device
 from .encoder import pack_tokens
 from .tokenization import load_tokenizer
 
@@ -62,11 +63,7 @@ class HipHuggingFaceEmbedding:
                  query_instruction: Optional[str] = None, text_instruction: Optional[str] = None, **_ignored):
         if not (0 < embed_batch_size <= 2048):
             raise ValueError(f"embed_batch_size {embed_batch_size} not in (0, 2048]")
-        dev = torch.device("cuda" if device in (None, "cuda") else device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"device '{device}': tensor_truth_amd runs on HIP devices only (no CPU path)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = resolve_device(device)
         self.model_name = model_name
         self.device = dev
         self.embed_batch_size = embed_batch_size

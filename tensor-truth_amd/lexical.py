@@ -26,6 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._hostargs import _check_range, _dev_i, _need_device, _stream, grown
+from ._stored import IdTable, _StoredRerank, top_nodes
 from .encoder import pack_tokens
 
 SPARSE_FILE = "sparse_linear.pt"
@@ -97,34 +99,6 @@ def check_hybrid_weights(model_kwargs: Optional[dict]) -> Tuple[float, float]:
 
 
 # ---- host wrappers of the kernels ------------------------------------------------------------------------------------------------
-def _stream(dev: torch.device):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _check_range(name: str, a, lo: int, hi) -> None:
-    a = np.asarray(a)
-    bad = (a < lo) | (a > hi)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"{name}[{i}]={int(a.flat[i])} is outside {lo} .. {int(np.asarray(hi).flat[i]) if np.ndim(hi) else hi}")
-
-
-def _dev_i(a, dtype, dev: torch.device) -> torch.Tensor:
-    if isinstance(a, torch.Tensor):
-        if a.device.type != dev.type or (dev.index is not None and a.device.index != dev.index) or a.dtype != dtype \
-                or not a.is_contiguous():
-            raise ValueError(f"a contiguous device array of {dtype} on {dev} is expected")
-        return a
-    return torch.from_numpy(np.ascontiguousarray(a, dtype={torch.int32: np.int32, torch.int64: np.int64}[dtype])).to(dev)
-
-
-def _need_device(name: str, *tensors: torch.Tensor) -> torch.device:
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError(f"{name}: device tensors are needed; tensor_truth_amd has no CPU path")
-    return dev
-
-
 _WEIGHTS_ENTRY = {torch.bfloat16: "tt_lexical_weights", torch.float16: "tt_lexical_weights_f16", torch.float32: "tt_lexical_weights_f32"}
 
 
@@ -404,11 +378,12 @@ class M3Encoder:
 
 # ---- the store ----------------------------------------------------------------------------------------------------------------------
 class LexicalStore:
-    """Lexical vectors and dense rows of indexed passages, in HBM on one device: CSR arrays (``d_start`` int64, ``d_nnz`` int32 per
-    document; ``terms`` int32 and ``weights`` fp32 per distinct token: 8 bytes) plus one bf16 dense row of ``dim`` values per
-    document number.  ``add`` appends and grows by doubling; ``remove`` frees the id and writes ``d_nnz = -1`` on the device, so
-    that neither ``score`` nor ``search`` returns the document -- its entries stay where they are and are NOT reclaimed (there
-    is no compaction in this version; re-adding an id appends a new copy).  No persistence.
+    """Lexical vectors and -- with ``dim`` > 0 -- dense rows of indexed passages, in HBM on one device: CSR arrays (``d_start``
+    int64, ``d_nnz`` int32 per document; ``terms`` int32 and ``weights`` fp32 per distinct token: 8 bytes) plus one bf16 dense row
+    of ``dim`` values per document number (``dim`` 0 or None: no dense rows, ``dense`` is None and ``add`` takes none -- what
+    ``splade.SpladeStore`` is).  ``add`` appends and grows by doubling; ``remove`` frees the id and writes ``d_nnz = -1`` on the
+    device, so that neither ``score`` nor ``search`` returns the document -- its entries stay where they are and are NOT reclaimed
+    (there is no compaction in this version; re-adding an id appends a new copy and buries the older one).  No persistence.
 
     ``postings=True`` (with ``vocab_size``, the ids' range): ``seal()`` builds posting lists over the documents stored so far
     (``postings.py``: 4 bytes per entry + 12 per vocabulary id), and ``search`` then scores only the documents on the query's own
@@ -416,29 +391,26 @@ class LexicalStore:
     documents in the tail and re-seals once the tail exceeds ``max(65536, n_sealed / 4)`` documents; ``remove`` leaves the lists
     alone (a tombstone on a list scores NaN and is never selected).  ``stats``: the last search's figures."""
 
-    def __init__(self, dim: int, device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10,
+    def __init__(self, dim: Optional[int], device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10,
                  postings: bool = False, vocab_size: Optional[int] = None):
-        if dim <= 0 or dim % 128 or dim > MAX_HIDDEN:
-            raise ValueError(f"LexicalStore: dim={dim} (a multiple of 128 up to {MAX_HIDDEN})")
+        name, dim = type(self).__name__, int(dim or 0)
+        if dim < 0 or dim % 128 or dim > MAX_HIDDEN:
+            raise ValueError(f"{name}: dim={dim} (a multiple of 128 up to {MAX_HIDDEN})")
+        self.postings = bool(postings)
+        if self.postings and (vocab_size is None or int(vocab_size) < 1):
+            raise ValueError(f"postings=True needs vocab_size (every stored id lies in [0, vocab_size)), not {vocab_size!r}")
         if device.type != "cuda":
-            raise RuntimeError("LexicalStore lives on a HIP device; tensor_truth_amd has no CPU path")
+            raise RuntimeError(f"{name} lives on a HIP device; tensor_truth_amd has no CPU path")
         self.dim, self.device = dim, device
         self.terms = torch.zeros(max(capacity_terms, 1), dtype=torch.int32, device=device)
         self.weights = torch.zeros(max(capacity_terms, 1), dtype=torch.float32, device=device)
         self.d_start = torch.zeros(max(capacity_docs, 1), dtype=torch.int64, device=device)
         self.d_nnz = torch.zeros(max(capacity_docs, 1), dtype=torch.int32, device=device)
-        self.dense = torch.zeros((max(capacity_docs, 1), dim), dtype=torch.bfloat16, device=device)
+        self.dense = torch.zeros((max(capacity_docs, 1), dim), dtype=torch.bfloat16, device=device) if dim else None
         self.n_terms = 0
         self.n_docs = 0
-        self._doc_of: Dict[Any, int] = {}
-        self._id_of: List[Any] = []          # document number -> node id (None once removed)
+        self._ids = IdTable()
         self._ws: Optional[torch.Tensor] = None
-        self._init_postings(postings, vocab_size)
-
-    def _init_postings(self, postings: bool, vocab_size: Optional[int]) -> None:
-        self.postings = bool(postings)
-        if self.postings and (vocab_size is None or int(vocab_size) < 1):
-            raise ValueError(f"postings=True needs vocab_size (every stored id lies in [0, vocab_size)), not {vocab_size!r}")
         self.vocab_size = None if vocab_size is None else int(vocab_size)
         self.index = None                    # postings.PostingsIndex over documents [0, index.n_sealed)
         self._pws: Optional[torch.Tensor] = None
@@ -470,27 +442,19 @@ class LexicalStore:
             self.seal()
 
     def __len__(self) -> int:
-        return len(self._doc_of)
+        return len(self._ids)
 
-    @staticmethod
-    def _grown(t: torch.Tensor, used: int, need: int) -> torch.Tensor:
-        cap = t.shape[0]
-        if need <= cap:
-            return t
-        while cap < need:
-            cap *= 2
-        new = torch.zeros((cap,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-        new[:used].copy_(t[:used])
-        return new
-
-    def add(self, node_ids: Sequence[Any], lexical: LexicalWeights, dense: torch.Tensor) -> np.ndarray:
-        """Append the passages' lexical vectors and dense rows (fp32 or bf16 [n][dim]; rounded to bf16 to nearest even) -> their
-        document numbers."""
+    def add(self, node_ids: Sequence[Any], lexical: LexicalWeights, dense: Optional[torch.Tensor] = None) -> np.ndarray:
+        """Append the passages' lexical vectors and -- exactly when the store has dense rows -- their dense rows (fp32 or bf16
+        [n][dim]; rounded to bf16 to nearest even) -> their document numbers."""
         nnz = np.ascontiguousarray(lexical.nnz, dtype=np.int32)
         n = len(nnz)
-        if len(node_ids) != n or dense.dim() != 2 or tuple(dense.shape) != (n, self.dim):
-            raise ValueError(f"add: {len(node_ids)} node ids, {n} lexical vectors and dense {tuple(dense.shape)} do not match "
-                             f"[n][{self.dim}]")
+        if (dense is None) == bool(self.dim):
+            raise ValueError(f"add: dense rows are needed by a store with dim={self.dim}" if self.dim else
+                             "add: dense rows are not taken by a store without them (dim=0)")
+        if len(node_ids) != n or (dense is not None and (dense.dim() != 2 or tuple(dense.shape) != (n, self.dim))):
+            raise ValueError(f"add: {len(node_ids)} node ids, {n} lexical vectors" + (" do not match" if dense is None else
+                             f" and dense {tuple(dense.shape)} do not match [n][{self.dim}]"))
         _check_range("nnz", nnz, 0, MAX_DOC_NNZ)
         total = int(nnz.sum())
         if lexical.terms.numel() != total or lexical.weights.numel() != total:
@@ -502,53 +466,46 @@ class LexicalStore:
         if n == 0:
             return np.zeros(0, dtype=np.int32)
         self._check_vocab(lexical)
-        self.terms = self._grown(self.terms, self.n_terms, self.n_terms + total)
-        self.weights = self._grown(self.weights, self.n_terms, self.n_terms + total)
-        self.d_start = self._grown(self.d_start, self.n_docs, self.n_docs + n)
-        self.d_nnz = self._grown(self.d_nnz, self.n_docs, self.n_docs + n)
-        self.dense = self._grown(self.dense, self.n_docs, self.n_docs + n)
+        self.terms = grown(self.terms, self.n_terms, self.n_terms + total)
+        self.weights = grown(self.weights, self.n_terms, self.n_terms + total)
+        self.d_start = grown(self.d_start, self.n_docs, self.n_docs + n)
+        self.d_nnz = grown(self.d_nnz, self.n_docs, self.n_docs + n)
         self.terms[self.n_terms:self.n_terms + total].copy_(lexical.terms.to(self.device))
         self.weights[self.n_terms:self.n_terms + total].copy_(lexical.weights.to(self.device))
         self.d_start[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(want + self.n_terms))
         self.d_nnz[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(nnz))
-        self.dense[self.n_docs:self.n_docs + n].copy_(dense.to(device=self.device, dtype=torch.bfloat16))
+        if dense is not None:
+            self.dense = grown(self.dense, self.n_docs, self.n_docs + n)
+            self.dense[self.n_docs:self.n_docs + n].copy_(dense.to(device=self.device, dtype=torch.bfloat16))
         docs = np.arange(self.n_docs, self.n_docs + n, dtype=np.int32)
-        for nid, d in zip(node_ids, docs):
-            old = self._doc_of.get(nid)
-            if old is not None:              # re-added: the older copy becomes a tombstone
-                self._bury(old)
-            self._doc_of[nid] = int(d)
-            self._id_of.append(nid)
+        for old in self._ids.assign(node_ids):           # re-added: the older copy becomes a tombstone
+            self.d_nnz[old:old + 1].fill_(-1)
         self.n_terms += total
         self.n_docs += n
         self._after_add()
         return docs
 
-    def _bury(self, doc: int) -> None:
-        self.d_nnz[doc:doc + 1].fill_(-1)
-        self._id_of[doc] = None
-
     def remove(self, node_id: Any) -> bool:
         """Forget ``node_id`` -> whether it was stored.  Its document number becomes a tombstone; its entries are not reclaimed."""
-        doc = self._doc_of.pop(node_id, None)
+        doc = self._ids.pop(node_id)
         if doc is None:
             return False
-        self._bury(doc)
+        self.d_nnz[doc:doc + 1].fill_(-1)
         return True
 
     def lookup(self, node_ids: Sequence[Any]) -> np.ndarray:
         """-> document numbers (int32), -1 for an id that is not stored."""
-        return np.fromiter((self._doc_of.get(n, -1) for n in node_ids), dtype=np.int32, count=len(node_ids))
+        return self._ids.lookup(node_ids)
 
     def node_id(self, doc: int) -> Any:
         """The node id of document number ``doc`` (None: removed, or no such document)."""
-        return self._id_of[doc] if 0 <= doc < len(self._id_of) else None
+        return self._ids.node_id(doc)
 
     @property
     def nbytes(self) -> int:
         """Bytes the store holds in HBM (capacity, not fill)."""
-        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz, self.dense)) \
-            + (0 if self.index is None else self.index.nbytes)
+        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz, self.dense)
+                   if t is not None) + (0 if self.index is None else self.index.nbytes)
 
     @staticmethod
     def _check_query(lexical: LexicalWeights) -> np.ndarray:
@@ -601,7 +558,7 @@ class _M3Model:
         return sum(t.numel() * t.element_size() for t in self.parameters())
 
 
-class HipM3HybridRerank:
+class HipM3HybridRerank(_StoredRerank):
     """Hybrid (dense + lexical) rerank postprocessor with the surface of ``HipColbertRerank``: ``postprocess_nodes`` (keyword or
     positional), ``rerank``, ``predict``, ``.model`` (with ``.parameters()``), ``index_nodes``, ``stats``.  ``index_nodes`` encodes
     nodes' EMBED-mode content once into the instance's ``LexicalStore`` (and keeps the nodes, for ``HipLexicalRetriever``).  At
@@ -635,103 +592,35 @@ class HipM3HybridRerank:
         self.nodes: Dict[Any, Any] = {}      # node id -> the indexed node (what HipLexicalRetriever returns)
         self.stats = {"queries": 0, "stored": 0, "encoded": 0}
 
-    # ---- ingest -----------------------------------------------------------------------------------------------------
-    def index_nodes(self, nodes) -> int:
-        """Encode the nodes' EMBED-mode content into the store (a ``NodeWithScore`` or a bare node) -> how many were added."""
-        from .schema import MetadataMode
-
-        bare = [getattr(n, "node", n) for n in nodes]
-        if not bare:
-            return 0
-        dense, lw = self.encoder.encode([n.get_content(metadata_mode=MetadataMode.EMBED) for n in bare], is_query=False)
-        self.store.add([n.id_ for n in bare], lw, dense)
-        for n in bare:
-            self.nodes[n.id_] = n
-        return len(bare)
-
     def remove_node(self, node_id: Any) -> bool:
         self.nodes.pop(node_id, None)
         return self.store.remove(node_id)
 
-    # ---- scoring ----------------------------------------------------------------------------------------------------
-    def _score(self, queries: List[str], docs: List[Any], pairs: List[Tuple[int, int]], stored: Optional[np.ndarray] = None) -> List[float]:
-        """Hybrid scores of ``pairs`` (query number, document number).  ``stored[d]`` >= 0: document d is that entry of the store;
-        else ``docs[d]`` (text) is encoded here."""
-        q_dense, q_lw = self.encoder.encode(queries, is_query=True)
-        n_q = len(queries)
-        stored = np.full(len(docs), -1, dtype=np.int32) if stored is None else stored
-        per_q: List[List[int]] = [[] for _ in range(n_q)]
-        for q, d in pairs:
-            per_q[q].append(d)
-        width = max(len(p) for p in per_q)
-        fresh = [d for d in range(len(docs)) if stored[d] < 0]
-        out: Dict[Tuple[int, int], float] = {}
-        if len(fresh) < len(docs):
-            cand = np.full((n_q, width), -1, dtype=np.int32)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    cand[q, j] = stored[d]
-            s = self.store.score(q_lw, cand, dense=q_dense, hybrid_weights=self.hybrid_weights)[2].cpu().numpy()
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    if stored[d] >= 0:
-                        out[(q, d)] = float(s[q, j])
-        if fresh:
-            d_dense, d_lw = self.encoder.encode([docs[d] for d in fresh], is_query=False)
-            _check_range("d_nnz", d_lw.nnz, 0, MAX_DOC_NNZ)
-            slot = {d: i for i, d in enumerate(fresh)}
-            cand = np.full((n_q, width), -1, dtype=np.int32)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    cand[q, j] = slot.get(d, -1)
-            s = lexical_score(q_lw.terms, q_lw.weights, LexicalStore._check_query(q_lw), q_lw.nnz, d_lw.terms, d_lw.weights, d_lw.starts,
-                              d_lw.nnz, cand=cand, q_dense=q_dense.to(torch.bfloat16), d_dense=d_dense.to(torch.bfloat16),
-                              hybrid_weights=self.hybrid_weights)[2].cpu().numpy()
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    if stored[d] < 0:
-                        out[(q, d)] = float(s[q, j])
-        st = self.stats
-        st["queries"] += n_q
-        st["stored"] += len(docs) - len(fresh)
-        st["encoded"] += len(fresh)
-        return [out[p] for p in pairs]
+    # ---- what _StoredRerank asks for --------------------------------------------------------------------------------
+    def encode_queries(self, texts):
+        return self.encoder.encode(texts, is_query=True)
 
-    def predict(self, pairs: Sequence[Sequence[str]]) -> List[float]:
-        """[(query, passage), ...] -> hybrid scores; every passage is encoded in the call."""
-        pairs = list(pairs)
-        if not pairs:
-            return []
-        q_no: Dict[str, int] = {}
-        d_no: Dict[str, int] = {}
-        idx = [(q_no.setdefault(q, len(q_no)), d_no.setdefault(d, len(d_no))) for q, d in pairs]
-        return self._score(list(q_no), list(d_no), idx)
+    def encode_documents(self, texts):
+        return self.encoder.encode(texts, is_query=False)
 
-    def postprocess_nodes(self, nodes, query_bundle=None, query_str: Optional[str] = None):
-        from .schema import MetadataMode
+    def add_documents(self, nodes, encoded) -> None:
+        dense, lw = encoded
+        self.store.add([n.id_ for n in nodes], lw, dense)
+        self.nodes.update((n.id_, n) for n in nodes)
 
-        if query_bundle is None and query_str is None:
-            raise ValueError("Missing query bundle in extra info.")
-        q = query_str if query_bundle is None else query_bundle.query_str
-        if len(nodes) == 0:
-            return []
-        stored = self.store.lookup([n.node.id_ for n in nodes])
-        docs = [None if s >= 0 else n.node.get_content(metadata_mode=MetadataMode.EMBED) for n, s in zip(nodes, stored)]
-        scores = self._score([q], docs, [(0, d) for d in range(len(nodes))], stored)
-        for n, s in zip(nodes, scores):
-            if self.keep_retrieval_score:
-                n.node.metadata["retrieval_score"] = n.score
-            n.score = float(s)
-        return sorted(nodes, key=lambda x: -x.score)[: self.top_n]
+    def lookup(self, ids) -> np.ndarray:
+        return self.store.lookup(ids)
 
-    _postprocess_nodes = postprocess_nodes
+    def score_stored(self, q, cands) -> np.ndarray:
+        q_dense, q_lw = q
+        return self.store.score(q_lw, cands[0], dense=q_dense, hybrid_weights=self.hybrid_weights)[2].cpu().numpy()
 
-    def rerank(self, query: str, documents: Sequence[str], top_n: Optional[int] = None):
-        scores = self.predict([(query, d) for d in documents])
-        order = sorted(range(len(documents)), key=lambda i: -scores[i])
-        if top_n is not None:
-            order = order[:top_n]
-        return [{"index": i, "relevance_score": float(scores[i])} for i in order]
+    def score_fresh(self, q, d, cand) -> np.ndarray:
+        (q_dense, q_lw), (d_dense, d_lw) = q, d
+        _check_range("d_nnz", d_lw.nnz, 0, MAX_DOC_NNZ)
+        return lexical_score(q_lw.terms, q_lw.weights, LexicalStore._check_query(q_lw), q_lw.nnz, d_lw.terms, d_lw.weights, d_lw.starts,
+                             d_lw.nnz, cand=cand, q_dense=q_dense.to(torch.bfloat16), d_dense=d_dense.to(torch.bfloat16),
+                             hybrid_weights=self.hybrid_weights)[2].cpu().numpy()
 
 
 class HipLexicalRetriever:
@@ -754,14 +643,4 @@ class HipLexicalRetriever:
             from .schema import NodeWithScore as node_type
         rr = self.reranker
         _, lw = rr.encoder.encode([query_bundle.query_str], is_query=True)
-        if rr.store.postings and rr.store.index is None:
-            rr.store.seal()
-        scores, idx = rr.store.search(lw, self.similarity_top_k)
-        out = []
-        for s, d in zip(scores[0].cpu().tolist(), idx[0].cpu().tolist()):
-            if d < 0 or not s > 0:
-                continue
-            node = rr.nodes.get(rr.store.node_id(d))
-            if node is not None:
-                out.append(node_type(node=node, score=float(s)))
-        return out
+        return top_nodes(rr.store, lw, self.similarity_top_k, rr.nodes, node_type)

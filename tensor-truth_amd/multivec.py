@@ -27,7 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .colbert import TokenVectors, TokenVectorStore, _check_range, _dev_i, _stream
+from ._hostargs import _check_range, _dev_i, _stream
+from ._stored import _StoredRerank
+from .colbert import TokenVectors, TokenVectorStore, _maxsim
 from .lexical import (MAX_DOC_NNZ, SPARSE_FILE, LexicalStore, LexicalWeights, M3Encoder, _M3Model, has_lexical_head, lexical_score,
                       load_sparse_head)
 
@@ -89,7 +91,6 @@ def check_m3_weights(model_kwargs: Optional[dict]) -> Tuple[float, float, float]
 # ---- host wrappers of the kernels ------------------------------------------------------------------------------------------------
 _PROJECT_ENTRY = {torch.bfloat16: ("tt_multivec_project", torch.bfloat16), torch.float16: ("tt_multivec_project_f16", torch.float16),
                   torch.float32: ("tt_multivec_project_f32", torch.float16)}
-_MAXSIM_ENTRY = {torch.bfloat16: "tt_maxsim_wide", torch.float16: "tt_maxsim_wide_f16"}
 
 
 def _check_dim(what: str, dim: int) -> None:
@@ -137,48 +138,8 @@ def maxsim_wide(q_vecs: torch.Tensor, q_start, q_len, d_vecs: torch.Tensor, d_st
     (q_len 1 .. 512, d_len 0 .. 8192, rows inside the buffers) before anything touches a device, and uploaded; device tensors are
     taken as they are -- their owner (``MultiVectorStore``, ``M3MultiVectorEncoder``) checked them when it made them, and the kernel
     clamps a length into its range."""
-    if q_vecs.dtype != d_vecs.dtype or q_vecs.dim() != 2 or d_vecs.dim() != 2 or q_vecs.shape[1] != d_vecs.shape[1]:
-        raise ValueError("maxsim_wide: query and document vectors must be [*, dim] of one 16-bit type")
-    name = _MAXSIM_ENTRY.get(q_vecs.dtype)
-    if name is None:
-        raise ValueError(f"maxsim_wide: 16-bit operands are bfloat16 or float16, not {q_vecs.dtype}")
-    dim = int(q_vecs.shape[1])
-    _check_dim("maxsim_wide", dim)
-    if not (q_vecs.is_contiguous() and d_vecs.is_contiguous()):
-        raise ValueError("maxsim_wide: row-major vectors with a row stride of dim are needed")
-    n_q = len(q_len)
-    if not isinstance(q_len, torch.Tensor):
-        _check_range("q_len", q_len, 1, MAX_QUERY_LEN)
-        _check_range("q_start", q_start, 0, q_vecs.shape[0] - np.asarray(q_len))
-    if not isinstance(d_len, torch.Tensor):
-        _check_range("d_len", d_len, 0, MAX_DOC_LEN)
-        _check_range("d_start", d_start, 0, d_vecs.shape[0] - np.asarray(d_len))
-    n_docs = len(d_len)
-    if cand is None:
-        n_cand = n_docs if n_cand is None else int(n_cand)
-        if not 0 <= n_cand <= n_docs:
-            raise ValueError(f"n_cand={n_cand} with {n_docs} documents")
-    elif not isinstance(cand, torch.Tensor):
-        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(n_q, -1)
-        if cand.size and cand.max() >= n_docs:
-            raise ValueError(f"cand holds document number {int(cand.max())} with {n_docs} documents")
-    dev = q_vecs.device                                   # (the host-side refusals above need no device)
-    if dev.type != "cuda" or d_vecs.device != dev:
-        raise RuntimeError("maxsim_wide: device tensors are needed; tensor_truth_amd has no CPU path")
-    cand_t = None
-    if cand is not None:
-        cand_t = _dev_i(cand, torch.int32, dev)
-        n_cand = int(cand_t.shape[1]) if cand_t.dim() == 2 else int(cand_t.numel() // max(n_q, 1))
-    qs, ql = _dev_i(q_start, torch.int32, dev), _dev_i(q_len, torch.int32, dev)
-    ds, dl = _dev_i(d_start, torch.int64, dev), _dev_i(d_len, torch.int32, dev)
-    scores = torch.empty((n_q, n_cand), dtype=torch.float32, device=dev)
-    lib = _lib.load_library()
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(q_vecs.data_ptr(), qs.data_ptr(), ql.data_ptr(), n_q, d_vecs.data_ptr(), ds.data_ptr(), dl.data_ptr(),
-                                cand_t.data_ptr() if cand_t is not None else None, n_cand, dim, 1 if mean else 0, scores.data_ptr(),
-                                _stream(dev))
-    _lib.check(rc, name)
-    return scores
+    return _maxsim("maxsim_wide", "tt_maxsim_wide", MAX_QUERY_LEN, MAX_DOC_LEN, _check_dim, (1 if mean else 0,), q_vecs, q_start, q_len,
+                   d_vecs, d_start, d_len, cand, n_cand)
 
 
 def m3_mix(dense: torch.Tensor, lex: torch.Tensor, mv: torch.Tensor, weights: Sequence[float]) -> torch.Tensor:
@@ -307,7 +268,7 @@ class MultiVectorStore(TokenVectorStore):
 
 
 # ---- postprocessor ---------------------------------------------------------------------------------------------------------------
-class HipM3AllRerank:
+class HipM3AllRerank(_StoredRerank):
     """Rerank postprocessor over all three heads of BGE-M3, with the surface of ``HipM3HybridRerank``: ``postprocess_nodes`` (keyword
     or positional), ``rerank``, ``predict``, ``.model`` (with ``.parameters()``), ``index_nodes``, ``remove_node``, ``stats``.
     ``index_nodes`` encodes nodes' EMBED-mode content once into the instance's ``LexicalStore`` and ``MultiVectorStore``.  At query
@@ -343,118 +304,44 @@ class HipM3AllRerank:
         self.nodes: Dict[Any, Any] = {}
         self.stats = {"queries": 0, "stored": 0, "encoded": 0}
 
-    # ---- ingest -----------------------------------------------------------------------------------------------------
-    def index_nodes(self, nodes) -> int:
-        """Encode the nodes' EMBED-mode content into the two stores (a ``NodeWithScore`` or a bare node) -> how many were added."""
-        from .schema import MetadataMode
-
-        bare = [getattr(n, "node", n) for n in nodes]
-        if not bare:
-            return 0
-        dense, lw, tv = self.encoder.encode([n.get_content(metadata_mode=MetadataMode.EMBED) for n in bare], is_query=False)
-        ids = [n.id_ for n in bare]
-        self.store.add(ids, lw, dense)
-        self.vectors.add(ids, tv.vectors, tv.lens)
-        for n in bare:
-            self.nodes[n.id_] = n
-        return len(bare)
-
     def remove_node(self, node_id: Any) -> bool:
         self.nodes.pop(node_id, None)
         self.vectors.remove(node_id)
         return self.store.remove(node_id)
 
-    # ---- scoring ----------------------------------------------------------------------------------------------------
+    # ---- what _StoredRerank asks for --------------------------------------------------------------------------------
+    def encode_queries(self, texts):
+        return self.encoder.encode(texts, is_query=True)
+
+    def encode_documents(self, texts):
+        return self.encoder.encode(texts, is_query=False)
+
+    def add_documents(self, nodes, encoded) -> None:
+        dense, lw, tv = encoded
+        ids = [n.id_ for n in nodes]
+        self.store.add(ids, lw, dense)
+        self.vectors.add(ids, tv.vectors, tv.lens)
+        self.nodes.update((n.id_, n) for n in nodes)
+
+    def lookup(self, ids) -> np.ndarray:
+        return np.stack((self.store.lookup(ids), self.vectors.lookup(ids)))
+
     def _mix(self, lex: torch.Tensor, dense: torch.Tensor, mv: torch.Tensor) -> np.ndarray:
         return m3_mix(dense, lex, mv, self.m3_weights).cpu().numpy()
 
-    def _score(self, queries: List[str], docs: List[Any], pairs: List[Tuple[int, int]], stored: Optional[np.ndarray] = None,
-               stored_mv: Optional[np.ndarray] = None) -> List[float]:
-        """Combined scores of ``pairs`` (query number, document number).  ``stored[d]`` >= 0: document d is that entry of the
-        lexical store and ``stored_mv[d]`` that of the vector store; else ``docs[d]`` (text) is encoded here."""
-        q_dense, q_lw, q_tv = self.encoder.encode(queries, is_query=True)
-        n_q = len(queries)
-        stored = np.full(len(docs), -1, dtype=np.int32) if stored is None else stored
-        stored_mv = np.full(len(docs), -1, dtype=np.int32) if stored_mv is None else stored_mv
-        per_q: List[List[int]] = [[] for _ in range(n_q)]
-        for q, d in pairs:
-            per_q[q].append(d)
-        width = max(len(p) for p in per_q)
-        fresh = [d for d in range(len(docs)) if stored[d] < 0]
-        hw = (1.0, 1.0)          # (tt_lexical_score's own mix is not read: its lex and dense outputs are)
-        q_start = LexicalStore._check_query(q_lw)
-        out: Dict[Tuple[int, int], float] = {}
-        if len(fresh) < len(docs):
-            cand = np.full((n_q, width), -1, dtype=np.int32)
-            cand_mv = np.full((n_q, width), -1, dtype=np.int32)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    cand[q, j] = stored[d]
-                    cand_mv[q, j] = stored_mv[d] if stored[d] >= 0 else -1
-            lex, dense, _ = self.store.score(q_lw, cand, dense=q_dense, hybrid_weights=hw)
-            s = self._mix(lex, dense, self.vectors.score(q_tv, cand_mv, mean=True))
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    if stored[d] >= 0:
-                        out[(q, d)] = float(s[q, j])
-        if fresh:
-            d_dense, d_lw, d_tv = self.encoder.encode([docs[d] for d in fresh], is_query=False)
-            _check_range("d_nnz", d_lw.nnz, 0, MAX_DOC_NNZ)
-            slot = {d: i for i, d in enumerate(fresh)}
-            cand = np.full((n_q, width), -1, dtype=np.int32)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    cand[q, j] = slot.get(d, -1)
-            lex, dense, _ = lexical_score(q_lw.terms, q_lw.weights, q_start, q_lw.nnz, d_lw.terms, d_lw.weights, d_lw.starts, d_lw.nnz,
-                                          cand=cand, q_dense=q_dense.to(torch.bfloat16), d_dense=d_dense.to(torch.bfloat16),
-                                          hybrid_weights=hw)
-            mv = maxsim_wide(q_tv.vectors, np.asarray(q_tv.starts).astype(np.int32), q_tv.lens, d_tv.vectors, d_tv.starts, d_tv.lens,
-                             cand=cand, mean=True)
-            s = self._mix(lex, dense, mv)
-            for q, ds in enumerate(per_q):
-                for j, d in enumerate(ds):
-                    if stored[d] < 0:
-                        out[(q, d)] = float(s[q, j])
-        st = self.stats
-        st["queries"] += n_q
-        st["stored"] += len(docs) - len(fresh)
-        st["encoded"] += len(fresh)
-        return [out[p] for p in pairs]
+    _HW = (1.0, 1.0)          # (tt_lexical_score's own mix is not read: its lex and dense outputs are)
 
-    def predict(self, pairs: Sequence[Sequence[str]]) -> List[float]:
-        """[(query, passage), ...] -> combined scores; every passage is encoded in the call."""
-        pairs = list(pairs)
-        if not pairs:
-            return []
-        q_no: Dict[str, int] = {}
-        d_no: Dict[str, int] = {}
-        idx = [(q_no.setdefault(q, len(q_no)), d_no.setdefault(d, len(d_no))) for q, d in pairs]
-        return self._score(list(q_no), list(d_no), idx)
+    def score_stored(self, q, cands) -> np.ndarray:
+        q_dense, q_lw, q_tv = q
+        lex, dense, _ = self.store.score(q_lw, cands[0], dense=q_dense, hybrid_weights=self._HW)
+        return self._mix(lex, dense, self.vectors.score(q_tv, cands[1], mean=True))
 
-    def postprocess_nodes(self, nodes, query_bundle=None, query_str: Optional[str] = None):
-        from .schema import MetadataMode
-
-        if query_bundle is None and query_str is None:
-            raise ValueError("Missing query bundle in extra info.")
-        q = query_str if query_bundle is None else query_bundle.query_str
-        if len(nodes) == 0:
-            return []
-        ids = [n.node.id_ for n in nodes]
-        stored, stored_mv = self.store.lookup(ids), self.vectors.lookup(ids)
-        stored = np.where(stored_mv >= 0, stored, -1).astype(np.int32)       # (a node is stored when both stores hold it)
-        docs = [None if s >= 0 else n.node.get_content(metadata_mode=MetadataMode.EMBED) for n, s in zip(nodes, stored)]
-        scores = self._score([q], docs, [(0, d) for d in range(len(nodes))], stored, stored_mv)
-        for n, s in zip(nodes, scores):
-            if self.keep_retrieval_score:
-                n.node.metadata["retrieval_score"] = n.score
-            n.score = float(s)
-        return sorted(nodes, key=lambda x: -x.score)[: self.top_n]
-
-    _postprocess_nodes = postprocess_nodes
-
-    def rerank(self, query: str, documents: Sequence[str], top_n: Optional[int] = None):
-        scores = self.predict([(query, d) for d in documents])
-        order = sorted(range(len(documents)), key=lambda i: -scores[i])
-        if top_n is not None:
-            order = order[:top_n]
-        return [{"index": i, "relevance_score": float(scores[i])} for i in order]
+    def score_fresh(self, q, d, cand) -> np.ndarray:
+        (q_dense, q_lw, q_tv), (d_dense, d_lw, d_tv) = q, d
+        _check_range("d_nnz", d_lw.nnz, 0, MAX_DOC_NNZ)
+        lex, dense, _ = lexical_score(q_lw.terms, q_lw.weights, LexicalStore._check_query(q_lw), q_lw.nnz, d_lw.terms, d_lw.weights,
+                                      d_lw.starts, d_lw.nnz, cand=cand, q_dense=q_dense.to(torch.bfloat16),
+                                      d_dense=d_dense.to(torch.bfloat16), hybrid_weights=self._HW)
+        mv = maxsim_wide(q_tv.vectors, np.asarray(q_tv.starts).astype(np.int32), q_tv.lens, d_tv.vectors, d_tv.starts, d_tv.lens,
+                         cand=cand, mean=True)
+        return self._mix(lex, dense, mv)

@@ -175,10 +175,9 @@ def postings_build(d_terms, d_weights, d_start, d_nnz, n_sealed: int, vocab: int
     import torch
 
     from . import _lib
+    from ._hostargs import _need_device, _stream
 
-    dev = d_terms.device
-    if dev.type != "cuda":
-        raise RuntimeError("postings_build: device tensors are needed; tensor_truth_amd has no CPU path")
+    dev = _need_device("postings_build", d_terms)
     if not 1 <= int(vocab):
         raise ValueError(f"postings_build: vocab={vocab}")
     lib = _lib.load_library()
@@ -194,7 +193,7 @@ def postings_build(d_terms, d_weights, d_start, d_nnz, n_sealed: int, vocab: int
     with torch.cuda.device(dev):
         rc = lib.tt_postings_build(d_terms.data_ptr(), d_weights.data_ptr(), d_start.data_ptr(), d_nnz.data_ptr(), int(n_sealed),
                                    int(vocab), post_off.data_ptr(), post_doc.data_ptr(), int(post_cap), term_ub.data_ptr(),
-                                   flags.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+                                   flags.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
     _lib.check(rc, "tt_postings_build")
     return PostingsIndex(vocab, n_sealed, post_off, post_doc, term_ub, int(flags.item()))
 
@@ -208,7 +207,8 @@ def lexical_topk_postings(q_terms, q_weights, q_start, q_nnz, d_terms, d_weights
     import torch
 
     from . import _lib
-    from .lexical import MAX_QUERY_NNZ, MAX_SCAN_K, MAX_SCAN_QUERIES, _check_entries, _dev_i
+    from ._hostargs import _dev_i, _need_device, _stream
+    from .lexical import MAX_QUERY_NNZ, MAX_SCAN_K, MAX_SCAN_QUERIES, _check_entries
 
     n_q, n_docs = len(q_nnz), len(d_nnz)
     if not 1 <= n_q <= MAX_SCAN_QUERIES:
@@ -222,9 +222,7 @@ def lexical_topk_postings(q_terms, q_weights, q_start, q_nnz, d_terms, d_weights
     lo, hi, start, longest = ranges
     if len(start) != n_q + 1 or len(lo) != int(start[-1]) or len(hi) != len(lo):
         raise ValueError("lexical_topk_postings: range_start [n_q + 1] and one (lo, hi) per range are needed")
-    dev = d_terms.device
-    if dev.type != "cuda":
-        raise RuntimeError("lexical_topk_postings: device tensors are needed; tensor_truth_amd has no CPU path")
+    dev = _need_device("lexical_topk_postings", d_terms)
     qs, qn = _dev_i(q_start, torch.int32, dev), _dev_i(q_nnz, torch.int32, dev)
     lo_t = torch.from_numpy(np.ascontiguousarray(np.append(lo, 0), dtype=np.int64)).to(dev)      # (never empty: a valid pointer)
     hi_t = torch.from_numpy(np.ascontiguousarray(np.append(hi, 0), dtype=np.int64)).to(dev)
@@ -244,7 +242,7 @@ def lexical_topk_postings(q_terms, q_weights, q_start, q_nnz, d_terms, d_weights
                                           index.post_doc.data_ptr(), index.n_entries, index.n_sealed, lo_t.data_ptr(),
                                           hi_t.data_ptr(), st_t.data_ptr(), int(longest), int(k), scores.data_ptr(), idx.data_ptr(),
                                           thr.data_ptr(), cnt.data_ptr(), cand_cnt.data_ptr(), workspace.data_ptr(),
-                                          workspace.numel() * workspace.element_size(), torch.cuda.current_stream(dev).cuda_stream)
+                                          workspace.numel() * workspace.element_size(), _stream(dev))
     _lib.check(rc, "tt_lexical_topk_postings")
     return scores, idx, thr, cnt, cand_cnt, workspace
 

@@ -29,6 +29,8 @@ logger = logging.getLogger(__name__)
 from . import weights as _weights
 from .coalesce import Coalescer
 from . import precision as _precision
+from ._hostargs import resolve_device
+from ._stored import rerank_result
 from .encoder import pack_tokens
 from .schema import MetadataMode, NodeWithScore
 from .tokenization import load_tokenizer
@@ -39,11 +41,7 @@ class HipSentenceTransformerRerank:
                  keep_retrieval_score: bool = False, model_kwargs: Optional[Dict[str, Any]] = None,
                  max_length: int = 512, batch_pairs: int = 1024, coalesce: bool = True, max_coalesced_calls: int = 64,
                  coalesce_wait_s: float = 0.0, **_ignored):
-        dev = torch.device("cuda" if device in (None, "cuda") else device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"device '{device}': tensor_truth_amd runs on HIP devices only (no CPU path)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = resolve_device(device)
         self.model_name = model
         self.top_n = top_n
         self.device = dev
@@ -294,11 +292,7 @@ class HipSentenceTransformerRerank:
 
     # ---- core/ranking.py Reranker protocol (reference: core/ranking.py:16-32) ---------------------------
     def rerank(self, query: str, documents: Sequence[str], top_n: Optional[int] = None):
-        scores = self.predict([(query, d) for d in documents])
-        order = sorted(range(len(documents)), key=lambda i: -scores[i])
-        if top_n is not None:
-            order = order[:top_n]
-        return [{"index": i, "relevance_score": float(scores[i])} for i in order]
+        return rerank_result(self.predict([(query, d) for d in documents]), top_n)
 
 
 class RerankerWithTokenSource:

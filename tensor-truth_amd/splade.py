@@ -18,6 +18,7 @@ and cannot be checked offline.  The loader is therefore strict: a tensor, a modu
 """
 from __future__ import annotations
 
+import functools
 import json
 import os
 import re
@@ -27,10 +28,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._hostargs import _dev_i, _need_device, _stream, _suffix, read_json, resolve_device
+from ._hostargs import resolve_dtype as _resolve_dtype
+from ._stored import top_nodes
 from .colbert import bert_state_names
 from .encoder import Encoder, EncoderConfig, EncoderWeights, pack_tokens
-from .lexical import MAX_DOC_NNZ, MAX_QUERY_NNZ, MAX_SCAN_K, LexicalStore, LexicalWeights, _check_range, _dev_i, _need_device, _stream, \
-    lexical_score
+from .lexical import MAX_DOC_NNZ, MAX_QUERY_NNZ, MAX_SCAN_K, LexicalStore, LexicalWeights
 
 # the kernels' limits (include/tt_hip.h)
 MAX_HIDDEN, MAX_VOCAB, MAX_SEQ_LEN, MAX_SEQS, MAX_TERMS = 1024, 65536, 8192, 65535, 8192
@@ -45,14 +48,6 @@ _POOLING_READ = frozenset(("pooling_strategy", "activation_function", "word_embe
 _POOLING_UNUSED = frozenset(("chunk_size",))          # how upstream slices its own max over a long batch: no effect on a value
 _ST_CONFIG_UNUSED = frozenset(("__version__", "prompts", "default_prompt_name", "model_type"))
 _SBERT_READ = frozenset(("max_seq_length", "do_lower_case"))
-
-
-def _read_json(path: str) -> dict:
-    with open(path, encoding="utf-8") as f:
-        d = json.load(f)
-    if not isinstance(d, dict):
-        raise ValueError(f"{path}: a JSON object is expected")
-    return d
 
 
 # ---- checkpoint --------------------------------------------------------------------------------------------------------------------
@@ -70,26 +65,13 @@ def detect_layout(model_dir: Optional[str]) -> Optional[str]:
             return None
         return "sparse_encoder" if "SpladePooling" in kinds else None
     try:
-        archs = _read_json(os.path.join(model_dir, "config.json")).get("architectures") or []
+        archs = read_json(os.path.join(model_dir, "config.json")).get("architectures") or []
     except (OSError, ValueError):
         return None
     return "hf" if any(str(a).endswith("ForMaskedLM") for a in archs) else None
 
 
-def resolve_dtype(model_kwargs: Optional[dict]) -> torch.dtype:
-    mk = model_kwargs or {}
-    td = mk.get("torch_dtype")
-    name = str(td).replace("torch.", "") if td is not None else None
-    if name is None and mk.get("precision") is not None:
-        name = {"bf16": "bfloat16", "fp16": "float16"}.get(str(mk["precision"]).lower(), str(mk["precision"]))
-        if name not in ("bfloat16", "float16"):
-            raise NotImplementedError(f"precision={mk['precision']!r} is not available for SPLADE checkpoints: torch_dtype bfloat16 "
-                                      "(the default) or float16")
-    if name is None or name in ("bfloat16", "bf16"):
-        return torch.bfloat16
-    if name in ("float16", "fp16", "half"):
-        return torch.float16
-    raise NotImplementedError(f"torch_dtype={td!r} is not available for SPLADE checkpoints: bfloat16 (the default) or float16")
+resolve_dtype = functools.partial(_resolve_dtype, family="SPLADE")
 
 
 def check_pooling(model_dir: str) -> Tuple[Optional[int], Optional[int]]:
@@ -105,7 +87,7 @@ def check_pooling(model_dir: str) -> Tuple[Optional[int], Optional[int]]:
     if mods[0].get("path", "") not in ("", "."):
         raise NotImplementedError(f"modules.json: MLMTransformer module at path {mods[0].get('path')!r} (expected the directory itself)")
     where = os.path.join(str(mods[1].get("path", "1_SpladePooling")), "config.json")
-    pc = _read_json(os.path.join(model_dir, where))
+    pc = read_json(os.path.join(model_dir, where))
     unknown = sorted(set(pc) - _POOLING_READ - _POOLING_UNUSED)
     if unknown:
         raise NotImplementedError(f"{where} carries fields the SPLADE path does not know: {unknown[:6]}")
@@ -120,7 +102,7 @@ def check_pooling(model_dir: str) -> Tuple[Optional[int], Optional[int]]:
                                   "computed ('log1p_relu', log1p(log1p(relu(x))), is a different function)")
     p = os.path.join(model_dir, "config_sentence_transformers.json")
     if os.path.exists(p):
-        sc = _read_json(p)
+        sc = read_json(p)
         unknown = sorted(set(sc) - _ST_CONFIG_UNUSED - {"similarity_fn_name"})
         if unknown:
             raise NotImplementedError(f"config_sentence_transformers.json carries fields the SPLADE path does not know: {unknown[:6]}")
@@ -130,7 +112,7 @@ def check_pooling(model_dir: str) -> Tuple[Optional[int], Optional[int]]:
     max_seq = None
     p = os.path.join(model_dir, "sentence_bert_config.json")
     if os.path.exists(p):
-        sb = _read_json(p)
+        sb = read_json(p)
         unknown = sorted(set(sb) - _SBERT_READ)
         if unknown:
             raise NotImplementedError(f"sentence_bert_config.json carries fields the SPLADE path does not know: {unknown[:6]}")
@@ -195,7 +177,7 @@ def load_checkpoint(model_dir: str, model_kwargs: Optional[dict] = None):
     layout = detect_layout(model_dir)
     if layout is None and os.path.exists(os.path.join(model_dir or "", "modules.json")):
         check_pooling(model_dir)          # (names the module list it refuses)
-    hf = _read_json(os.path.join(model_dir, "config.json"))
+    hf = read_json(os.path.join(model_dir, "config.json"))
     mt = hf.get("model_type")
     if mt == "distilbert":
         raise NotImplementedError("config.json model_type='distilbert': DistilBERT SPLADE variants (vocab_transform / vocab_projector) "
@@ -223,14 +205,6 @@ def load_checkpoint(model_dir: str, model_kwargs: Optional[dict] = None):
 
 
 # ---- host wrappers of the kernels ------------------------------------------------------------------------------------------------
-def _suffix(dtype: torch.dtype) -> str:
-    if dtype == torch.bfloat16:
-        return ""
-    if dtype == torch.float16:
-        return "_f16"
-    raise ValueError(f"16-bit operands are bfloat16 or float16, not {dtype}")
-
-
 def splade_pool(t: torch.Tensor, E: torch.Tensor, bias: torch.Tensor, seq_start, seq_len, max_len: Optional[int] = None,
                 activation: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``tt_splade_pool[_f16]``, picked by ``t.dtype`` -> fp32 [n_seq][Vp] on the device (``out``: a tensor [n_seq][>= Vp] to write
@@ -427,80 +401,19 @@ class SpladeEncoder:
 
 # ---- the store ----------------------------------------------------------------------------------------------------------------------
 class SpladeStore(LexicalStore):
-    """Sparse vectors of indexed passages, in HBM on one device: ``LexicalStore``'s CSR arrays (``d_start`` int64, ``d_nnz`` int32
-    per document; ``terms`` int32 and ``weights`` fp32 per kept id: 8 bytes) WITHOUT dense rows.  ``add`` appends and grows by
-    doubling; ``remove`` writes ``d_nnz = -1`` (a tombstone: neither ``score`` nor ``search`` returns the document; its entries
-    are not reclaimed).  ``search`` is ``LexicalStore.search``: the exact top-k over every stored passage -- through posting lists
-    with ``postings=True`` and ``vocab_size``, as ``LexicalStore`` describes.  No persistence."""
+    """Sparse vectors of indexed passages, in HBM on one device: a ``LexicalStore`` WITHOUT dense rows (``d_start`` int64, ``d_nnz``
+    int32 per document; ``terms`` int32 and ``weights`` fp32 per kept id: 8 bytes).  ``add(node_ids, lexical)``, ``remove``, the
+    tombstones, ``search`` and the posting lists (``postings=True`` with ``vocab_size``) are ``LexicalStore``'s; ``score`` returns
+    the lexical scores alone.  No persistence."""
 
     def __init__(self, device: torch.device, capacity_terms: int = 1 << 16, capacity_docs: int = 1 << 10, postings: bool = False,
                  vocab_size: Optional[int] = None):
-        if device.type != "cuda":
-            raise RuntimeError("SpladeStore lives on a HIP device; tensor_truth_amd has no CPU path")
-        self.dim, self.device = 0, device
-        self.terms = torch.zeros(max(capacity_terms, 1), dtype=torch.int32, device=device)
-        self.weights = torch.zeros(max(capacity_terms, 1), dtype=torch.float32, device=device)
-        self.d_start = torch.zeros(max(capacity_docs, 1), dtype=torch.int64, device=device)
-        self.d_nnz = torch.zeros(max(capacity_docs, 1), dtype=torch.int32, device=device)
-        self.dense = None
-        self.n_terms = 0
-        self.n_docs = 0
-        self._doc_of: Dict[Any, int] = {}
-        self._id_of: List[Any] = []
-        self._ws: Optional[torch.Tensor] = None
-        self._init_postings(postings, vocab_size)
-
-    def add(self, node_ids: Sequence[Any], lexical: LexicalWeights) -> np.ndarray:   # noqa: D102 (no dense rows here)
-        """Append the passages' sparse vectors -> their document numbers."""
-        nnz = np.ascontiguousarray(lexical.nnz, dtype=np.int32)
-        n = len(nnz)
-        if len(node_ids) != n:
-            raise ValueError(f"add: {len(node_ids)} node ids and {n} sparse vectors")
-        _check_range("nnz", nnz, 0, MAX_DOC_NNZ)
-        total = int(nnz.sum())
-        if lexical.terms.numel() != total or lexical.weights.numel() != total:
-            raise ValueError(f"add: {lexical.terms.numel()} terms for {total} entries")
-        want = np.zeros(n, dtype=np.int64)
-        np.cumsum(nnz[:-1], out=want[1:])
-        if n and not np.array_equal(np.asarray(lexical.starts, dtype=np.int64), want):
-            raise ValueError("add: packed sparse vectors are needed (text i right behind text i-1)")
-        if n == 0:
-            return np.zeros(0, dtype=np.int32)
-        self._check_vocab(lexical)
-        self.terms = self._grown(self.terms, self.n_terms, self.n_terms + total)
-        self.weights = self._grown(self.weights, self.n_terms, self.n_terms + total)
-        self.d_start = self._grown(self.d_start, self.n_docs, self.n_docs + n)
-        self.d_nnz = self._grown(self.d_nnz, self.n_docs, self.n_docs + n)
-        self.terms[self.n_terms:self.n_terms + total].copy_(lexical.terms.to(self.device))
-        self.weights[self.n_terms:self.n_terms + total].copy_(lexical.weights.to(self.device))
-        self.d_start[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(want + self.n_terms))
-        self.d_nnz[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(nnz))
-        docs = np.arange(self.n_docs, self.n_docs + n, dtype=np.int32)
-        for nid, d in zip(node_ids, docs):
-            old = self._doc_of.get(nid)
-            if old is not None:              # re-added: the older copy becomes a tombstone
-                self._bury(old)
-            self._doc_of[nid] = int(d)
-            self._id_of.append(nid)
-        self.n_terms += total
-        self.n_docs += n
-        self._after_add()
-        return docs
-
-    @property
-    def nbytes(self) -> int:
-        """Bytes the store holds in HBM (capacity, not fill)."""
-        return sum(t.numel() * t.element_size() for t in (self.terms, self.weights, self.d_start, self.d_nnz)) \
-            + (0 if self.index is None else self.index.nbytes)
+        super().__init__(0, device, capacity_terms, capacity_docs, postings, vocab_size)
 
     def score(self, lexical: LexicalWeights, cand) -> torch.Tensor:   # noqa: D102 (no dense part here)
         """Every query against its row of ``cand`` (document numbers, -1 = none) -> fp32 [n_q][n_cand] on the device.  A removed
         document scores -inf."""
-        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(len(lexical), -1)
-        if cand.size and cand.max() >= self.n_docs:
-            raise ValueError(f"document number {int(cand.max())} with {self.n_docs} documents stored")
-        return lexical_score(lexical.terms, lexical.weights, self._check_query(lexical), lexical.nnz, self.terms, self.weights,
-                             self.d_start[: self.n_docs], self.d_nnz[: self.n_docs], cand=cand)[0]
+        return super().score(lexical, cand)[0]
 
 
 # ---- retriever ----------------------------------------------------------------------------------------------------------------------
@@ -523,11 +436,7 @@ class HipSpladeRetriever:
             raise ValueError(f"similarity_top_k={similarity_top_k} (1 .. {MAX_SCAN_K})")
         mk = dict(model_kwargs or {})
         dtype = resolve_dtype(mk)
-        dev = torch.device("cuda" if device in (None, "cuda") else device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"device '{device}': tensor_truth_amd runs on HIP devices only (no CPU path)")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = resolve_device(device)
         self.model_name, self.similarity_top_k, self.device = model, int(similarity_top_k), dev
         max_seq = None
         if "state_dict" in mk or ("synthetic_seed" in mk and _weights.find_model_dir(model, mk) is None):
@@ -586,18 +495,9 @@ class HipSpladeRetriever:
         if self.store.n_docs == 0:
             return []
         lw = self.encoder.encode([query_bundle.query_str], is_query=True, max_terms=self.query_max_terms)
-        if self.store.postings and self.store.index is None:
-            self.store.seal()
-        scores, idx = self.store.search(lw, self.similarity_top_k)
+        hits = top_nodes(self.store, lw, self.similarity_top_k, self.nodes, node_type)
         self.stats["queries"] += 1
-        out = []
-        for s, d in zip(scores[0].cpu().tolist(), idx[0].cpu().tolist()):
-            if d < 0 or not s > 0:
-                continue
-            node = self.nodes.get(self.store.node_id(d))
-            if node is not None:
-                out.append(node_type(node=node, score=float(s)))
-        return out
+        return hits
 
 
 def synthetic_state(cfg: EncoderConfig, seed: int = 0) -> Dict[str, torch.Tensor]:

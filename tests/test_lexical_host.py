@@ -262,3 +262,42 @@ def test_length_arrays_are_refused_on_the_host():
         lexical.LexicalStore(128, torch.device("cpu"))
     with pytest.raises(ValueError, match="dim=96"):
         lexical.LexicalStore(96, torch.device("cpu"))
+
+
+def test_the_store_takes_dense_rows_exactly_when_it_has_them():
+    """What ``LexicalStore`` (and ``SpladeStore``, the same store without dense rows) refuses before a device is touched."""
+    from tensor_truth_amd import lexical
+    from tensor_truth_amd.splade import SpladeStore
+
+    cpu = torch.device("cpu")
+    for make in (lambda **kw: lexical.LexicalStore(128, cpu, **kw), lambda **kw: lexical.LexicalStore(0, cpu, **kw),
+                 lambda **kw: SpladeStore(cpu, **kw)):
+        with pytest.raises(ValueError, match="postings=True needs vocab_size"):
+            make(postings=True)
+        with pytest.raises(ValueError, match="vocab_size"):
+            make(postings=True, vocab_size=0)
+        with pytest.raises(RuntimeError, match="lives on a HIP device"):
+            make(postings=True, vocab_size=VOCAB)
+    assert SpladeStore.add is lexical.LexicalStore.add and "nbytes" not in vars(SpladeStore)
+
+    def store(cls, dim):          # (no device: ``add`` refuses before it reads an array of the store)
+        st = object.__new__(cls)
+        st.dim = dim
+        return st
+
+    lw = lexical.LexicalWeights(torch.zeros(1, dtype=torch.int32), torch.ones(1), np.array([0, 1]), np.array([1, 0], dtype=np.int32))
+    ids = ["a", "b"]
+    for st in (store(SpladeStore, 0), store(lexical.LexicalStore, 0)):
+        with pytest.raises(ValueError, match="dense rows are not taken"):
+            st.add(ids, lw, torch.zeros(2, 128))
+        with pytest.raises(ValueError, match="3 node ids, 2 lexical vectors"):
+            st.add(ids + ["c"], lw)
+    st = store(lexical.LexicalStore, 128)
+    with pytest.raises(ValueError, match="dense rows are needed"):
+        st.add(ids, lw)
+    with pytest.raises(ValueError, match=r"dense \(2, 256\) do not match \[n\]\[128\]"):
+        st.add(ids, lw, torch.zeros(2, 256))
+    with pytest.raises(ValueError, match=r"nnz\[0\]=8193"):
+        st.add(ids, lexical.LexicalWeights(lw.terms, lw.weights, lw.starts, np.array([8193, 0])), torch.zeros(2, 128))
+    with pytest.raises(ValueError, match="packed lexical vectors"):
+        st.add(ids, lexical.LexicalWeights(lw.terms, lw.weights, np.array([0, 0]), lw.nnz), torch.zeros(2, 128))

@@ -361,6 +361,46 @@ def test_store_with_postings_equals_the_store_without(dev, built_lib, kind):
     assert on.stats["fallbacks"] == 2 and on.stats["candidates"] == 0 and on.stats["passes"] == 1, on.stats
 
 
+def test_a_store_without_dense_rows_is_the_same_store(dev, built_lib):
+    """``LexicalStore`` with ``dim`` 0, ``SpladeStore`` and ``LexicalStore`` with dense rows hold the same CSR arrays and give the
+    same lexical scores; only the dense array, what ``add`` takes and ``nbytes`` differ.  Capacity 1, documents of 1 and 0
+    entries: every array grows."""
+    from tensor_truth_amd.lexical import LexicalStore
+    from tensor_truth_amd.splade import SpladeStore
+
+    docs = [{11: 2.0}, {}, {11: 0.5, 12: 1.0}]
+    q = _lw(dev, [{11: 1.0, 12: 3.0}])
+    cand = np.arange(3, dtype=np.int32)[None]
+    plain, bare, dense = SpladeStore(dev, 1, 1), LexicalStore(0, dev, 1, 1), LexicalStore(128, dev, 1, 1)
+    for st in (plain, bare):
+        assert st.dense is None and st.dim == 0 and st.nbytes == 8 + 12
+        with pytest.raises(ValueError, match="dense rows are not taken"):
+            st.add(["a"], _lw(dev, docs[:1]), torch.zeros(1, 128))
+        assert st.add(["a", "b"], _lw(dev, docs[:2])).tolist() == [0, 1] and st.add(["c"], _lw(dev, docs[2:])).tolist() == [2]
+        assert st.nbytes == 8 * 4 + 12 * 4, "capacity doubles: 4 entries, 4 documents, no dense rows"
+    assert dense.nbytes == 8 + 12 + 256
+    with pytest.raises(ValueError, match="dense rows are needed"):
+        dense.add(["a"], _lw(dev, docs[:1]))
+    dense.add(["a", "b"], _lw(dev, docs[:2]), torch.ones(2, 128))
+    dense.add(["c"], _lw(dev, docs[2:]), torch.ones(1, 128))
+    assert dense.nbytes == 8 * 4 + (12 + 256) * 4
+    want = [[2.0, 0.0, 3.5]]
+    assert plain.score(q, cand).cpu().tolist() == want
+    for st in (bare, dense):
+        lex, none_d, none_h = st.score(q, cand)
+        assert lex.cpu().tolist() == want and none_d is None and none_h is None
+        assert all(torch.equal(getattr(st, a)[:n], getattr(plain, a)[:n]) for a, n in (("terms", 3), ("weights", 3), ("d_start", 3), ("d_nnz", 3)))
+    lex, dn, hy = dense.score(q, cand, dense=torch.ones(1, 128), hybrid_weights=(1.0, 1.0))
+    assert lex.cpu().tolist() == want and dn.cpu().tolist() == [[128.0] * 3] and hy.cpu().tolist() == [[65.0, 64.0, 65.75]]
+    # tombstones: a re-added id buries its older copy, remove writes d_nnz = -1
+    for st in (plain, bare, dense):
+        st.add(["a"], _lw(dev, docs[2:]), *([torch.ones(1, 128)] if st.dim else []))
+        assert st.remove("b") and not st.remove("b") and len(st) == 2
+        assert st.d_nnz[:4].cpu().tolist() == [-1, -1, 2, 2] and st.lookup(["a", "b", "c"]).tolist() == [3, -1, 2]
+        assert [st.node_id(d) for d in range(5)] == [None, None, "c", "a", None]
+        assert st.search(q, 4)[1].cpu().tolist() == [[2, 3, -1, -1]]
+
+
 def test_add_reseals_once_the_tail_outgrows_the_lists(dev, built_lib):
     from tensor_truth_amd.splade import SpladeStore
 
