@@ -52,6 +52,21 @@ template <int N>
 __device__ __forceinline__ void lds_wait2n(u32x4& a, u32x4& b) {
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
 }
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void lds_write64_async(uint32_t addr, uint2 v) {
+    const u32x2 d = u32x2{v.x, v.y};
+    asm volatile("ds_write_b64 %0, %1" :: "v"(addr), "v"(d) : "memory");
+}
+
+// IO: how the kernel's two ends touch global memory.
+//   kIoLineStores   the context block of a wave (32 rows x DH) is transposed through the wave's slice of the dead K / V buffers and
+//                   leaves in whole rows: DH = 64: four global_store_dwordx4 per wave, each eight full 128-byte lines (eight lanes
+//                   per row); DH = 32: two, each sixteen 64-byte rows.  0: a lane writes its own row in 8-byte pieces -- kept for
+//                   the f16c planes and for outputs that are not 16-byte aligned (tt_attention_launch).
+//   kIoShapeStores, kIoShapeQ   (diagnostic library, TT_ATT_IO, wrong results by design) stand-ins that only give the stores / the Q
+//                   loads the whole-row SHAPE, with the registers as they stand: what the access shape alone is worth
+//                   (profiles/attention_io_gate.log).
+constexpr int kIoLineStores = 1, kIoShapeStores = 4, kIoShapeQ = 8;
 
 // ABL (diagnostic builds, TT_ATT_ABLATE, wrong results by design -- what each part of the key-tile loop costs): 1 = no
 // exponentials (the scaled difference goes on as the "probability"), 2 = no softmax at all (no mask, maximum, FMAs,
@@ -60,7 +75,7 @@ __device__ __forceinline__ void lds_wait2n(u32x4& a, u32x4& b) {
 // NW (round 4): waves = 32-row query blocks per workgroup.  4 is the shape of rounds 1-3; 8 (256 rows) is taken where a sequence's
 // last workgroup stays mostly full (tt_attention_launch: the measured rule); 5 exists as an experiment (uneven piece map).  A
 // row's arithmetic does not depend on NW.
-template <int DH, bool STAMP = false, int ABL = 0, int NW = kWaves>
+template <int DH, bool STAMP = false, int ABL = 0, int NW = kWaves, int IO = kIoLineStores>
 __global__ __launch_bounds__(64 * NW, 4) void attention_kernel(AttnParams p) {
     constexpr int RB = DH * 2;              // bytes per K row
     constexpr int CH = RB / 16;             // 16-B chunks per K row
@@ -133,8 +148,18 @@ __global__ __launch_bounds__(64 * NW, 4) void attention_kernel(AttnParams p) {
     const int q_row_c = q_row < len ? q_row : len - 1;     // clamp: result discarded
     const uint16_t* qp = p.qk + (size_t)(t0 + q_row_c) * p.ld_qk + p.q_col0 + head * DH + hh * 8;
     ex8 qf[KS];
+    if constexpr ((IO & kIoShapeQ) != 0) {
+        // stand-in: the block's 32 rows in KS loads of whole rows (CH lanes per row), used as the fragments as they land
 #pragma unroll
-    for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const ex8*>(qp + s * 16);
+        for (int s = 0; s < KS; ++s) {
+            const int r = (qt * NW + wslot) * 32 + s * (64 / CH) + lane / CH;
+            const int rc = r < len ? r : len - 1;
+            qf[s] = *reinterpret_cast<const ex8*>(p.qk + (size_t)(t0 + rc) * p.ld_qk + p.q_col0 + head * DH + (lane % CH) * 8);
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const ex8*>(qp + s * 16);
+    }
 
     const int n_kt = (alen + kKTile - 1) / kKTile;
     const int n_g8 = (alen + 7) >> 3;
@@ -440,16 +465,81 @@ __global__ __launch_bounds__(64 * NW, 4) void attention_kernel(AttnParams p) {
             }
             return;
         }
-        uint16_t* op = p.out + (size_t)(t0 + q_row) * p.ld_out + head * DH;
+        if constexpr ((IO & (kIoLineStores | kIoShapeStores)) == 0) {
+            uint16_t* op = p.out + (size_t)(t0 + q_row) * p.ld_out + head * DH;
 #pragma unroll
-        for (int d = 0; d < DT; ++d)
+            for (int d = 0; d < DT; ++d)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                uint2 o;
-                o.x = pack_e2(acc_o[d][4 * g + 0] * inv, acc_o[d][4 * g + 1] * inv);
-                o.y = pack_e2(acc_o[d][4 * g + 2] * inv, acc_o[d][4 * g + 3] * inv);
-                *reinterpret_cast<uint2*>(op + 32 * d + 8 * g + 4 * hh) = o;
+                for (int g = 0; g < 4; ++g) {
+                    uint2 o;
+                    o.x = pack_e2(acc_o[d][4 * g + 0] * inv, acc_o[d][4 * g + 1] * inv);
+                    o.y = pack_e2(acc_o[d][4 * g + 2] * inv, acc_o[d][4 * g + 3] * inv);
+                    *reinterpret_cast<uint2*>(op + 32 * d + 8 * g + 4 * hh) = o;
+                }
+        }
+    }
+    if constexpr ((IO & (kIoLineStores | kIoShapeStores)) != 0) {
+        // ---- whole rows: the wave's block as [32 rows][RB bytes] through LDS, read back CH lanes per row ----------------------
+        // (p.out_scales is a kernel argument: every wave of the workgroup takes the same side of this branch)
+        if (p.out_scales) return;
+        constexpr int RPI = 64 / CH;            // rows per store instruction: 8 whole 128-byte lines (DH 64), 16 rows of 64 B (DH 32)
+        constexpr int NI = 32 / RPI;            // store instructions per wave: 4 / 2
+        constexpr int RPL = 128 / RB;           // rows per 128 bytes of the slice
+        u32x4 t[NI];
+        if constexpr ((IO & kIoShapeStores) != 0) {
+            // stand-in: the pieces this lane holds, two per instruction, to where the transposed ones would go
+            uint2 o[DT * 4];
+#pragma unroll
+            for (int d = 0; d < DT; ++d)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    o[4 * d + g].x = pack_e2(acc_o[d][4 * g + 0] * inv, acc_o[d][4 * g + 1] * inv);
+                    o[4 * d + g].y = pack_e2(acc_o[d][4 * g + 2] * inv, acc_o[d][4 * g + 3] * inv);
+                }
+#pragma unroll
+            for (int i = 0; i < NI; ++i) t[i] = u32x4{o[2 * i].x, o[2 * i].y, o[2 * i + 1].x, o[2 * i + 1].y};
+            if (!wave_active) return;
+        } else {
+            // The K / V buffers are dead once every wave has left the key loop (its last tile's fragments are read, and no copy is in
+            // flight: tile n_kt - 1 was waited for at the top of the last iteration).  Idle waves pass the barrier too.
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (!wave_active) return;
+            // wave w's slice: 32 * RB bytes at w * 32 * RB (NW slices fit the two buffers: 8 x 4 KiB = 2 BUF at DH 64).  The 16-byte
+            // chunk c of row r sits at chunk c ^ swz(r), swz(r) = (r / RPL) & (CH - 1), as in the GEMM epilogue's staging: the
+            // 8-byte writes (16 consecutive rows per lane group) and the 16-byte reads (whole rows) both spread over the banks.
+            // (Four-wave slices would also fit the ONE buffer the last tile is not in, which needs no barrier: measured the same,
+            // 1.139 against 1.141 ms, profiles/attention_io_gate.log -- not kept.)
+            const uint32_t slice = lds0 + (uint32_t)wave * (32 * RB);
+            const uint32_t wbase = slice + ql * RB + (((ql / RPL) & (CH - 1)) << 4) + 8 * hh;
+#pragma unroll
+            for (int d = 0; d < DT; ++d)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    uint2 o;
+                    o.x = pack_e2(acc_o[d][4 * g + 0] * inv, acc_o[d][4 * g + 1] * inv);
+                    o.y = pack_e2(acc_o[d][4 * g + 2] * inv, acc_o[d][4 * g + 3] * inv);
+                    lds_write64_async(wbase ^ (uint32_t)((4 * d + g) << 4), o);      // bits 4.. of the chunk index only: row and half stay
+                }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const int r0 = lane / CH;
+            const uint32_t raddr = slice + r0 * RB + (((lane % CH) ^ ((r0 / RPL) & (CH - 1))) << 4);   // + i * RPI * RB: swz(r0 + i RPI) = swz(r0)
+            t[0] = lds_read128_async<0>(raddr);
+            t[1] = lds_read128_async<RPI * RB>(raddr);
+            if constexpr (NI == 4) {
+                t[2] = lds_read128_async<2 * RPI * RB>(raddr);
+                t[3] = lds_read128_async<3 * RPI * RB>(raddr);
+                lds_wait4n<0>(t[0], t[1], t[2], t[3]);
+            } else {
+                lds_wait2n<0>(t[0], t[1]);
             }
+        }
+        const int row0 = (qt * NW + wslot) * 32 + lane / CH;      // row inside the sequence of this lane's piece in instruction 0
+        uint16_t* op = p.out + (size_t)(t0 + row0) * p.ld_out + head * DH + (lane % CH) * 8;
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            if (row0 + i * RPI < len) *reinterpret_cast<u32x4*>(op + (size_t)(i * RPI) * p.ld_out) = t[i];
     }
 }
 
@@ -1030,6 +1120,11 @@ int tt_attention_launch(const AttnParams& p, hipStream_t st) {
         // (rows are padded to 8 per sequence; unknown total: the caller is a test or a tool with uniform lengths)
         else if (B >= 5 && (r8 == 0 || r8 >= 5) && (p.total_rows <= 0 || (long long)p.total_rows * 10 >= (long long)p.n_seq * p.max_len * 7)) nw = 8;
     }
+    // The four- and five-wave kernels step from a wave's first K piece to its next by toggling bit 6 of the lane's byte offset
+    // (kvoff0 ^ 64), which is the chunk swizzle only while the K row stride is a multiple of 128 bytes.  Any other stride (found by
+    // tests/test_attention_io_gpu.py: every sequence of more than one key tile came out wrong) takes the eight-wave kernel, one K
+    // piece per wave: the same bits.  (The package's own strides are multiples of heads x 64.)
+    if (p.head_dim == 64 && nw != 8 && p.ld_qk % 64) nw = 8;
     const int n_qt = (p.max_len + 32 * nw - 1) / (32 * nw);
     const long long pairs8 = ((long long)p.heads * p.n_seq + 7) / 8 * 8;
     if (pairs8 * n_qt > 0x7FFFFFFFLL) {
@@ -1048,6 +1143,18 @@ int tt_attention_launch(const AttnParams& p, hipStream_t st) {
     // TT_ATT_ROTATE=1: tail tiles deal their live row blocks to different waves (A/B switch, measured neutral; same bits either way)
     static const bool rotate = TT_DIAG_ENV_INT("TT_ATT_ROTATE", 0) == 1;
     q.rotate = rotate ? 1 : 0;
+    // Whole-row context stores (kIoLineStores) need 16-byte aligned rows; the f16c planes keep their own stores.  Same bits either way.
+    int io = (!p.out_scales && p.ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0) ? kIoLineStores : 0;
+#if TT_DIAG   // TT_ATT_IO (read per launch: tools/att_bench alternates it): 0 = the 8-byte stores, 1 = whole rows, 4 / 8 / 12 = the gate's stand-ins
+    {
+        const int io_env = TT_DIAG_ENV_INT("TT_ATT_IO", -1);
+        if (io_env >= 0 && io) io = io_env;
+        if ((io & (kIoShapeStores | kIoShapeQ)) && (p.head_dim != 64 || nw != kWaves)) {
+            tt_set_error("attention: the I/O stand-ins are four-wave, head_dim 64 (set TT_ATT_WAVES=4)");
+            return TT_E_UNSUPPORTED;
+        }
+    }
+#endif
     TtProfScope prof(TT_K_ATTENTION, st);
 #if TT_DIAG
     // Resident form (round 5): every sequence's aligned key frame (up to 7 rows of its predecessor in front) fits kResMaxTiles key tiles
@@ -1077,25 +1184,35 @@ int tt_attention_launch(const AttnParams& p, hipStream_t st) {
         return TT_E_UNSUPPORTED;
     }
     if (p.head_dim == 64 && p.dbg) {
-        hipLaunchKernelGGL((attention_kernel<64, true>), grid, dim3(64 * kWaves), 0, st, q);
+        hipLaunchKernelGGL((attention_kernel<64, true, 0, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
     } else if (p.head_dim == 64 && TT_DIAG_ENV_INT("TT_ATT_ABLATE", 0) != 0) {
         static const int abl = TT_DIAG_ENV_INT("TT_ATT_ABLATE", 0);
-        if (abl == 1) hipLaunchKernelGGL((attention_kernel<64, false, 1>), grid, dim3(64 * kWaves), 0, st, q);
-        else if (abl == 2) hipLaunchKernelGGL((attention_kernel<64, false, 2>), grid, dim3(64 * kWaves), 0, st, q);
-        else if (abl == 3) hipLaunchKernelGGL((attention_kernel<64, false, 3>), grid, dim3(64 * kWaves), 0, st, q);
-        else hipLaunchKernelGGL((attention_kernel<64, false, 4>), grid, dim3(64 * kWaves), 0, st, q);
+        if (abl == 1) hipLaunchKernelGGL((attention_kernel<64, false, 1, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
+        else if (abl == 2) hipLaunchKernelGGL((attention_kernel<64, false, 2, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
+        else if (abl == 3) hipLaunchKernelGGL((attention_kernel<64, false, 3, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
+        else hipLaunchKernelGGL((attention_kernel<64, false, 4, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
+    } else
+#endif
+#if TT_DIAG   // the stand-ins of the I/O gate (TT_ATT_IO = 4, 8, 12; tools/gpu_att_io_gate.sh): the shipping shape only
+    if (p.head_dim == 64 && nw == kWaves && (io & (kIoShapeStores | kIoShapeQ)) && !p.out_scales) {
+        if (io == kIoShapeStores) hipLaunchKernelGGL((attention_kernel<64, false, 0, kWaves, kIoShapeStores>), grid, dim3(64 * kWaves), 0, st, q);
+        else if (io == kIoShapeQ) hipLaunchKernelGGL((attention_kernel<64, false, 0, kWaves, kIoShapeQ>), grid, dim3(64 * kWaves), 0, st, q);
+        else hipLaunchKernelGGL((attention_kernel<64, false, 0, kWaves, kIoShapeStores | kIoShapeQ>), grid, dim3(64 * kWaves), 0, st, q);
     } else
 #endif
     if (p.head_dim == 64 && nw == 8) {
-        hipLaunchKernelGGL((attention_kernel<64, false, 0, 8>), grid, dim3(64 * 8), 0, st, q);
+        if (io) hipLaunchKernelGGL((attention_kernel<64, false, 0, 8>), grid, dim3(64 * 8), 0, st, q);
+        else hipLaunchKernelGGL((attention_kernel<64, false, 0, 8, 0>), grid, dim3(64 * 8), 0, st, q);
 #if TT_DIAG   // five waves: measured slower than the better of four and eight at every length (EXPERIMENTS.md round 4)
     } else if (p.head_dim == 64 && nw == 5) {
-        hipLaunchKernelGGL((attention_kernel<64, false, 0, 5>), grid, dim3(64 * 5), 0, st, q);
+        hipLaunchKernelGGL((attention_kernel<64, false, 0, 5, 0>), grid, dim3(64 * 5), 0, st, q);
 #endif
     } else if (p.head_dim == 64) {
-        hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(64 * kWaves), 0, st, q);
+        if (io) hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(64 * kWaves), 0, st, q);
+        else hipLaunchKernelGGL((attention_kernel<64, false, 0, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
     } else if (p.head_dim == 32) {
-        hipLaunchKernelGGL(attention_kernel<32>, grid, dim3(64 * kWaves), 0, st, q);
+        if (io) hipLaunchKernelGGL(attention_kernel<32>, grid, dim3(64 * kWaves), 0, st, q);
+        else hipLaunchKernelGGL((attention_kernel<32, false, 0, kWaves, 0>), grid, dim3(64 * kWaves), 0, st, q);
     } else {
         tt_set_error("attention: head_dim %d not in {32, 64}", p.head_dim);
         return TT_E_UNSUPPORTED;

@@ -1,9 +1,11 @@
 // Standalone timing of tt_attention_varlen on the rerank shape (800 sequences x 292 tokens, 16 heads x 64).
 //   ./att_bench [n_seq] [len] [iters]
+//   ./att_bench_diag n_seq len iters rounds io[,io...]     the diagnostic library's TT_ATT_IO variants alternated in one process
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 #include "../include/tt_hip.h"
@@ -43,6 +45,34 @@ int main(int argc, char** argv) {
     CK(hipDeviceSynchronize());
     hipStream_t st; CK(hipStreamCreate(&st));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    if (argc > 5) {
+        // ./att_bench n_seq len iters rounds io[,io...]: the TT_ATT_IO variants of the diagnostic library alternated in ONE process,
+        // `rounds` times over (the library reads the switch at every launch); one line per variant and round
+        const int rounds = atoi(argv[4]);
+        std::vector<int> ios;
+        for (char* s = strtok(argv[5], ","); s; s = strtok(nullptr, ",")) ios.push_back(atoi(s));
+        // (the process's first launches run on clocks that are still ramping: 1.29 against 1.18 ms for the same kernel -- spend them here)
+        for (int i = 0; i < 200; ++i) tt_attention_varlen(qk, 2 * H, 0, H, vt, 8 * H, out, H, ss, sl, n_seq, heads, dh, len, st);
+        CK(hipStreamSynchronize(st));
+        for (int r = 0; r < rounds; ++r)
+            for (int io : ios) {
+                char v[16];
+                snprintf(v, sizeof v, "%d", io);
+                setenv("TT_ATT_IO", v, 1);
+                for (int i = 0; i < 3; ++i) {
+                    int rc = tt_attention_varlen(qk, 2 * H, 0, H, vt, 8 * H, out, H, ss, sl, n_seq, heads, dh, len, st);
+                    if (rc) { fprintf(stderr, "rc=%d %s\n", rc, tt_last_error()); return 1; }
+                }
+                CK(hipStreamSynchronize(st));
+                CK(hipEventRecord(e0, st));
+                for (int i = 0; i < iters; ++i) tt_attention_varlen(qk, 2 * H, 0, H, vt, 8 * H, out, H, ss, sl, n_seq, heads, dh, len, st);
+                CK(hipEventRecord(e1, st));
+                CK(hipEventSynchronize(e1));
+                float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= iters;
+                printf("attention n_seq=%d len=%d round=%d TT_ATT_IO=%d: %.4f ms\n", n_seq, len, r, io, ms);
+            }
+        return 0;
+    }
     for (int i = 0; i < 3; ++i) {
         int rc = tt_attention_varlen(qk, 2 * H, 0, H, vt, 8 * H, out, H, ss, sl, n_seq, heads, dh, len, st);
         if (rc) { fprintf(stderr, "rc=%d %s\n", rc, tt_last_error()); return 1; }
