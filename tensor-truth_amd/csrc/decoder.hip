@@ -13,52 +13,14 @@
 //   a    = SiLU(gu[:, :F]) * gu[:, F:]                   [T][F]
 //   h    = GEMM(a, Wdown) + h1
 // and after the last layer  out = RMSNorm(h) * g_final.  Every row op reads one token row only, so a token's result does not
-// depend on how the batch is packed; the attention mixes the rows of one sequence only.  The attention tile, the embedding gather,
-// the gated-activation kernel, the workspace plan and the batch-argument checks are the ones ModernBERT uses too (varlen.h).
+// depend on how the batch is packed; the attention mixes the rows of one sequence only.  The schedule itself is prenorm.h's (the
+// driver ModernBERT and T5 run on too: DecFamily below says what is Qwen3's); the attention tile, the embedding gather, RMSNorm, the
+// gated-activation kernel, the workspace plan and the shape and batch-argument checks are varlen.h's.
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "varlen.h"
+#include "prenorm.h"
 
 namespace {
-
-// ---- RMSNorm over rows of H <= 1024 elements: one wave per row, four rows per block ---------------------------------------------
-__global__ __launch_bounds__(256) void dec_rmsnorm_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                          const float* __restrict__ g, int rows, int H, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const uint4* src = reinterpret_cast<const uint4*>(in + (size_t)row * H);
-    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)row * H);
-    const int nc = H / 8;   // <= 128 chunks of 8 elements: at most two per lane
-    uint4 v[2];
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int c = lane + 64 * j;
-        v[j] = c < nc ? src[c] : uint4{0u, 0u, 0u, 0u};
-        const uint32_t u[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float a = elo(u[k]), b = ehi(u[k]);
-            ss += a * a;
-            ss += b * b;
-        }
-    }
-    const float r = rsqrtf(wave_sum(ss) / (float)H + eps);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int c = lane + 64 * j;
-        if (c >= nc) continue;
-        const uint32_t u[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-        uint32_t o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int e = 8 * c + 2 * k;
-            o[k] = pack_e2(elo(u[k]) * r * g[e], ehi(u[k]) * r * g[e + 1]);
-        }
-        dst[c] = uint4{o[0], o[1], o[2], o[3]};
-    }
-}
 
 // ---- per-head RMSNorm of q and k with their weights, then rotate-half RoPE, in place; V heads copied to the V8 layout ---------
 // One block per token row, one wave per head at a time; lane i < D / 2 holds the pair (i, i + D / 2).
@@ -221,33 +183,13 @@ __global__ __launch_bounds__(256) void dec_score_kernel(const uint16_t* __restri
 }
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
-int check_heads(int heads, int kv_heads, int head_dim) {
-    if (head_dim != 64 && head_dim != 128) {
-        tt_set_error("decoder: head_dim=%d not in {64, 128}", head_dim);
-        return TT_E_UNSUPPORTED;
-    }
-    TT_CHECK_ARG(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "decoder: heads=%d is not a multiple of kv_heads=%d", heads,
-                 kv_heads);
-    return TT_OK;
-}
-
-int check_shape(int hidden, int heads, int kv_heads, int head_dim) {
-    if (int rc = check_heads(heads, kv_heads, head_dim)) return rc;
-    if (hidden <= 0 || hidden % 128 || hidden > 1024) {
-        tt_set_error("decoder: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", hidden);
-        return TT_E_UNSUPPORTED;
-    }
-    return TT_OK;
-}
+int check_heads(int heads, int kv_heads, int head_dim) { return check_gqa_heads("decoder", heads, kv_heads, head_dim, 64, 128); }
 
 int check_weights(const tt_decoder_weights* w) {
     TT_CHECK_ARG(w != nullptr, "null weights");
-    if (int rc = check_shape(w->hidden, w->heads, w->kv_heads, w->head_dim)) return rc;
-    if (((w->heads + 2 * w->kv_heads) * w->head_dim) % 128 || (w->heads * w->head_dim) % 64 || w->ffn <= 0 || w->ffn % 64) {
-        tt_set_error("decoder: (heads + 2 kv_heads) * head_dim = %d must be a multiple of 128, heads * head_dim and ffn=%d of 64",
-                     (w->heads + 2 * w->kv_heads) * w->head_dim, w->ffn);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_heads(w->heads, w->kv_heads, w->head_dim)) return rc;
+    if (int rc = check_hidden("decoder", w->hidden)) return rc;
+    if (int rc = check_qkv_width("decoder", w->heads, w->kv_heads, w->head_dim, w->ffn)) return rc;
     TT_CHECK_ARG(w->layers >= 0 && (w->layers == 0 || w->layer != nullptr), "layer array missing");
     TT_CHECK_ARG(w->embed && w->final_norm && w->vocab > 0, "embedding table / final norm missing");
     TT_CHECK_ARG(w->rms_eps > 0.f && w->rope_theta > 0.f, "rms_eps=%g rope_theta=%g", w->rms_eps, w->rope_theta);
@@ -258,14 +200,7 @@ VarlenWs dec_plan(const tt_decoder_weights* w, int n_rows) {
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn, D = (size_t)w->head_dim;
     const size_t nqkv = (size_t)(w->heads + 2 * w->kv_heads) * D;
     // zeros: the GEMMs' bias operand (the model has none)
-    return varlen_plan(n_rows, H, nqkv, w->kv_heads * D, w->heads * D, F, std::max(nqkv, std::max(2 * F, H)));
-}
-
-int rmsnorm_launch(const uint16_t* in, uint16_t* out, const float* g, int rows, int H, float eps, hipStream_t st) {
-    TtProfScope prof(TT_K_ROWOPS, st);
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, in, out, g, rows, H, eps);
-    TT_CHECK_LAUNCH();
-    return TT_OK;
+    return varlen_plan(n_rows, H, nqkv, w->kv_heads * D, w->heads * D, 2 * F, F, std::max(nqkv, std::max(2 * F, H)));
 }
 
 int qknorm_rope_launch(uint16_t* qkv, int ld, const int32_t* pos, const float* qn, const float* kn, int rows, int nq, int nkv, int D,
@@ -312,86 +247,67 @@ int attention_rows_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, c
 // rows of the compact buffers of the pooled-row tail: up to 256 sequences a multiple of 64 (the skinny GEMMs), else of 256
 int rows_pad(int n_seq) { return pooled_rows_pad(n_seq, tt_gemm_skinny_enabled()); }
 
+// what prenorm.h's driver asks of a family.  pool_row != nullptr (tt_decoder_forward_rows): the last layer's attention is the
+// pooled-row one, into compact rows of b.ctx
+struct DecFamily {
+    static constexpr QkvForm qkv = QkvForm::Packed;
+    const tt_decoder_weights* w;
+    const int32_t *ids, *pos, *pool_row;
+
+    int nqkv() const { return (w->heads + 2 * w->kv_heads) * w->head_dim; }
+    PreNormDims dims() const { return {w->hidden, w->heads * w->head_dim, nqkv(), w->ffn, w->layers}; }
+    int embed(const VarlenBufs& b, int T, hipStream_t st) const { return embed_gather_launch(ids, w->embed, w->vocab, w->hidden, b.ha, T, st); }
+    int norm(const uint16_t* in, uint16_t* out, const float* g, const float*, int rows, hipStream_t st) const {
+        return rmsnorm_launch<false>(in, out, g, rows, w->hidden, w->rms_eps, st);
+    }
+    PreNormLayer layer(int l) const {
+        const tt_decoder_layer_weights& lw = w->layer[l];
+        return {lw.attn_norm, lw.qkv_w, lw.o_w, lw.ffn_norm, lw.gate_up_w, lw.down_w};
+    }
+    int post_qkv(int l, const VarlenBufs& b, int T, hipStream_t st) const {
+        return qknorm_rope_launch(b.qkv, nqkv(), pos, w->layer[l].q_norm, w->layer[l].k_norm, T, w->heads, w->kv_heads, w->head_dim,
+                                  w->rms_eps, w->rope_theta, b.vt, 8 * w->kv_heads * w->head_dim, st);
+    }
+    int attention(int l, const VarlenBufs& b, const PackedSeqs& s, hipStream_t st) const {
+        const int D = w->head_dim, nq = w->heads, nkv = w->kv_heads;
+        if (pool_row && l == w->layers - 1) {
+            TT_CHECK_HIP(hipMemsetAsync(b.ctx, 0, (size_t)rows_pad(s.n_seq) * nq * D * 2, st));
+            return attention_rows_launch(b.qkv, nqkv(), 0, nq * D, b.vt, 8 * nkv * D, b.ctx, nq * D, s.seq_start, s.seq_len, pool_row,
+                                         s.n_seq, s.n_rows, nq, nkv, D, st);
+        }
+        return attention_launch(b.qkv, nqkv(), 0, nq * D, b.vt, 8 * nkv * D, b.ctx, nq * D, s.seq_start, s.seq_len, s.n_seq, s.n_rows, nq,
+                                nkv, D, s.max_len, st);
+    }
+    const float* final_norm() const { return w->final_norm; }
+};
+
 // The forward behind tt_decoder_forward (pool_row == nullptr: every layer over every row, out [n_rows][H]) and
 // tt_decoder_forward_rows (the last layer's attention, output projection, MLP and the final norm for the rows pool_row names only,
 // out [rows_pad(n_seq)][H]).  Arguments are checked by the callers.
-int dec_run(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
-            const int32_t* pool_row, int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const VarlenWs e = dec_plan(w, n_rows);
-    char* ws = (char*)workspace;
-    const int H = w->hidden, F = w->ffn, D = w->head_dim, nq = w->heads, nkv = w->kv_heads, T = n_rows;
-    const int nqkv = (nq + 2 * nkv) * D;
-    uint16_t* ha = (uint16_t*)(ws + e.off_ha);
-    uint16_t* hb = (uint16_t*)(ws + e.off_hb);
-    uint16_t* x = (uint16_t*)(ws + e.off_x);
-    uint16_t* qkv = (uint16_t*)(ws + e.off_qkv);
-    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
-    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
-    uint16_t* gu = (uint16_t*)(ws + e.off_gu);
-    uint16_t* act = (uint16_t*)(ws + e.off_act);
-    const float* zero = (const float*)(ws + e.off_zero);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
-    // rows that belong to no sequence are never written by the attention kernel: keep them finite (their V rows are masked keys)
-    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * nq * D * 2, st));
+int dec_run(const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* pool_row, const PackedSeqs& s,
+            void* hidden_out, void* workspace, hipStream_t st) {
+    const DecFamily fam{w, ids, pos, pool_row};
+    const int H = w->hidden, T = s.n_rows, L = w->layers;
+    VarlenBufs b;
+    if (int rc = varlen_begin(dec_plan(w, T), workspace, T, w->heads * w->head_dim, st, &b)) return rc;
+    if (!pool_row) return prenorm_run<Silu>(fam, b, s, hidden_out, st);
+    if (int rc = fam.embed(b, T, st)) return rc;
+    if (int rc = prenorm_layers<Silu>(fam, 0, L - 1, b, s, st)) return rc;
+    // The last layer for the pooled rows only, on compact [M][...] buffers that reuse the full-size ones this layer no longer needs
+    // (launches of one stream run in order): context -> ctx, residual rows of ha -> hb, h1 -> x, its norm -> ha, the layer's output
+    // -> hb.  Rows n_seq .. M - 1 are zero and stay zero through every step.  A model without layers: embedding -> final norm of
+    // the pooled rows.
+    const int M = rows_pad(s.n_seq);
+    if (L > 0)
+        if (int rc = prenorm_attention_half(fam, L - 1, b, s, T, st)) return rc;
     {
         TtProfScope prof(TT_K_ROWOPS, st);
-        hipLaunchKernelGGL(embed_gather_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, ha);
+        hipLaunchKernelGGL(dec_gather_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, b.ha, H, pool_row, s.n_seq, M, T, H, b.hb);
         TT_CHECK_LAUNCH();
     }
-    // the rows of one layer's second half: M rows of residual `res` and context `c`, through h1 (and x, gu, act) into `out`
-    auto block_tail = [&](const tt_decoder_layer_weights& lw, int M, const uint16_t* c, const uint16_t* res, uint16_t* h1, uint16_t* xn,
-                          uint16_t* out) -> int {
-        GemmParams go = gemm_16(c, lw.o_w, zero, M, H, nq * D);
-        go.residual = res; go.ldr = H; go.C = h1; go.ldc = H;
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = rmsnorm_launch(h1, xn, lw.ffn_norm, M, H, w->rms_eps, st)) return rc;
-        GemmParams g1 = gemm_16(xn, lw.gate_up_w, zero, M, 2 * F, H);
-        g1.C = gu; g1.ldc = 2 * F;
-        if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        if (int rc = gated_act_launch<Silu>(gu, act, M, F, st)) return rc;
-        GemmParams g2 = gemm_16(act, lw.down_w, zero, M, H, F);
-        g2.residual = h1; g2.ldr = H; g2.C = out; g2.ldc = H;
-        return tt_gemm_launch(g2, TT_EPI_RESIDUAL, st);
-    };
-    auto gather = [&](uint16_t* dst, int M) -> int {
-        TtProfScope prof(TT_K_ROWOPS, st);
-        hipLaunchKernelGGL(dec_gather_rows_kernel, dim3((M + 3) / 4), dim3(256), 0, st, ha, H, pool_row, n_seq, M, T, H, dst);
-        TT_CHECK_LAUNCH();
-        return TT_OK;
-    };
-    for (int l = 0; l < w->layers; ++l) {
-        const tt_decoder_layer_weights& lw = w->layer[l];
-        if (int rc = rmsnorm_launch(ha, x, lw.attn_norm, T, H, w->rms_eps, st)) return rc;
-        GemmParams g = gemm_16(x, lw.qkv_w, zero, T, nqkv, H);
-        g.C = qkv; g.ldc = nqkv;
-        if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
-        if (int rc = qknorm_rope_launch(qkv, nqkv, pos, lw.q_norm, lw.k_norm, T, nq, nkv, D, w->rms_eps, w->rope_theta, vt, 8 * nkv * D,
-                                        st))
-            return rc;
-        if (pool_row && l == w->layers - 1) {
-            // The last layer for the pooled rows only, on compact [M][...] buffers that reuse the full-size ones this layer no longer
-            // needs (launches of one stream run in order): context -> ctx, residual rows of ha -> hb, h1 -> x, its norm -> ha,
-            // the layer's output -> hb.  Rows n_seq .. M - 1 are zero and stay zero through every step.
-            const int M = rows_pad(n_seq);
-            TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)M * nq * D * 2, st));
-            if (int rc = attention_rows_launch(qkv, nqkv, 0, nq * D, vt, 8 * nkv * D, ctx, nq * D, seq_start, seq_len, pool_row, n_seq, T,
-                                               nq, nkv, D, st))
-                return rc;
-            if (int rc = gather(hb, M)) return rc;
-            if (int rc = block_tail(lw, M, ctx, hb, x, ha, hb)) return rc;
-            return rmsnorm_launch(hb, (uint16_t*)hidden_out, w->final_norm, M, H, w->rms_eps, st);
-        }
-        if (int rc = attention_launch(qkv, nqkv, 0, nq * D, vt, 8 * nkv * D, ctx, nq * D, seq_start, seq_len, n_seq, T, nq, nkv, D,
-                                      max_len, st))
-            return rc;
-        if (int rc = block_tail(lw, T, ctx, ha, hb, x, ha)) return rc;
-    }
-    if (pool_row) {   // a model without layers: embedding -> final norm of the pooled rows
-        const int M = rows_pad(n_seq);
-        if (int rc = gather(hb, M)) return rc;
-        return rmsnorm_launch(hb, (uint16_t*)hidden_out, w->final_norm, M, H, w->rms_eps, st);
-    }
-    return rmsnorm_launch(ha, (uint16_t*)hidden_out, w->final_norm, T, H, w->rms_eps, st);
+    if (L > 0)
+        if (int rc = prenorm_tail_half<Silu>(fam, L - 1, b, M, b.ctx, b.hb, b.x, b.ha, b.hb, st)) return rc;
+    return fam.norm(b.hb, (uint16_t*)hidden_out, w->final_norm, b.zero, M, st);
 }
 
 int check_forward_args(const char* what, const tt_decoder_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* type_ids,
@@ -424,7 +340,7 @@ int tt_decoder_forward(const tt_decoder_weights* w, const int32_t* ids, const in
     if (int rc = check_forward_args("tt_decoder_forward", w, ids, pos, type_ids, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out,
                                     workspace, workspace_bytes))
         return rc;
-    return dec_run(w, ids, pos, seq_start, seq_len, nullptr, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+    return dec_run(w, ids, pos, nullptr, PackedSeqs{seq_start, seq_len, n_seq, n_rows, max_len}, hidden_out, workspace, (hipStream_t)stream);
 }
 
 size_t tt_decoder_rows_workspace_bytes(const tt_decoder_weights* w, int n_rows, int n_seq) {
@@ -440,7 +356,7 @@ int tt_decoder_forward_rows(const tt_decoder_weights* w, const int32_t* ids, con
         return rc;
     TT_CHECK_ARG(pool_row != nullptr, "pool_row is NULL (one row per sequence)");
     TT_CHECK_ARG(n_seq <= n_rows, "n_seq=%d exceeds n_rows=%d", n_seq, n_rows);
-    return dec_run(w, ids, pos, seq_start, seq_len, pool_row, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+    return dec_run(w, ids, pos, pool_row, PackedSeqs{seq_start, seq_len, n_seq, n_rows, max_len}, hidden_out, workspace, (hipStream_t)stream);
 }
 
 int tt_decoder_score(const void* hidden, int ld, const float* score_w, int n_seq, int hidden_size, float* scores, float* logits,

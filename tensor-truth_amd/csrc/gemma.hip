@@ -18,8 +18,10 @@
 //   h    = h1 + norm(y; post_feedforward_layernorm), x = norm(h; the next layer's input_layernorm)   the same row op; after the
 //                                                        last layer the second norm is the model's final norm and x is hidden_out
 // Every row op reads one token row only, so a token's result does not depend on how the batch is packed; the attention mixes the
-// rows of one sequence only.  The attention tile, the gated-activation kernel, the workspace plan and the batch-argument checks are
-// the ones the decoder and ModernBERT paths use (varlen.h).
+// rows of one sequence only.  The layer loop below is this family's own: the sandwich norms produce the next layer's x inside the
+// residual row op and the projections have no residual epilogue, so prenorm.h's two halves do not fit it.  The forward's prologue and
+// buffers are prenorm.h's; the attention tile and its windowed wrapper, the gated-activation kernel with the tanh GELU, the
+// workspace plan and the shape and batch-argument checks varlen.h's; the Dense tail pool_dense.h's.
 //
 // The row ops that add or subtract (h + norm(y), the rotation a cos - b sin) evaluate in fp64: where the two terms cancel, an fp32
 // evaluation's own error (1e-7 of the terms) exceeds a bf16 ulp of the small result, and the parity tests hold every element to one
@@ -27,7 +29,8 @@
 // residual op still runs at two thirds of the copy bandwidth.
 //
 // bf16 only: the model card rules fp16 out (activations overflow), so this file is compiled once and has no _f16 twins.
-#include "varlen.h"
+#include "pool_dense.h"
+#include "prenorm.h"
 
 #include <cmath>
 
@@ -192,157 +195,14 @@ __global__ __launch_bounds__(256) void gm_add_norm_kernel(const uint16_t* __rest
     }
 }
 
-// ---- GELU_tanh(gate) * up through varlen.h's gated_act_kernel: gu [T][2F] (gate columns, then up columns) -> out [T][F] -----------
-// torch's gelu(approximate="tanh"): 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3), written as x / (1 + exp(-2 u))
-// (1 + tanh(u) = 2 / (1 + exp(-2 u))), fp32.
-struct GeluTanh {
-    static __device__ __forceinline__ float f(float x) {
-        const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-        return x / (1.0f + expf(-2.0f * u));
-    }
-};
-
-// ---- bidirectional GQA attention with a window over packed varlen sequences, head_dim 256 --------------------------------------
-// The decoder's launch geometry: one wave per (16-query tile, sequence, query head) on varlen.h's tile with the window mask.
-__global__ __launch_bounds__(64) void gm_attention_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
-                                                          const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
-                                                          int ld_out, const int32_t* __restrict__ seq_start,
-                                                          const int32_t* __restrict__ seq_len, int n_seq, int n_rows, int group, int w,
-                                                          float scale_log2) {
-    const int t = blockIdx.x;
-    for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
-        attention_tile<256, true>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, w, scale_log2, b,
-                                  blockIdx.z, t);
-}
-
-// ---- the sentence-transformers tail: mean pooling -> Dense 1 -> Dense 2 -> L2 normalisation, fp32 -----------------------------------
-// One block of sixteen waves per GM_SB sequences: the two matrices are read once per block, not once per sequence.  The rows live
-// in LDS: buf_a [GM_SB][wa] (the pooled rows, later the second Dense's outputs; wa = max(H, n2)) and buf_b [GM_SB][n1] -- up to
-// 128 KiB, so one block per CU: its sixteen waves are what hides the matrices' load latency.
-//   pooling  wave v < GM_SB takes the block's sequence v; a column is summed over the sequence's rows in ascending order;
-//   Dense    thread t owns the outputs t, t + 1024, ... of all GM_SB sequences and walks the inputs in ascending order over the
-//            TRANSPOSED matrix (coalesced rows); the pooled values are LDS broadcasts;
-//   norm     out = v / max(||v||, 1e-12), one wave per sequence.
-// What a sequence gets depends on its own rows only, not on its place in the block or the batch.
-constexpr int GM_SB = 8;
-constexpr int GM_TAIL_THREADS = 1024;
-
-__device__ __forceinline__ void gm_dense(const float* __restrict__ in, int in_stride, int K, const float* __restrict__ wt, int N,
-                                         float* __restrict__ outp, int out_stride) {
-    for (int o = threadIdx.x; o < N; o += GM_TAIL_THREADS) {
-        float acc[GM_SB];
-#pragma unroll
-        for (int s = 0; s < GM_SB; ++s) acc[s] = 0.f;
-        for (int i = 0; i < K; i += 4) {
-            const float w0 = wt[(size_t)i * N + o], w1 = wt[(size_t)(i + 1) * N + o], w2 = wt[(size_t)(i + 2) * N + o],
-                        w3 = wt[(size_t)(i + 3) * N + o];
-#pragma unroll
-            for (int s = 0; s < GM_SB; ++s) {
-                const float4 x = *reinterpret_cast<const float4*>(in + s * in_stride + i);
-                acc[s] += x.x * w0;
-                acc[s] += x.y * w1;
-                acc[s] += x.z * w2;
-                acc[s] += x.w * w3;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < GM_SB; ++s) outp[s * out_stride + o] = acc[s];
-    }
-}
-
-__global__ __launch_bounds__(GM_TAIL_THREADS) void gm_pool_dense_kernel(const uint16_t* __restrict__ hidden, int ld,
-                                                            const int32_t* __restrict__ seq_start, const int32_t* __restrict__ seq_len,
-                                                            int n_seq, int H, int n1, int n2, const float* __restrict__ w1t,
-                                                            const float* __restrict__ w2t, float* __restrict__ out,
-                                                            uint16_t* __restrict__ out16) {
-    extern __shared__ float gm_lds[];
-    const int wa = H > n2 ? H : n2;
-    float* buf_a = gm_lds;
-    float* buf_b = gm_lds + GM_SB * wa;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int b0 = blockIdx.x * GM_SB;
-    for (int slot = wave; slot < GM_SB; slot += GM_TAIL_THREADS / 64) {
-        const int b = b0 + slot;
-        const int s0 = b < n_seq ? seq_start[b] : -1;
-        const int n = b < n_seq ? seq_len[b] : 0;
-        // lane owns the 8-element chunks lane, lane + 64 (H <= 1024)
-        float acc[2][8];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
-        if (s0 >= 0) {
-            for (int r = 0; r < n; ++r) {
-                const uint4* src = reinterpret_cast<const uint4*>(hidden + (size_t)(s0 + r) * ld);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int ch = lane + 64 * j;
-                    if (ch >= H / 8) continue;
-                    const uint4 v = src[ch];
-                    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        acc[j][2 * k] += elo(u[k]);
-                        acc[j][2 * k + 1] += ehi(u[k]);
-                    }
-                }
-            }
-        }
-        const float inv_n = (s0 >= 0 && n > 0) ? 1.0f / (float)n : 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ch = lane + 64 * j;
-            if (ch >= H / 8) continue;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) buf_a[slot * wa + 8 * ch + k] = acc[j][k] * inv_n;
-        }
-    }
-    __syncthreads();
-    gm_dense(buf_a, wa, H, w1t, n1, buf_b, n1);
-    __syncthreads();
-    gm_dense(buf_b, n1, n1, w2t, n2, buf_a, wa);
-    __syncthreads();
-    for (int slot = wave; slot < GM_SB; slot += GM_TAIL_THREADS / 64) {
-        const int b = b0 + slot;
-        if (b >= n_seq) continue;   // (wave-uniform)
-        float ss = 0.f;
-        for (int o = lane; o < n2; o += 64) ss += buf_a[slot * wa + o] * buf_a[slot * wa + o];
-        const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
-        for (int o = lane; o < n2; o += 64) {
-            const float v = buf_a[slot * wa + o] * inv;
-            out[(size_t)b * n2 + o] = v;
-            if (out16) out16[(size_t)b * n2 + o] = f32_to_bf16_bits(v);
-        }
-    }
-}
-
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
-int check_heads(int heads, int kv_heads, int head_dim) {
-    if (head_dim != 256) {
-        tt_set_error("gemma: head_dim=%d (supported: 256)", head_dim);
-        return TT_E_UNSUPPORTED;
-    }
-    TT_CHECK_ARG(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "gemma: heads=%d is not a multiple of kv_heads=%d", heads, kv_heads);
-    return TT_OK;
-}
-
-int check_hidden(int hidden) {
-    if (hidden <= 0 || hidden % 128 || hidden > 1024) {
-        tt_set_error("gemma: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", hidden);
-        return TT_E_UNSUPPORTED;
-    }
-    return TT_OK;
-}
+int check_heads(int heads, int kv_heads, int head_dim) { return check_gqa_heads("gemma", heads, kv_heads, head_dim, 256); }
 
 int check_weights(const tt_gemma_weights* w) {
     TT_CHECK_ARG(w != nullptr, "null weights");
     if (int rc = check_heads(w->heads, w->kv_heads, w->head_dim)) return rc;
-    if (int rc = check_hidden(w->hidden)) return rc;
-    if (((w->heads + 2 * w->kv_heads) * w->head_dim) % 128 || (w->heads * w->head_dim) % 64 || w->ffn <= 0 || w->ffn % 64) {
-        tt_set_error("gemma: (heads + 2 kv_heads) * head_dim = %d must be a multiple of 128, heads * head_dim and ffn=%d of 64",
-                     (w->heads + 2 * w->kv_heads) * w->head_dim, w->ffn);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_hidden("gemma", w->hidden)) return rc;
+    if (int rc = check_qkv_width("gemma", w->heads, w->kv_heads, w->head_dim, w->ffn)) return rc;
     TT_CHECK_ARG(w->layers >= 0 && (w->layers == 0 || w->layer != nullptr), "layer array missing");
     TT_CHECK_ARG(w->embed && w->final_norm && w->vocab > 0, "embedding table / final norm missing");
     TT_CHECK_ARG(w->rms_eps > 0.f && w->global_rope_theta > 0.f && w->local_rope_theta > 0.f && w->window >= 0 && w->embed_scale > 0.f,
@@ -361,7 +221,7 @@ GemmaWs gm_plan(const tt_gemma_weights* w, int n_rows) {
     const size_t nqkv = (size_t)(w->heads + 2 * w->kv_heads) * D;
     GemmaWs p{};
     // zeros: the GEMMs' bias operand (the model has none)
-    p.e = varlen_plan(n_rows, H, nqkv, w->kv_heads * D, w->heads * D, F, std::max(nqkv, std::max(2 * F, H)));
+    p.e = varlen_plan(n_rows, H, nqkv, w->kv_heads * D, w->heads * D, 2 * F, F, std::max(nqkv, std::max(2 * F, H)));
     // y: the output of the two projections that feed a post-norm
     const size_t T = ((size_t)n_rows + 255) / 256 * 256;
     p.off_y = tt_align_up(p.e.total, 256);
@@ -399,69 +259,42 @@ int qknorm_rope_launch(uint16_t* qkv, int ld, const int32_t* pos, const float* q
     return TT_OK;
 }
 
-// window < 0: no window
-int attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, const uint16_t* vt, int ldvt, uint16_t* out, int ld_out,
-                     const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads, int max_len,
-                     int window, hipStream_t st) {
-    const int n_qt = (max_len + 15) / 16;
-    const dim3 grid(n_qt, std::min(n_seq, 65535), heads);   // more sequences: each block row takes every 65535th
-    const float scale_log2 = 1.4426950408889634f / 16.0f;   // log2(e) / sqrt(256)
-    const int w = (window < 0 || window > n_rows) ? n_rows : window;   // |q - k| < n_rows within a batch
-    TtProfScope prof(TT_K_ATTENTION, st);
-    hipLaunchKernelGGL(gm_attention_kernel, grid, dim3(64), 0, st, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len,
-                       n_seq, n_rows, heads / kv_heads, w, scale_log2);
-    TT_CHECK_LAUNCH();
-    return TT_OK;
-}
-
 int gm_run(const tt_gemma_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len, int n_seq,
            int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
     const GemmaWs p = gm_plan(w, n_rows);
-    const VarlenWs& e = p.e;
-    char* ws = (char*)workspace;
     const int H = w->hidden, F = w->ffn, D = w->head_dim, nq = w->heads, nkv = w->kv_heads, T = n_rows;
     const int nqkv = (nq + 2 * nkv) * D;
-    uint16_t* ha = (uint16_t*)(ws + e.off_ha);
-    uint16_t* hb = (uint16_t*)(ws + e.off_hb);
-    uint16_t* x = (uint16_t*)(ws + e.off_x);
-    uint16_t* qkv = (uint16_t*)(ws + e.off_qkv);
-    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
-    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
-    uint16_t* gu = (uint16_t*)(ws + e.off_gu);
-    uint16_t* act = (uint16_t*)(ws + e.off_act);
-    uint16_t* y = (uint16_t*)(ws + p.off_y);
-    const float* zero = (const float*)(ws + e.off_zero);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
-    // rows that belong to no sequence are never written by the attention kernel: keep them finite (their V rows are masked keys)
-    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * nq * D * 2, st));
-    if (int rc = embed_launch(ids, w, T, ha, st)) return rc;
-    if (w->layers == 0) return add_norm_launch(nullptr, ha, nullptr, w->final_norm, T, H, w->rms_eps, nullptr, (uint16_t*)hidden_out, st);
-    if (int rc = add_norm_launch(nullptr, ha, nullptr, w->layer[0].input_norm, T, H, w->rms_eps, nullptr, x, st)) return rc;
+    VarlenBufs b;
+    if (int rc = varlen_begin(p.e, workspace, T, nq * D, st, &b)) return rc;
+    uint16_t* y = (uint16_t*)((char*)workspace + p.off_y);
+    if (int rc = embed_launch(ids, w, T, b.ha, st)) return rc;
+    if (w->layers == 0) return add_norm_launch(nullptr, b.ha, nullptr, w->final_norm, T, H, w->rms_eps, nullptr, (uint16_t*)hidden_out, st);
+    if (int rc = add_norm_launch(nullptr, b.ha, nullptr, w->layer[0].input_norm, T, H, w->rms_eps, nullptr, b.x, st)) return rc;
     for (int l = 0; l < w->layers; ++l) {
         const tt_gemma_layer_weights& lw = w->layer[l];
         const bool last = l == w->layers - 1;
-        GemmParams g = gemm_16(x, lw.qkv_w, zero, T, nqkv, H);
-        g.C = qkv; g.ldc = nqkv;
+        GemmParams g = gemm_16(b.x, lw.qkv_w, b.zero, T, nqkv, H);
+        g.C = b.qkv; g.ldc = nqkv;
         if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
-        if (int rc = qknorm_rope_launch(qkv, nqkv, pos, lw.q_norm, lw.k_norm, T, nq, nkv, w->rms_eps,
-                                        lw.sliding ? w->local_rope_theta : w->global_rope_theta, vt, 8 * nkv * D, st))
+        if (int rc = qknorm_rope_launch(b.qkv, nqkv, pos, lw.q_norm, lw.k_norm, T, nq, nkv, w->rms_eps,
+                                        lw.sliding ? w->local_rope_theta : w->global_rope_theta, b.vt, 8 * nkv * D, st))
             return rc;
-        if (int rc = attention_launch(qkv, nqkv, 0, nq * D, vt, 8 * nkv * D, ctx, nq * D, seq_start, seq_len, n_seq, T, nq, nkv, max_len,
-                                      lw.sliding ? w->window : -1, st))
+        if (int rc = window_attention_launch<256>(b.qkv, nqkv, 0, nq * D, b.vt, 8 * nkv * D, b.ctx, nq * D, seq_start, seq_len, n_seq, T, nq, nkv,
+                                                  max_len, lw.sliding ? w->window : -1, st))
             return rc;
-        GemmParams go = gemm_16(ctx, lw.o_w, zero, T, H, nq * D);
+        GemmParams go = gemm_16(b.ctx, lw.o_w, b.zero, T, H, nq * D);
         go.C = y; go.ldc = H;
         if (int rc = tt_gemm_launch(go, TT_EPI_BIAS, st)) return rc;
-        if (int rc = add_norm_launch(y, ha, lw.post_attn_norm, lw.pre_ffn_norm, T, H, w->rms_eps, hb, x, st)) return rc;
-        GemmParams g1 = gemm_16(x, lw.gate_up_w, zero, T, 2 * F, H);
-        g1.C = gu; g1.ldc = 2 * F;
+        if (int rc = add_norm_launch(y, b.ha, lw.post_attn_norm, lw.pre_ffn_norm, T, H, w->rms_eps, b.hb, b.x, st)) return rc;
+        GemmParams g1 = gemm_16(b.x, lw.gate_up_w, b.zero, T, 2 * F, H);
+        g1.C = b.gu; g1.ldc = 2 * F;
         if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        if (int rc = gated_act_launch<GeluTanh>(gu, act, T, F, st)) return rc;
-        GemmParams g2 = gemm_16(act, lw.down_w, zero, T, H, F);
+        if (int rc = gated_act_launch<GeluTanh>(b.gu, b.act, T, F, st)) return rc;
+        GemmParams g2 = gemm_16(b.act, lw.down_w, b.zero, T, H, F);
         g2.C = y; g2.ldc = H;
         if (int rc = tt_gemm_launch(g2, TT_EPI_BIAS, st)) return rc;
-        if (int rc = add_norm_launch(y, hb, lw.post_ffn_norm, last ? w->final_norm : w->layer[l + 1].input_norm, T, H, w->rms_eps, ha,
-                                     last ? (uint16_t*)hidden_out : x, st))
+        if (int rc = add_norm_launch(y, b.hb, lw.post_ffn_norm, last ? w->final_norm : w->layer[l + 1].input_norm, T, H, w->rms_eps, b.ha,
+                                     last ? (uint16_t*)hidden_out : b.x, st))
             return rc;
     }
     return TT_OK;
@@ -495,7 +328,7 @@ int tt_gemma_forward(const tt_gemma_weights* w, const int32_t* ids, const int32_
 int tt_gemma_pool_dense(const tt_gemma_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
                         int n_seq, float* out_f32, void* out_16, void* stream) {
     TT_CHECK_ARG(w != nullptr, "null weights");
-    if (int rc = check_hidden(w->hidden)) return rc;
+    if (int rc = check_hidden("gemma", w->hidden)) return rc;
     TT_CHECK_ARG(n_seq >= 0, "n_seq=%d", n_seq);
     if (n_seq == 0) return TT_OK;
     TT_CHECK_ARG(hidden && seq_start && seq_len && out_f32, "null pointer");
@@ -507,14 +340,9 @@ int tt_gemma_pool_dense(const tt_gemma_weights* w, const void* hidden, int ld, c
         return TT_E_UNSUPPORTED;
     }
     TT_CHECK_ARG(ld >= w->hidden && ld % 8 == 0 && ((uintptr_t)hidden % 16) == 0, "hidden=%d ld=%d (16-byte aligned rows)", w->hidden, ld);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)GM_SB * (std::max(w->hidden, w->dense2_out) + w->dense1_out) * sizeof(float);   // <= 128 KiB
-    TT_SET_MAX_LDS(gm_pool_dense_kernel, GM_SB * (1024 + 3072) * sizeof(float));
-    TtProfScope prof(TT_K_ROWOPS, st);
-    hipLaunchKernelGGL(gm_pool_dense_kernel, dim3((n_seq + GM_SB - 1) / GM_SB), dim3(GM_TAIL_THREADS), lds, st, (const uint16_t*)hidden, ld, seq_start,
-                       seq_len, n_seq, w->hidden, w->dense1_out, w->dense2_out, w->dense1_wt, w->dense2_wt, out_f32, (uint16_t*)out_16);
-    TT_CHECK_LAUNCH();
-    return TT_OK;
+    // LDS: eight rows of max(hidden, dense2_out) + dense1_out floats, <= 128 KiB
+    return pool_dense_launch(hidden, ld, seq_start, seq_len, n_seq, w->hidden, w->dense1_out, w->dense2_out, w->dense1_wt, w->dense2_wt,
+                             out_f32, out_16, POOL_SB * (1024 + 3072) * sizeof(float), (hipStream_t)stream);
 }
 
 int tt_gemma_qk_norm_rope(void* qkv, int ld, const int32_t* pos, const float* q_norm, const float* k_norm, int n_rows, int heads,
@@ -530,7 +358,7 @@ int tt_gemma_qk_norm_rope(void* qkv, int ld, const int32_t* pos, const float* q_
 
 int tt_gemma_add_norm(const void* y, const void* h, const float* norm_a, const float* norm_b, int n_rows, int hidden, float eps,
                       void* h_out, void* x_out, void* stream) {
-    if (int rc = check_hidden(hidden)) return rc;
+    if (int rc = check_hidden("gemma", hidden)) return rc;
     TT_CHECK_ARG(h && norm_b && x_out && n_rows > 0, "null pointer or n_rows=%d", n_rows);
     TT_CHECK_ARG(y == nullptr || (norm_a && h_out), "y without norm_a / h_out");
     TT_CHECK_ARG(eps > 0.f, "eps=%g", eps);
@@ -551,8 +379,8 @@ int tt_attention_window_gqa(const void* qkv, int ld, int q_col0, int k_col0, con
                      ld >= std::max(q_col0 + heads * head_dim, k_col0 + kv_heads * head_dim) && ld_out >= heads * head_dim &&
                      ldvt >= 8 * kv_heads * head_dim && ldvt % 8 == 0,
                  "ld=%d q_col0=%d k_col0=%d ld_out=%d ldvt=%d", ld, q_col0, k_col0, ld_out, ldvt);
-    return attention_launch((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out, seq_start, seq_len,
-                            n_seq, n_rows, heads, kv_heads, max_len, window, (hipStream_t)stream);
+    return window_attention_launch<256>((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out,
+                                        seq_start, seq_len, n_seq, n_rows, heads, kv_heads, max_len, window, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -16,11 +16,12 @@
 //   h    = GEMM(a, Wo_mlp) + h1
 // with h = LayerNorm(tok_embeddings[ids]) * g_emb before the first layer and out = LayerNorm(h) * g_final after the last.  Every
 // row op reads one token row only, so a token's result does not depend on how the batch is packed; the attention mixes the rows of
-// one sequence only.  The attention tile, the embedding gather, the gated-activation kernel, the workspace plan and the
-// batch-argument checks are the ones the decoder path uses too (varlen.h).
+// one sequence only.  The schedule itself is prenorm.h's (the driver Qwen3 and T5 run on too: MbFamily below says what is
+// ModernBERT's); the attention tile and its windowed wrapper, the embedding gather, the gated-activation kernel, the workspace plan
+// and the batch-argument checks are varlen.h's, and so is the head's pooling loop.
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
-#include "varlen.h"
+#include "prenorm.h"
 
 #include <cmath>
 
@@ -62,19 +63,6 @@ __global__ __launch_bounds__(256) void mb_rope_kernel(uint16_t* __restrict__ qkv
     }
 }
 
-// ---- bidirectional attention with a sliding window over packed varlen sequences, head_dim 64 ---------------------------------
-// One wave per (16-query tile, sequence, head) on varlen.h's tile with the window mask; every head has its own K and V (group 1).
-__global__ __launch_bounds__(64) void mb_attention_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
-                                                          const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
-                                                          int ld_out, const int32_t* __restrict__ seq_start,
-                                                          const int32_t* __restrict__ seq_len, int n_seq, int n_rows, int w,
-                                                          float scale_log2) {
-    const int t = blockIdx.x;
-    for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
-        attention_tile<64, true>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, 1, w, scale_log2, b,
-                                 blockIdx.z, t);
-}
-
 // ---- classification head: pooling -> head.dense -> GELU -> head.norm -> classifier -> sigmoid, fp32 ---------------------------
 // One wave (one block) per sequence.  The pooled row (the first token's, or the mean over the sequence's tokens summed in ascending
 // order) goes to LDS; lane l owns the dense outputs l, l + 64, ... and walks the inputs in ascending order over the TRANSPOSED
@@ -91,27 +79,7 @@ __global__ __launch_bounds__(64) void mb_head_kernel(const uint16_t* __restrict_
     const bool ok = s0 >= 0 && n > 0;
     // pooled row: lane owns the 8-element chunks lane, lane + 64 (H <= 1024)
     float acc[2][8];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
-    if (ok) {
-        for (int r = 0; r < n; ++r) {
-            const uint4* src = reinterpret_cast<const uint4*>(hidden + (size_t)(s0 + r) * ld);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int ch = lane + 64 * j;
-                if (ch >= H / 8) continue;
-                const uint4 v = src[ch];
-                const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    acc[j][2 * k] += elo(u[k]);
-                    acc[j][2 * k + 1] += ehi(u[k]);
-                }
-            }
-        }
-    }
+    pool_rows_sum(hidden, ld, s0, n, H, lane, acc);
     const float inv_n = ok ? 1.0f / (float)n : 0.f;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -169,10 +137,7 @@ __global__ __launch_bounds__(64) void mb_head_kernel(const uint16_t* __restrict_
 
 // ---- argument checks -----------------------------------------------------------------------------------------------------------
 int check_shape(int hidden, int heads, int ffn) {
-    if (hidden <= 0 || hidden % 128 || hidden > 1024) {
-        tt_set_error("modernbert: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", hidden);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_hidden("modernbert", hidden)) return rc;
     if (heads <= 0 || hidden != 64 * heads) {
         tt_set_error("modernbert: hidden=%d heads=%d: head_dim must be 64", hidden, heads);
         return TT_E_UNSUPPORTED;
@@ -198,12 +163,7 @@ int check_weights(const tt_modernbert_weights* w) {
 VarlenWs mb_plan(const tt_modernbert_weights* w, int n_rows) {
     const size_t H = (size_t)w->hidden, F = (size_t)w->ffn;
     // zeros: the GEMMs' bias operand and the LayerNorms' beta (the model has neither)
-    return varlen_plan(n_rows, H, 3 * H, H, H, F, std::max(3 * H, 2 * F));
-}
-
-int layernorm_launch(const uint16_t* in, uint16_t* out, const float* g, const float* zero, int rows, int H, float eps, hipStream_t st) {
-    TtProfScope prof(TT_K_ROWOPS, st);
-    return tt_layernorm_launch(in, out, g, zero, rows, H, eps, st);
+    return varlen_plan(n_rows, H, 3 * H, H, H, 2 * F, F, std::max(3 * H, 2 * F));
 }
 
 int rope_launch(uint16_t* qkv, int ld, const int32_t* pos, int rows, int heads, float theta, uint16_t* vt, int ldvt, hipStream_t st) {
@@ -215,82 +175,45 @@ int rope_launch(uint16_t* qkv, int ld, const int32_t* pos, int rows, int heads, 
     return TT_OK;
 }
 
-// window < 0: no window
-int window_attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, const uint16_t* vt, int ldvt, uint16_t* out, int ld_out,
-                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int max_len, int window,
-                            hipStream_t st) {
-    const int n_qt = (max_len + 15) / 16;
-    const dim3 grid(n_qt, std::min(n_seq, 65535), heads);   // more sequences: each block row takes every 65535th
-    const float scale_log2 = 1.4426950408889634f / 8.0f;    // log2(e) / sqrt(64)
-    const int w = (window < 0 || window > n_rows) ? n_rows : window;   // |q - k| < n_rows within a batch
-    TtProfScope prof(TT_K_ATTENTION, st);
-    hipLaunchKernelGGL(mb_attention_kernel, grid, dim3(64), 0, st, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len,
-                       n_seq, n_rows, w, scale_log2);
-    TT_CHECK_LAUNCH();
-    return TT_OK;
-}
+// what prenorm.h's driver asks of a family
+struct MbFamily {
+    static constexpr QkvForm qkv = QkvForm::Packed;
+    const tt_modernbert_weights* w;
+    const int32_t *ids, *pos;
 
-int mb_run(const tt_modernbert_weights* w, const int32_t* ids, const int32_t* pos, const int32_t* seq_start, const int32_t* seq_len,
-           int n_seq, int n_rows, int max_len, void* hidden_out, void* workspace, hipStream_t st) {
-    const VarlenWs e = mb_plan(w, n_rows);
-    char* ws = (char*)workspace;
-    const int H = w->hidden, F = w->ffn, nh = w->heads, T = n_rows;
-    uint16_t* ha = (uint16_t*)(ws + e.off_ha);
-    uint16_t* hb = (uint16_t*)(ws + e.off_hb);
-    uint16_t* x = (uint16_t*)(ws + e.off_x);
-    uint16_t* qkv = (uint16_t*)(ws + e.off_qkv);
-    uint16_t* vt = (uint16_t*)(ws + e.off_vt);
-    uint16_t* ctx = (uint16_t*)(ws + e.off_ctx);
-    uint16_t* gu = (uint16_t*)(ws + e.off_gu);
-    uint16_t* act = (uint16_t*)(ws + e.off_act);
-    const float* zero = (const float*)(ws + e.off_zero);
-    TT_CHECK_HIP(hipMemsetAsync(ws + e.off_zero, 0, e.zero_bytes, st));
-    // rows that belong to no sequence are never written by the attention kernels: keep them finite (their V rows are masked keys)
-    TT_CHECK_HIP(hipMemsetAsync(ctx, 0, (size_t)T * H * 2, st));
-    {
+    PreNormDims dims() const { return {w->hidden, w->hidden, 3 * w->hidden, w->ffn, w->layers}; }
+    // the LayerNorms are the encoder's row op (rowops.hip) with a zero beta
+    int norm(const uint16_t* in, uint16_t* out, const float* g, const float* zero, int rows, hipStream_t st) const {
         TtProfScope prof(TT_K_ROWOPS, st);
-        hipLaunchKernelGGL(embed_gather_kernel, dim3(T), dim3(128), 0, st, ids, (const uint16_t*)w->embed, w->vocab, H, hb);
-        TT_CHECK_LAUNCH();
+        return tt_layernorm_launch(in, out, g, zero, rows, w->hidden, w->norm_eps, st);
     }
-    if (int rc = layernorm_launch(hb, ha, w->emb_norm, zero, T, H, w->norm_eps, st)) return rc;
-    for (int l = 0; l < w->layers; ++l) {
+    int embed(const VarlenBufs& b, int T, hipStream_t st) const {
+        if (int rc = embed_gather_launch(ids, w->embed, w->vocab, w->hidden, b.hb, T, st)) return rc;
+        return norm(b.hb, b.ha, w->emb_norm, b.zero, T, st);
+    }
+    PreNormLayer layer(int l) const {
         const tt_modernbert_layer_weights& lw = w->layer[l];
-        const uint16_t* xin = ha;
-        if (lw.attn_norm) {
-            if (int rc = layernorm_launch(ha, x, lw.attn_norm, zero, T, H, w->norm_eps, st)) return rc;
-            xin = x;
-        }
-        GemmParams g = gemm_16(xin, lw.qkv_w, zero, T, 3 * H, H);
-        g.C = qkv; g.ldc = 3 * H;
-        if (int rc = tt_gemm_launch(g, TT_EPI_BIAS, st)) return rc;
-        if (int rc = rope_launch(qkv, 3 * H, pos, T, nh, lw.sliding ? w->local_rope_theta : w->global_rope_theta, vt, 8 * H, st)) return rc;
-        if (lw.sliding) {
-            if (int rc = window_attention_launch(qkv, 3 * H, 0, H, vt, 8 * H, ctx, H, seq_start, seq_len, n_seq, T, nh, max_len,
-                                                 w->local_attention / 2, st))
-                return rc;
-        } else {
-            // global layers: the encoder's bidirectional kernel (64-wide heads, the same Q / K rows and V8 layout)
-            AttnParams a{};
-            a.qk = qkv; a.ld_qk = 3 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = vt; a.ldvt = 8 * H;
-            a.out = ctx; a.ld_out = H; a.seq_start = seq_start; a.seq_len = seq_len;
-            a.n_seq = n_seq; a.heads = nh; a.head_dim = 64; a.max_len = max_len; a.total_rows = T;
-            a.scale = 0.125f;
-            if (int rc = tt_attention_launch(a, st)) return rc;
-        }
-        GemmParams go = gemm_16(ctx, lw.o_w, zero, T, H, H);
-        go.residual = ha; go.ldr = H; go.C = hb; go.ldc = H;
-        if (int rc = tt_gemm_launch(go, TT_EPI_RESIDUAL, st)) return rc;
-        if (int rc = layernorm_launch(hb, x, lw.mlp_norm, zero, T, H, w->norm_eps, st)) return rc;
-        GemmParams g1 = gemm_16(x, lw.wi_w, zero, T, 2 * F, H);
-        g1.C = gu; g1.ldc = 2 * F;
-        if (int rc = tt_gemm_launch(g1, TT_EPI_BIAS, st)) return rc;
-        if (int rc = gated_act_launch<GeluErf>(gu, act, T, F, st)) return rc;
-        GemmParams g2 = gemm_16(act, lw.wo_w, zero, T, H, F);
-        g2.residual = hb; g2.ldr = H; g2.C = ha; g2.ldc = H;
-        if (int rc = tt_gemm_launch(g2, TT_EPI_RESIDUAL, st)) return rc;
+        return {lw.attn_norm, lw.qkv_w, lw.o_w, lw.mlp_norm, lw.wi_w, lw.wo_w};
     }
-    return layernorm_launch(ha, (uint16_t*)hidden_out, w->final_norm, zero, T, H, w->norm_eps, st);
-}
+    int post_qkv(int l, const VarlenBufs& b, int T, hipStream_t st) const {
+        return rope_launch(b.qkv, 3 * w->hidden, pos, T, w->heads, w->layer[l].sliding ? w->local_rope_theta : w->global_rope_theta, b.vt,
+                           8 * w->hidden, st);
+    }
+    int attention(int l, const VarlenBufs& b, const PackedSeqs& s, hipStream_t st) const {
+        const int H = w->hidden;
+        if (w->layer[l].sliding)
+            return window_attention_launch<64>(b.qkv, 3 * H, 0, H, b.vt, 8 * H, b.ctx, H, s.seq_start, s.seq_len, s.n_seq, s.n_rows,
+                                               w->heads, w->heads, s.max_len, w->local_attention / 2, st);
+        // global layers: the encoder's bidirectional kernel (64-wide heads, the same Q / K rows and V8 layout)
+        AttnParams a{};
+        a.qk = b.qkv; a.ld_qk = 3 * H; a.q_col0 = 0; a.k_col0 = H; a.vt = b.vt; a.ldvt = 8 * H;
+        a.out = b.ctx; a.ld_out = H; a.seq_start = s.seq_start; a.seq_len = s.seq_len;
+        a.n_seq = s.n_seq; a.heads = w->heads; a.head_dim = 64; a.max_len = s.max_len; a.total_rows = s.n_rows;
+        a.scale = 0.125f;
+        return tt_attention_launch(a, st);
+    }
+    const float* final_norm() const { return w->final_norm; }
+};
 
 }  // namespace
 
@@ -312,7 +235,10 @@ int tt_modernbert_forward(const tt_modernbert_weights* w, const int32_t* ids, co
         const tt_modernbert_layer_weights& lw = w->layer[l];
         TT_CHECK_ARG(lw.qkv_w && lw.o_w && lw.mlp_norm && lw.wi_w && lw.wo_w, "layer %d has a null weight pointer", l);
     }
-    return mb_run(w, ids, pos, seq_start, seq_len, n_seq, n_rows, max_len, hidden_out, workspace, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    VarlenBufs b;
+    if (int rc = varlen_begin(mb_plan(w, n_rows), workspace, n_rows, w->hidden, st, &b)) return rc;
+    return prenorm_run<GeluErf>(MbFamily{w, ids, pos}, b, PackedSeqs{seq_start, seq_len, n_seq, n_rows, max_len}, hidden_out, st);
 }
 
 int tt_modernbert_head(const tt_modernbert_weights* w, const void* hidden, int ld, const int32_t* seq_start, const int32_t* seq_len,
@@ -352,8 +278,8 @@ int tt_attention_window(const void* qkv, int ld, int q_col0, int k_col0, const v
     if (int rc = check_attention_layout("windowed attention", true, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len,
                                         n_seq, n_rows, heads, head_dim, max_len))
         return rc;
-    return window_attention_launch((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out, seq_start,
-                                   seq_len, n_seq, n_rows, heads, max_len, window, (hipStream_t)stream);
+    return window_attention_launch<64>((const uint16_t*)qkv, ld, q_col0, k_col0, (const uint16_t*)vt, ldvt, (uint16_t*)out, ld_out,
+                                       seq_start, seq_len, n_seq, n_rows, heads, heads, max_len, window, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -44,8 +44,6 @@ inline PostLnLayer postln_layer_of(const tt_layer_weights& lw) {
     return {lw.qkv_w, lw.qkv_b, lw.o_w, lw.o_b, lw.ln1_g, lw.ln1_b, lw.ffn1_w, lw.ffn1_b, lw.ffn2_w, lw.ffn2_b, lw.ln2_g, lw.ln2_b};
 }
 
-enum class QkvForm { SplitV8, Packed };
-
 struct PostLnDims {
     int hidden, heads, ffn, layers;
     float ln_eps;
@@ -55,19 +53,10 @@ struct PostLnDims {
     size_t tail_bytes;   // the family's own scratch behind the zeros (DeBERTa's score tables)
 };
 
-// the packed batch of one forward
-struct PackedSeqs {
-    const int32_t *seq_start, *seq_len;
-    int n_seq, n_rows, max_len;
-};
-
 // the limits every post-LN family shares: the row ops hold a row of up to 1024 values, the attention kernels take heads of 64, the
 // GEMM tiles are 128 columns wide (`ffn_multiple`: 64 where the up-projection is 2F wide)
 inline int check_postln_shape(const char* family, int hidden, int heads, int ffn, int ffn_multiple) {
-    if (hidden <= 0 || hidden % 128 || hidden > 1024) {
-        tt_set_error("%s: hidden=%d must be a multiple of 128 and <= 1024 (the scan's limit)", family, hidden);
-        return TT_E_UNSUPPORTED;
-    }
+    if (int rc = check_hidden(family, hidden)) return rc;
     if (heads <= 0 || hidden != 64 * heads) {
         tt_set_error("%s: hidden=%d heads=%d: head_dim must be 64", family, hidden, heads);
         return TT_E_UNSUPPORTED;

@@ -1,8 +1,9 @@
-// What the rotary, pre-norm, packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT; gemma.hip; and,
-// for the attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias, and deberta.hip:
+// What the packed-varlen model families share (decoder.hip: Qwen3; modernbert.hip: ModernBERT; t5.hip; gemma.hip; and, for the
+// attention tile and the argument checks, mpnet.hip: MPNet's post-LN layer with a relative-position bias, and deberta.hip:
 // DeBERTa-v2/v3's post-LN layer with disentangled attention; jinabert.hip: JinaBERT's post-LN layer with ALiBi): the attention
-// tile over the V8 layout, the embedding gather, the gated activation, the workspace plan and the forwards' argument checks.
-// The post-LN families' shared block is postln.h, on top of this header.
+// tile over the V8 layout and its windowed wrapper, the embedding gather, RMSNorm, the gated activation and its gates, the workspace
+// plan and the shape and argument checks.  The pre-norm families' shared block is prenorm.h, the post-LN families' postln.h, the
+// sentence-transformers tail (its pooling loop is here) pool_dense.h -- all on top of this header.
 // Device code sits in an anonymous namespace or is a template: one copy per translation unit and element type (common.h TT_F16).
 #pragma once
 #include "common.h"
@@ -29,8 +30,72 @@ __global__ __launch_bounds__(128) void embed_gather_kernel(const int32_t* __rest
     for (int c = threadIdx.x; c < H / 8; c += blockDim.x) dst[c] = ok ? src[c] : uint4{0u, 0u, 0u, 0u};
 }
 
+inline int embed_gather_launch(const int32_t* ids, const void* table, int vocab, int H, uint16_t* out, int rows, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(embed_gather_kernel, dim3(rows), dim3(128), 0, st, ids, (const uint16_t*)table, vocab, H, out);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
+// ---- RMSNorm over rows of H <= 1024 elements: one wave per row, four rows per block ---------------------------------------------
+// fp32 statistics.  ROUND_BEFORE_WEIGHT = false (Qwen3): out = e(v * rsqrt(mean(v^2) + eps) * w), one rounding to the element type.
+// ROUND_BEFORE_WEIGHT = true (T5LayerNorm): out = e(e(v * rsqrt(mean(v^2) + eps)) * w), the normalised value rounded to the
+// element type BEFORE the weight multiplies it, as transformers' T5LayerNorm does with 16-bit weights; the second product is exact
+// in fp32 when w holds values of the element type.
+template <bool ROUND_BEFORE_WEIGHT>
+__global__ __launch_bounds__(256) void rmsnorm_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
+                                                      const float* __restrict__ g, int rows, int H, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const uint4* src = reinterpret_cast<const uint4*>(in + (size_t)row * H);
+    uint4* dst = reinterpret_cast<uint4*>(out + (size_t)row * H);
+    const int nc = H / 8;   // <= 128 chunks of 8 elements: at most two per lane
+    uint4 v[2];
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j;
+        v[j] = c < nc ? src[c] : uint4{0u, 0u, 0u, 0u};
+        const uint32_t u[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a = elo(u[k]), b = ehi(u[k]);
+            ss += a * a;
+            ss += b * b;
+        }
+    }
+    const float r = rsqrtf(wave_sum(ss) / (float)H + eps);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = lane + 64 * j;
+        if (c >= nc) continue;
+        const uint32_t u[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+        uint32_t o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = 8 * c + 2 * k;
+            if constexpr (ROUND_BEFORE_WEIGHT) {
+                const uint32_t n2 = pack_e2(elo(u[k]) * r, ehi(u[k]) * r);   // the first rounding
+                o[k] = pack_e2(elo(n2) * g[e], ehi(n2) * g[e + 1]);
+            } else {
+                o[k] = pack_e2(elo(u[k]) * r * g[e], ehi(u[k]) * r * g[e + 1]);
+            }
+        }
+        dst[c] = uint4{o[0], o[1], o[2], o[3]};
+    }
+}
+
+template <bool ROUND_BEFORE_WEIGHT>
+int rmsnorm_launch(const uint16_t* in, uint16_t* out, const float* g, int rows, int H, float eps, hipStream_t st) {
+    TtProfScope prof(TT_K_ROWOPS, st);
+    hipLaunchKernelGGL(rmsnorm_kernel<ROUND_BEFORE_WEIGHT>, dim3((rows + 3) / 4), dim3(256), 0, st, in, out, g, rows, H, eps);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
 // ---- gated activation: gu [T][2F] (activated columns, then the columns that multiply them) -> out [T][F] ---------------------
-// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (GeluErf and Silu below)
+// out = Act::f(gu[:, :F]) * gu[:, F:], Act::f one fp32 value at a time (GeluErf, Silu and GeluTanh below)
 template <class Act>
 __global__ __launch_bounds__(256) void gated_act_kernel(const uint16_t* __restrict__ gu, uint16_t* __restrict__ out, int64_t n_chunks,
                                                         int F) {
@@ -76,6 +141,42 @@ struct GeluErf {
 struct Silu {
     static __device__ __forceinline__ float f(float x) { return x / (1.0f + expf(-x)); }
 };
+// GELU_tanh(gate) * up (EmbeddingGemma; T5 v1.1's gelu_new, transformers NewGELUActivation, is the same function):
+// 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3), written as x / (1 + exp(-2 u)) (1 + tanh(u) = 2 / (1 + exp(-2 u))), fp32
+struct GeluTanh {
+    static __device__ __forceinline__ float f(float x) {
+        const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
+        return x / (1.0f + expf(-2.0f * u));
+    }
+};
+
+// ---- the sum of the rows s0 .. s0 + n - 1 of `hidden` [.][ld], one wave: lane owns the 8-element chunks lane, lane + 64 (H <= 1024)
+// (the mean pooling of pool_dense.h's tail and of modernbert.hip's classification head)
+// A column is summed in ascending row order, 16-byte reads (any row may start a range).  s0 < 0 or n <= 0: zeros.
+__device__ __forceinline__ void pool_rows_sum(const uint16_t* __restrict__ hidden, int ld, int s0, int n, int H, int lane,
+                                              float (&acc)[2][8]) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
+    if (s0 >= 0) {
+        for (int r = 0; r < n; ++r) {
+            const uint4* src = reinterpret_cast<const uint4*>(hidden + (size_t)(s0 + r) * ld);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int ch = lane + 64 * j;
+                if (ch >= H / 8) continue;
+                const uint4 v = src[ch];
+                const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    acc[j][2 * k] += elo(u[k]);
+                    acc[j][2 * k + 1] += ehi(u[k]);
+                }
+            }
+        }
+    }
+}
 
 // ---- embeddings: out[r] = LayerNorm(word[ids[r]] + type[0]) * gamma + beta ------------------------------------------------------
 // One wave per row, four rows per block, as rowops.hip: lane l holds the 16-byte pieces l and l + 64 of the row (H <= 1024), the sum
@@ -371,6 +472,37 @@ __device__ __forceinline__ void attention_tile(const uint16_t* __restrict__ qkv,
     }
 }
 
+// ---- bidirectional GQA attention with a sliding window over packed varlen sequences (ModernBERT: D = 64, group 1; EmbeddingGemma:
+// D = 256): one wave per (16-query tile, sequence, query head) on the tile above with the window mask
+template <int D>
+__global__ __launch_bounds__(64) void window_attention_kernel(const uint16_t* __restrict__ qkv, int ld, int q_col0, int k_col0,
+                                                              const uint16_t* __restrict__ vt, int ldvt, uint16_t* __restrict__ out,
+                                                              int ld_out, const int32_t* __restrict__ seq_start,
+                                                              const int32_t* __restrict__ seq_len, int n_seq, int n_rows, int group,
+                                                              int w, float scale_log2) {
+    const int t = blockIdx.x;
+    for (int b = blockIdx.y; b < n_seq; b += gridDim.y)   // (wave-uniform: every lane takes the same sequences)
+        attention_tile<D, true>(qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start, seq_len, n_rows, group, w, scale_log2, b,
+                                blockIdx.z, t);
+}
+
+// window < 0: no window
+template <int D>
+int window_attention_launch(const uint16_t* qkv, int ld, int q_col0, int k_col0, const uint16_t* vt, int ldvt, uint16_t* out, int ld_out,
+                            const int32_t* seq_start, const int32_t* seq_len, int n_seq, int n_rows, int heads, int kv_heads, int max_len,
+                            int window, hipStream_t st) {
+    static_assert(D == 64 || D == 256, "head widths with a window: 64, 256");
+    const int n_qt = (max_len + 15) / 16;
+    const dim3 grid(n_qt, std::min(n_seq, 65535), heads);   // more sequences: each block row takes every 65535th
+    const float scale_log2 = 1.4426950408889634f / (D == 64 ? 8.0f : 16.0f);   // log2(e) / sqrt(D)
+    const int w = (window < 0 || window > n_rows) ? n_rows : window;   // |q - k| < n_rows within a batch
+    TtProfScope prof(TT_K_ATTENTION, st);
+    hipLaunchKernelGGL(window_attention_kernel<D>, grid, dim3(64), 0, st, qkv, ld, q_col0, k_col0, vt, ldvt, out, ld_out, seq_start,
+                       seq_len, n_seq, n_rows, heads / kv_heads, w, scale_log2);
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 // One forward's workspace: the residual stream twice (ha, hb), the normed rows x, the projections' outputs and the fp32 zeros that
 // stand in for the biases (and LayerNorm betas) these models do not have.  Rows are padded to the 256-row GEMM tile.
@@ -378,7 +510,9 @@ struct VarlenWs {
     size_t off_ha, off_hb, off_x, off_qkv, off_vt, off_ctx, off_gu, off_act, off_zero, zero_bytes, total;
 };
 
-inline VarlenWs varlen_plan(int n_rows, size_t H, size_t qkv_width, size_t vt_width, size_t ctx_width, size_t F, size_t zero_floats) {
+// gu_width: 2F, or 0 for an MLP without a gate (its up-projection goes straight to act: no gate buffer)
+inline VarlenWs varlen_plan(int n_rows, size_t H, size_t qkv_width, size_t vt_width, size_t ctx_width, size_t gu_width, size_t F,
+                            size_t zero_floats) {
     VarlenWs e{};
     const size_t T = ((size_t)n_rows + 255) / 256 * 256;
     WsPlanner ws;
@@ -388,12 +522,56 @@ inline VarlenWs varlen_plan(int n_rows, size_t H, size_t qkv_width, size_t vt_wi
     e.off_qkv = ws.take(T * qkv_width * 2);
     e.off_vt = ws.take(T * vt_width * 2);
     e.off_ctx = ws.take(T * ctx_width * 2);
-    e.off_gu = ws.take(T * 2 * F * 2);
+    e.off_gu = ws.take(T * gu_width * 2);
     e.off_act = ws.take(T * F * 2);
     e.zero_bytes = zero_floats * 4;
     e.off_zero = ws.take(e.zero_bytes);
     e.total = ws.off;
     return e;
+}
+
+// the packed batch of one forward
+struct PackedSeqs {
+    const int32_t *seq_start, *seq_len;
+    int n_seq, n_rows, max_len;
+};
+
+// how a layer's QKV projection is stored: q | k rows [T][2H] plus V in the V8 layout [T/8][H][8], written by the GEMM's epilogue
+// (TT_EPI_QKV), or one packed row [T][qkv width] of which the family's next launch copies V out (TT_EPI_BIAS)
+enum class QkvForm { SplitV8, Packed };
+
+// ---- shape checks, each called with the family's prefix ("decoder", "t5", ...) -----------------------------------------------------
+// the row ops hold a row of up to 1024 values, and the scan takes vectors up to that width (`name`: what the family calls it)
+inline int check_hidden(const char* family, int hidden, const char* name = "hidden") {
+    if (hidden <= 0 || hidden % 128 || hidden > 1024) {
+        tt_set_error("%s: %s=%d must be a multiple of 128 and <= 1024 (the scan's limit)", family, name, hidden);
+        return TT_E_UNSUPPORTED;
+    }
+    return TT_OK;
+}
+
+// grouped-query heads of width d0 (or d1, where the family's attention has two instantiations)
+inline int check_gqa_heads(const char* family, int heads, int kv_heads, int head_dim, int d0, int d1 = 0) {
+    if (head_dim != d0 && (d1 == 0 || head_dim != d1)) {
+        if (d1)
+            tt_set_error("%s: head_dim=%d not in {%d, %d}", family, head_dim, d0, d1);
+        else
+            tt_set_error("%s: head_dim=%d (supported: %d)", family, head_dim, d0);
+        return TT_E_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "%s: heads=%d is not a multiple of kv_heads=%d", family, heads,
+                 kv_heads);
+    return TT_OK;
+}
+
+// the GEMM tiles: the fused q | k | v projection is 128 columns wide, the output projection's K and the gated MLP's F 64
+inline int check_qkv_width(const char* family, int heads, int kv_heads, int head_dim, int ffn) {
+    if (((heads + 2 * kv_heads) * head_dim) % 128 || (heads * head_dim) % 64 || ffn <= 0 || ffn % 64) {
+        tt_set_error("%s: (heads + 2 kv_heads) * head_dim = %d must be a multiple of 128, heads * head_dim and ffn=%d of 64", family,
+                     (heads + 2 * kv_heads) * head_dim, ffn);
+        return TT_E_UNSUPPORTED;
+    }
+    return TT_OK;
 }
 
 // the batch arguments every packed forward takes (`family`: "a decoder", "ModernBERT"; `need`: the plan's total -- the caller

@@ -13,11 +13,11 @@ from __future__ import annotations
 import ctypes
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional
+from typing import Dict, List, Optional
 
 import torch
 
-from .encoder import DECODER_BF16_PATH, DECODER_FP16_PATH, EncoderConfig, _strip_prefix
+from .encoder import DECODER_BF16_PATH, DECODER_FP16_PATH, EncoderConfig, _FamilyWeights, _strip_prefix
 
 
 @dataclass(frozen=True)
@@ -72,26 +72,21 @@ def check_config(cfg: DecoderConfig) -> None:
         raise NotImplementedError(f"decoder embedder: heads={nq} kv_heads={nkv} head_dim={D} ffn={cfg.ffn} do not fit the GEMM tiles")
 
 
-class DecoderWeights:
+class DecoderWeights(_FamilyWeights):
     """Device-resident ``Qwen3Model`` weights for ``tt_decoder_forward`` (bf16) or ``tt_decoder_forward_f16`` (fp16): the
     projections in the element type -- q/k/v rows concatenated into one matrix, gate/up into another -- and the RMSNorm weights
     in fp32.  A ``*ForSequenceClassification`` checkpoint (``cfg.num_labels``) brings ``score.weight``: ``score_w``, fp32 [H], the
     operand of ``tt_decoder_score`` (transformers' head is ``Linear(H, 1, bias=False)``: a ``score.bias`` is refused like any
     other tensor the forward would not read)."""
 
+    _paths, _path_name = (DECODER_BF16_PATH, DECODER_FP16_PATH), "the decoder embedder"
+
     def __init__(self, cfg: DecoderConfig, state: Dict[str, torch.Tensor], device: torch.device,
                  dtype: torch.dtype = torch.bfloat16):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("DecoderWeights: the decoder embedder computes in bfloat16 or float16")
-        if device.type != "cuda":
-            raise RuntimeError("DecoderWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype)
         check_config(cfg)
         if cfg.num_labels not in (0, 1):
             raise ValueError("only single-label (sigmoid) cross-encoder heads are supported")
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = DECODER_FP16_PATH if dtype == torch.float16 else DECODER_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = _strip_prefix(state)
         names = state_names(cfg)
         missing = [n for n in names if n not in sd]
@@ -103,51 +98,26 @@ class DecoderWeights:
         extra = sorted(set(sd) - set(names) - {"lm_head.weight", "score.weight"})
         if extra:
             raise NotImplementedError(f"checkpoint carries tensors the decoder embedder does not compute: {extra[:4]}")
-
-        def mat(*names):
-            t = torch.cat([sd[n] for n in names], 0) if len(names) > 1 else sd[names[0]]
-            return self._kept(t.to(device=device, dtype=dtype).contiguous())
-
-        def vec(name):
-            return self._kept(sd[name].to(device=device, dtype=torch.float32).contiguous())
-
+        mat, vec = self._loaders(sd)
         H, D, nq, nkv, F = cfg.hidden, cfg.head_dim, cfg.heads, cfg.kv_heads, cfg.ffn
-        emb = mat("embed_tokens.weight")
-        if tuple(emb.shape) != (cfg.vocab_size, H):
-            raise ValueError(f"embed_tokens {tuple(emb.shape)} does not match {cfg}")
+        emb = mat(["embed_tokens.weight"], (cfg.vocab_size, H))
         self._layers = (_DecLayerW * max(cfg.layers, 1))()
         for i in range(cfg.layers):
             p, L = f"layers.{i}.", self._layers[i]
-            qkv = mat(*(p + f"self_attn.{n}_proj.weight" for n in ("q", "k", "v")))
-            o = mat(p + "self_attn.o_proj.weight")
-            gu = mat(p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight")
-            down = mat(p + "mlp.down_proj.weight")
-            for t, shape in ((qkv, ((nq + 2 * nkv) * D, H)), (o, (H, nq * D)), (gu, (2 * F, H)), (down, (H, F))):
-                if tuple(t.shape) != shape:
-                    raise ValueError(f"layer {i}: projection {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            L.qkv_w, L.o_w, L.gate_up_w, L.down_w = qkv.data_ptr(), o.data_ptr(), gu.data_ptr(), down.data_ptr()
-            L.q_norm, L.k_norm = vec(p + "self_attn.q_norm.weight").data_ptr(), vec(p + "self_attn.k_norm.weight").data_ptr()
-            L.attn_norm = vec(p + "input_layernorm.weight").data_ptr()
-            L.ffn_norm = vec(p + "post_attention_layernorm.weight").data_ptr()
+            L.qkv_w = mat([p + f"self_attn.{n}_proj.weight" for n in ("q", "k", "v")], ((nq + 2 * nkv) * D, H))
+            L.o_w = mat([p + "self_attn.o_proj.weight"], (H, nq * D))
+            L.gate_up_w = mat([p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], (2 * F, H))
+            L.down_w = mat([p + "mlp.down_proj.weight"], (H, F))
+            L.q_norm, L.k_norm = vec([p + "self_attn.q_norm.weight"], D), vec([p + "self_attn.k_norm.weight"], D)
+            L.attn_norm, L.ffn_norm = vec([p + "input_layernorm.weight"], H), vec([p + "post_attention_layernorm.weight"], H)
         self.struct = _DecW(hidden=H, layers=cfg.layers, heads=nq, kv_heads=nkv, head_dim=D, ffn=F, vocab=cfg.vocab_size,
-                            rms_eps=cfg.ln_eps, rope_theta=cfg.rope_theta, embed=emb.data_ptr(),
-                            layer=ctypes.cast(self._layers, POINTER(_DecLayerW)), final_norm=vec("norm.weight").data_ptr())
+                            rms_eps=cfg.ln_eps, rope_theta=cfg.rope_theta, embed=emb,
+                            layer=ctypes.cast(self._layers, POINTER(_DecLayerW)), final_norm=vec(["norm.weight"], H))
         self.score_w: Optional[torch.Tensor] = None
         if cfg.num_labels:
             if tuple(sd["score.weight"].shape) != (1, H):
                 raise ValueError(f"score.weight {tuple(sd['score.weight'].shape)} does not match {cfg} (expected (1, {H}))")
             self.score_w = self._kept(sd["score.weight"].reshape(H).to(device=device, dtype=torch.float32).contiguous())
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: DecoderConfig, seed: int = 0) -> Dict[str, torch.Tensor]:

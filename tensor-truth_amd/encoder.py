@@ -318,21 +318,26 @@ class _CheckpointWeights:
 
 
 class _FamilyWeights:
-    """What the weight holders of the post-LN packed-varlen families share (mpnet.py, deberta.py, jinabert.py, ropebert.py): the
-    dtype / device checks, the resident tensors and the two loaders of checkpoint entries.  A subclass names its two paths
-    (``_paths``: bf16, fp16) and what the dtype error calls them (``_path_name``), and builds its own ctypes struct."""
+    """What the weight holders of the packed-varlen families share -- post-LN (mpnet.py, deberta.py, jinabert.py, ropebert.py) and
+    pre-norm (decoder.py, modernbert.py, t5.py, gemma.py): the dtype / device checks, the resident tensors and the two loaders of
+    checkpoint entries.  A subclass names its paths (``_paths``: bf16, then fp16 where the family has one) and what the dtype error
+    calls them (``_path_name``), and builds its own ctypes struct."""
 
-    _paths: Tuple[EncoderPath, EncoderPath]
+    _paths: Tuple[EncoderPath, ...]
     _path_name: str
 
-    def _begin(self, cfg: EncoderConfig, device: torch.device, dtype: torch.dtype) -> None:
+    def _begin(self, cfg: EncoderConfig, device: torch.device, dtype: torch.dtype,
+               dtypes: Tuple[torch.dtype, ...] = (torch.bfloat16, torch.float16)) -> None:
+        """``dtypes``: what the family computes in, in the order of ``_paths`` (T5 and EmbeddingGemma: bfloat16 alone)."""
         name = type(self).__name__
-        if dtype not in (torch.bfloat16, torch.float16):
+        if dtype not in dtypes:
+            if len(dtypes) == 1:
+                raise NotImplementedError(f"{name}: {self._path_name} computes in bfloat16 only")
             raise ValueError(f"{name}: {self._path_name} computes in bfloat16 or float16")
         if device.type != "cuda":
             raise RuntimeError(f"{name} need a HIP device; tensor_truth_amd has no CPU path")
         self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = self._paths[dtype == torch.float16]
+        self.path = self._paths[dtypes.index(dtype)]
         self.gemm_dtype = dtype
         self._keep: List[torch.Tensor] = []
 

@@ -17,11 +17,11 @@ import json
 import os
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 
-from .encoder import GEMMA_BF16_PATH, EncoderConfig, _strip_prefix
+from .encoder import GEMMA_BF16_PATH, EncoderConfig, _FamilyWeights, _strip_prefix
 
 LAYER_KINDS = ("full_attention", "sliding_attention")
 
@@ -160,50 +160,33 @@ def embed_scale(hidden: int) -> float:
     return float(torch.tensor(float(hidden) ** 0.5).to(torch.bfloat16))
 
 
-class GemmaWeights:
+class GemmaWeights(_FamilyWeights):
     """Device-resident EmbeddingGemma weights for ``tt_gemma_forward``: the projections and the embedding table in bf16 -- q/k/v
     rows concatenated into one matrix, gate/up into another -- the norm weights in fp32 as stored (the kernels add the 1), and the
     Dense pair in fp32, transposed to [in][out] (the tail kernel's threads read them row by row)."""
 
+    _paths, _path_name = (GEMMA_BF16_PATH,), "the EmbeddingGemma path"
+
     def __init__(self, cfg: GemmaConfig, state: Dict[str, torch.Tensor], device: torch.device,
                  dtype: torch.dtype = torch.bfloat16):
-        if dtype != torch.bfloat16:
-            raise NotImplementedError("GemmaWeights: the EmbeddingGemma path computes in bfloat16 only")
-        if device.type != "cuda":
-            raise RuntimeError("GemmaWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype, dtypes=(torch.bfloat16,))
         check_config(cfg)
         if cfg.num_labels:
             raise NotImplementedError("gemma3_text: no classification head is supported")
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = GEMMA_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
-
-        def mat(shape, *names):
-            t = torch.cat([sd[n] for n in names], 0) if len(names) > 1 else sd[names[0]]
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{names[0]} ...: {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device, dtype=dtype).contiguous())
-
-        def vec(name, n):
-            t = sd[name]
-            if tuple(t.shape) != (n,):
-                raise ValueError(f"{name} {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(device=device, dtype=torch.float32).contiguous())
-
+        mat, vec = self._loaders(sd)
         H, D, nq, nkv, F = cfg.hidden, cfg.head_dim, cfg.heads, cfg.kv_heads, cfg.ffn
-        emb = mat((cfg.vocab_size, H), "embed_tokens.weight")
+        emb = mat(["embed_tokens.weight"], (cfg.vocab_size, H))
         self._layers = (_GemmaLayerW * max(cfg.layers, 1))()
         for i in range(cfg.layers):
             p, L = f"layers.{i}.", self._layers[i]
-            L.qkv_w = mat(((nq + 2 * nkv) * D, H), *(p + f"self_attn.{n}_proj.weight" for n in ("q", "k", "v"))).data_ptr()
-            L.o_w = mat((H, nq * D), p + "self_attn.o_proj.weight").data_ptr()
-            L.gate_up_w = mat((2 * F, H), p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight").data_ptr()
-            L.down_w = mat((H, F), p + "mlp.down_proj.weight").data_ptr()
-            L.q_norm, L.k_norm = vec(p + "self_attn.q_norm.weight", D).data_ptr(), vec(p + "self_attn.k_norm.weight", D).data_ptr()
+            L.qkv_w = mat([p + f"self_attn.{n}_proj.weight" for n in ("q", "k", "v")], ((nq + 2 * nkv) * D, H))
+            L.o_w = mat([p + "self_attn.o_proj.weight"], (H, nq * D))
+            L.gate_up_w = mat([p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"], (2 * F, H))
+            L.down_w = mat([p + "mlp.down_proj.weight"], (H, F))
+            L.q_norm, L.k_norm = vec([p + "self_attn.q_norm.weight"], D), vec([p + "self_attn.k_norm.weight"], D)
             for field, name in zip(("input_norm", "post_attn_norm", "pre_ffn_norm", "post_ffn_norm"), _LAYER_NORMS):
-                setattr(L, field, vec(p + name + ".weight", H).data_ptr())
+                setattr(L, field, vec([p + name + ".weight"], H))
             L.sliding = 1 if cfg.layer_types[i] == "sliding_attention" else 0
         d1, d2 = sd[DENSE_NAMES[0]], sd[DENSE_NAMES[1]]
         if d1.dim() != 2 or d2.dim() != 2 or d1.shape[1] != H or d2.shape[1] != d1.shape[0]:
@@ -215,21 +198,10 @@ class GemmaWeights:
         f32 = dict(device=device, dtype=torch.float32)
         self.struct = _GemmaW(hidden=H, layers=cfg.layers, heads=nq, kv_heads=nkv, head_dim=D, ffn=F, vocab=cfg.vocab_size,
                               window=cfg.window, rms_eps=cfg.ln_eps, global_rope_theta=cfg.global_rope_theta,
-                              local_rope_theta=cfg.local_rope_theta, embed_scale=embed_scale(H), embed=emb.data_ptr(),
-                              layer=ctypes.cast(self._layers, POINTER(_GemmaLayerW)), final_norm=vec("norm.weight", H).data_ptr(),
+                              local_rope_theta=cfg.local_rope_theta, embed_scale=embed_scale(H), embed=emb,
+                              layer=ctypes.cast(self._layers, POINTER(_GemmaLayerW)), final_norm=vec(["norm.weight"], H),
                               dense1_out=n1, dense2_out=n2, dense1_wt=self._kept(d1.to(**f32).t().contiguous()).data_ptr(),
                               dense2_wt=self._kept(d2.to(**f32).t().contiguous()).data_ptr())
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: GemmaConfig, seed: int = 0, dense: Tuple[int, int] = (0, 0)) -> Dict[str, torch.Tensor]:

@@ -14,11 +14,11 @@ from __future__ import annotations
 import ctypes
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 
-from .encoder import MODERNBERT_BF16_PATH, MODERNBERT_FP16_PATH, EncoderConfig, _strip_prefix
+from .encoder import MODERNBERT_BF16_PATH, MODERNBERT_FP16_PATH, EncoderConfig, _FamilyWeights, _strip_prefix
 
 
 @dataclass(frozen=True)
@@ -99,76 +99,47 @@ def check_state(cfg: ModernBertConfig, state: Dict[str, torch.Tensor]) -> Dict[s
     return sd
 
 
-class ModernBertWeights:
+class ModernBertWeights(_FamilyWeights):
     """Device-resident ModernBERT weights for ``tt_modernbert_forward`` (bf16) or ``tt_modernbert_forward_f16`` (fp16): the
     projections and the embedding table in the element type, the norm weights in fp32.  A ``*ForSequenceClassification``
     checkpoint (``cfg.num_labels``) brings the head, kept in fp32: ``head.dense`` transposed to [in][out] (the head kernel's lanes
     read it row by row), ``head.norm``, ``classifier.weight`` [H] and ``classifier.bias`` [1]."""
 
+    _paths, _path_name = (MODERNBERT_BF16_PATH, MODERNBERT_FP16_PATH), "the ModernBERT path"
+
     def __init__(self, cfg: ModernBertConfig, state: Dict[str, torch.Tensor], device: torch.device,
                  dtype: torch.dtype = torch.bfloat16):
-        if dtype not in (torch.bfloat16, torch.float16):
-            raise ValueError("ModernBertWeights: the ModernBERT path computes in bfloat16 or float16")
-        if device.type != "cuda":
-            raise RuntimeError("ModernBertWeights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype)
         check_config(cfg)
         if cfg.num_labels not in (0, 1):
             raise NotImplementedError("modernbert: num_labels > 1: only single-label (sigmoid) cross-encoder heads are supported")
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = MODERNBERT_FP16_PATH if dtype == torch.float16 else MODERNBERT_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
-
-        def mat(name, shape):
-            t = sd[name]
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device, dtype=dtype).contiguous())
-
-        def vec(name, n=None):
-            t = sd[name]
-            if tuple(t.shape) != (cfg.hidden if n is None else n,):
-                raise ValueError(f"{name} {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(device=device, dtype=torch.float32).contiguous())
-
+        mat, vec = self._loaders(sd)
         H, F = cfg.hidden, cfg.ffn
-        emb = mat("embeddings.tok_embeddings.weight", (cfg.vocab_size, H))
+        emb = mat(["embeddings.tok_embeddings.weight"], (cfg.vocab_size, H))
         self._layers = (_MbLayerW * max(cfg.layers, 1))()
         for i in range(cfg.layers):
             p, L = f"layers.{i}.", self._layers[i]
-            L.qkv_w = mat(p + "attn.Wqkv.weight", (3 * H, H)).data_ptr()
-            L.o_w = mat(p + "attn.Wo.weight", (H, H)).data_ptr()
-            L.wi_w = mat(p + "mlp.Wi.weight", (2 * F, H)).data_ptr()
-            L.wo_w = mat(p + "mlp.Wo.weight", (H, F)).data_ptr()
-            L.attn_norm = vec(p + "attn_norm.weight").data_ptr() if i else None
-            L.mlp_norm = vec(p + "mlp_norm.weight").data_ptr()
+            L.qkv_w = mat([p + "attn.Wqkv.weight"], (3 * H, H))
+            L.o_w = mat([p + "attn.Wo.weight"], (H, H))
+            L.wi_w = mat([p + "mlp.Wi.weight"], (2 * F, H))
+            L.wo_w = mat([p + "mlp.Wo.weight"], (H, F))
+            L.attn_norm = vec([p + "attn_norm.weight"], H) if i else None
+            L.mlp_norm = vec([p + "mlp_norm.weight"], H)
             L.sliding = 1 if cfg.layer_types[i] == "sliding_attention" else 0
         self.struct = _MbW(hidden=H, layers=cfg.layers, heads=cfg.heads, ffn=F, vocab=cfg.vocab_size,
                            local_attention=cfg.local_attention, norm_eps=cfg.ln_eps, global_rope_theta=cfg.global_rope_theta,
-                           local_rope_theta=cfg.local_rope_theta, embed=emb.data_ptr(),
-                           emb_norm=vec("embeddings.norm.weight").data_ptr(),
-                           layer=ctypes.cast(self._layers, POINTER(_MbLayerW)), final_norm=vec("final_norm.weight").data_ptr())
+                           local_rope_theta=cfg.local_rope_theta, embed=emb, emb_norm=vec(["embeddings.norm.weight"], H),
+                           layer=ctypes.cast(self._layers, POINTER(_MbLayerW)), final_norm=vec(["final_norm.weight"], H))
         if cfg.num_labels:
             dense, cls = sd["head.dense.weight"], sd["classifier.weight"]
             if tuple(dense.shape) != (H, H) or tuple(cls.shape) != (1, H) or tuple(sd["classifier.bias"].shape) != (1,):
                 raise ValueError(f"head.dense {tuple(dense.shape)} / classifier {tuple(cls.shape)} do not match {cfg} (one label)")
             f32 = dict(device=device, dtype=torch.float32)
             self.struct.head_dense_wt = self._kept(dense.to(**f32).t().contiguous()).data_ptr()
-            self.struct.head_norm = vec("head.norm.weight").data_ptr()
+            self.struct.head_norm = vec(["head.norm.weight"], H)
             self.struct.cls_w = self._kept(cls.reshape(H).to(**f32).contiguous()).data_ptr()
-            self.struct.cls_b = vec("classifier.bias", 1).data_ptr()
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
+            self.struct.cls_b = vec(["classifier.bias"], 1)
 
 
 def synthetic_state(cfg: ModernBertConfig, seed: int = 0) -> Dict[str, torch.Tensor]:

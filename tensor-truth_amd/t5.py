@@ -23,12 +23,12 @@ import json
 import os
 from ctypes import POINTER, Structure, c_float, c_int32, c_void_p
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from .encoder import T5_BF16_PATH, EncoderConfig
+from .encoder import T5_BF16_PATH, EncoderConfig, _FamilyWeights
 from .mpnet import MAX_DISTANCE, NUM_BUCKETS, distance_table
 
 MLP_KINDS = {"relu": 0, "gated-gelu": 1}     # feed_forward_proj -> tt_t5_weights.mlp_kind
@@ -257,55 +257,42 @@ def pooled_ranges(seq_start: np.ndarray, seq_len: np.ndarray, skip: int) -> Tupl
     return starts.astype(np.int32), lens.astype(np.int32)
 
 
-class T5Weights:
+class T5Weights(_FamilyWeights):
     """Device-resident T5 encoder weights for ``tt_t5_forward``: the projections and the embedding table in bf16 -- q (times 8), k
     and v rows concatenated into one matrix, wi_0 / wi_1 of the gated form into another -- the norm weights in fp32 holding the
     values their bf16 rounding has (transformers multiplies by the bf16 weight), block 0's bias table and the per-head distance
     table built from it in fp32, and the Dense module in fp32, transposed to [in][out] (the tail kernel's threads read it row by
     row)."""
 
+    _paths, _path_name = (T5_BF16_PATH,), "the T5 path"
+
     def __init__(self, cfg: T5Config, state: Dict[str, torch.Tensor], device: torch.device, dtype: torch.dtype = torch.bfloat16):
-        if dtype != torch.bfloat16:
-            raise NotImplementedError("T5Weights: the T5 path computes in bfloat16 only")
-        if device.type != "cuda":
-            raise RuntimeError("T5Weights need a HIP device; tensor_truth_amd has no CPU path")
+        self._begin(cfg, device, dtype, dtypes=(torch.bfloat16,))
         check_config(cfg)
-        self.cfg, self.device, self.dtype = cfg, device, dtype
-        self.path = T5_BF16_PATH
-        self.gemm_dtype = dtype
-        self._keep: List[torch.Tensor] = []
         sd = check_state(cfg, state)
         H, F = cfg.hidden, cfg.ffn
+        class Rounded:
+            """What the loaders read: every tensor rounded to bf16 first -- the norm weights then hold their bf16 values in fp32 --
+            and the q rows times 8 (a power of two: exact)."""
+            def __getitem__(self, name):
+                t = sd[name].to(dtype)
+                return t * 8.0 if name.endswith("SelfAttention.q.weight") else t
 
-        def mat(shape, *names, scale_first=None):
-            parts = [sd[n].to(dtype) for n in names]
-            if scale_first is not None:
-                parts[0] = parts[0] * scale_first      # a power of two: exact
-            t = torch.cat(parts, 0) if len(parts) > 1 else parts[0]
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{names[0]} ...: {tuple(t.shape)} does not match {cfg} (expected {shape})")
-            return self._kept(t.to(device=device).contiguous())
-
-        def vec(name, n):
-            t = sd[name]
-            if tuple(t.shape) != (n,):
-                raise ValueError(f"{name} {tuple(t.shape)} does not match {cfg}")
-            return self._kept(t.to(dtype).to(device=device, dtype=torch.float32).contiguous())
-
-        emb = mat((cfg.vocab_size, H), _EMBED)
+        mat, vec = self._loaders(Rounded())
+        emb = mat([_EMBED], (cfg.vocab_size, H))
         self._layers = (_T5LayerW * max(cfg.layers, 1))()
         for i in range(cfg.layers):
             p, L = f"encoder.block.{i}.", self._layers[i]
             a, m = p + "layer.0.SelfAttention.", p + "layer.1.DenseReluDense."
-            L.ln_attn = vec(p + "layer.0.layer_norm.weight", H).data_ptr()
-            L.qkv_w = mat((3 * H, H), a + "q.weight", a + "k.weight", a + "v.weight", scale_first=8.0).data_ptr()
-            L.o_w = mat((H, H), a + "o.weight").data_ptr()
-            L.ln_ffn = vec(p + "layer.1.layer_norm.weight", H).data_ptr()
+            L.ln_attn = vec([p + "layer.0.layer_norm.weight"], H)
+            L.qkv_w = mat([a + "q.weight", a + "k.weight", a + "v.weight"], (3 * H, H))
+            L.o_w = mat([a + "o.weight"], (H, H))
+            L.ln_ffn = vec([p + "layer.1.layer_norm.weight"], H)
             if cfg.mlp_kind == 1:
-                L.wi = mat((2 * F, H), m + "wi_0.weight", m + "wi_1.weight").data_ptr()
+                L.wi = mat([m + "wi_0.weight", m + "wi_1.weight"], (2 * F, H))
             else:
-                L.wi = mat((F, H), m + "wi.weight").data_ptr()
-            L.wo = mat((H, F), m + "wo.weight").data_ptr()
+                L.wi = mat([m + "wi.weight"], (F, H))
+            L.wo = mat([m + "wo.weight"], (H, F))
         rel = sd[_REL_BIAS]
         if tuple(rel.shape) != (NUM_BUCKETS, cfg.heads):
             raise ValueError(f"{_REL_BIAS} {tuple(rel.shape)} does not match {cfg} (expected {(NUM_BUCKETS, cfg.heads)})")
@@ -323,20 +310,9 @@ class T5Weights:
         self.out_dim = dense_out or H
         self.struct = _T5W(d_model=H, layers=cfg.layers, heads=cfg.heads, d_kv=cfg.d_kv, d_ff=F, vocab=cfg.vocab_size,
                            mlp_kind=cfg.mlp_kind, num_buckets=cfg.num_buckets, max_distance=cfg.max_distance, eps=cfg.ln_eps,
-                           embed=emb.data_ptr(), layer=ctypes.cast(self._layers, POINTER(_T5LayerW)),
-                           final_norm=vec("encoder.final_layer_norm.weight", H).data_ptr(), rel_bias=rel.data_ptr(),
+                           embed=emb, layer=ctypes.cast(self._layers, POINTER(_T5LayerW)),
+                           final_norm=vec(["encoder.final_layer_norm.weight"], H), rel_bias=rel.data_ptr(),
                            bias_table=self.bias_table.data_ptr(), dense_out=dense_out, dense_wt=dense_wt)
-
-    def _kept(self, t: torch.Tensor) -> torch.Tensor:
-        self._keep.append(t)
-        return t
-
-    def parameters(self) -> Iterable[torch.Tensor]:
-        """For ModelManager-style memory accounting (reference model_manager.py:477-507)."""
-        return iter(self._keep)
-
-    def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self._keep)
 
 
 def synthetic_state(cfg: T5Config, seed: int = 0, dense: Optional[int] = None) -> Dict[str, torch.Tensor]:
