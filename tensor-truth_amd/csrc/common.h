@@ -31,7 +31,7 @@
 #ifndef TT_DIAG
 #define TT_DIAG 0
 #endif
-// Round 5: the A/B switches of measured-and-rejected variants (TT_GEMM_XP, TT_GEMM_VARIANT, TT_ATT_WAVES, TT_SCAN_GEMM_*, ...) are
+// Round 5: the A/B switches of measured-and-rejected variants (TT_GEMM_SN, TT_ATT_WAVES, TT_SCAN_GEMM_*, ...) are
 // diagnostic-only too: the product library reads NO environment variable (tests/test_lib_abi.py greps its strings), every switch
 // is its default as a compile-time constant, and the instantiations only a non-default value could reach are not linked.
 #if TT_DIAG

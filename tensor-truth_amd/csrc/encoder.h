@@ -1,12 +1,7 @@
 // Internal interfaces of the encoder kernels (gemm.hip, attention.hip, rowops.hip, encoder_api.hip).
 #pragma once
 #include "common.h"
-
-enum { TT_EPI_BIAS = 0, TT_EPI_GELU = 1, TT_EPI_RESIDUAL = 2, TT_EPI_TANH = 3, TT_EPI_QKV = 4,
-       TT_EPI_VT = 5 /* internal: whole output stored transposed into vt (the V third of a QKV projection) */,
-       TT_EPI_SCAN = 6 /* internal: similarity scan -- A = corpus rows, W = 256 queries, nothing is stored: scores >= the
-                          query's threshold (bias[n]) are appended to per-query candidate lists (scan_api.hip) */,
-       TT_EPI_RELU = 7 /* max(acc + bias, 0): the up-projection of a ReLU MLP (T5 encoders, t5.hip) */ };
+#include "gemm_plan.h"   // the TT_EPI_* epilogue ids
 
 struct GemmParams {
     const uint16_t* A;        // [M][lda] bf16
@@ -28,7 +23,8 @@ struct GemmParams {
     float c8_inv_scale;
     int nt_store;             // whole-line output stores issued as streaming stores (set by the launcher)
     int sn;                   // super-tile width in N-tiles (32 tiles per super-tile: sm = 32 / sn); set by the launcher
-    int xp;                   // experiment switches of the persistent kernel (TT_GEMM_XP; see gemm.hip launch())
+    int scan_wave_lists;      // TT_EPI_SCAN, one-tile kernel: 1 = survivors go to wave-private LDS lists (set by tt_scan_gemm_launch).
+                              // 0 or 1 only: gemm_kernel_v3 still tests bit 17 of this word on every A-tile address (gemm.hip stage_half)
     // TT_EPI_SCAN: candidate lists of the filter pass (same layout as ScanParams' shared lists)
     int32_t* scan_cnt;        // [N] running candidate count per query (may exceed scan_cap)
     float* scan_scores;       // [N][scan_cap]
@@ -71,19 +67,6 @@ struct GemmParams {
     const uint8_t* a_scales;  // [M / 256][K / 128][1024]
     const uint8_t* w_scales;  // [N / 256][2 K / 128][1024]: the w_lo8 part's K / 128 chunks, then the w_x8 part's (exponents - 11)
     uint8_t* c_scales;        // GELU epilogue: the output's scales, tiled for a consumer with K = N
-#if TT_DIAG
-    // ---- LayerNorm-folding EXPERIMENT (round 6; diagnostic library only: tools/ln_fold_bench, profiles/r06_ln_folding_ab.log) ----
-    // 1 = consumer epilogue (bias / GELU; the A operand is the RAW pre-LayerNorm sum, W carries gamma):
-    //         out[m][n] = lnf_rows[m].rstd * acc + lnf_rows[m].nmr * lnf_c0[n] + bias[n]        (lnf_c0 = column sums of the folded W)
-    // 2 = producer epilogue (residual): the residual tile is the RAW pre-LayerNorm sum y of the previous block and LayerNorm(y) is
-    //     rebuilt on the fly, res = y * (rstd * gamma[n]) + (nmr * gamma[n] + beta[n])  (lnf_c0 = gamma, lnf_c1 = beta); the epilogue
-    //     also emits, per output row and 64-column strip, (sum, sum of squares) of the bf16-rounded outputs -> lnf_part[m][N / 64][2]
-    int lnf;
-    const float* lnf_rows;    // [M][2]: rstd, -mu * rstd of the rows of the folded LayerNorm's input
-    const float* lnf_c0;      // [N]
-    const float* lnf_c1;      // [N]
-    float* lnf_part;          // [M][N / 64][2]
-#endif
 };
 // Filter pass of the similarity scan for 65..256 queries per pass as a 256x256x64-tiled MFMA contraction (gemm.hip):
 // corpus [rows][dim] bf16 with rows a multiple of 256, queries256 [256][dim] bf16 (rows beyond the batch zero),

@@ -369,10 +369,6 @@ int tt_gemm_bf16(const void* a, const void* w, const float* bias, const void* re
     g.A = (const uint16_t*)a; g.lda = k; g.W = (const uint16_t*)w; g.bias = bias;
     g.residual = (const uint16_t*)residual; g.ldr = n; g.C = (uint16_t*)c; g.ldc = n;
     g.M = m; g.N = n; g.K = k;
-    // timing experiment only (wrong results; diagnostic library only): every output row lands on row 0 / every A row-block reads block 0
-    static const int dbg = TT_DIAG_ENV_INT("TT_GEMM_DEBUG_TRAFFIC", 0);
-    if (dbg & 1) g.ldc = 0;
-    if (dbg & 2) g.lda = 0;
     return tt_gemm_launch(g, epilogue, (hipStream_t)stream);
 }
 
@@ -428,26 +424,6 @@ __attribute__((visibility("default"))) int tt_attention_debug_stamps(const void*
     a.max_len = max_len; a.scale = 1.0f / sqrtf((float)head_dim);
     a.dbg = (unsigned long long*)stamps;
     return tt_attention_launch(a, (hipStream_t)stream);
-}
-
-// diagnostic only (not in tt_hip.h): the LayerNorm-folding experiment's epilogues (GemmParams.lnf; tools/ln_fold_bench)
-__attribute__((visibility("default"))) int tt_gemm_debug_lnfold(const void* a, const void* w, const float* bias, const void* residual,
-                                                                void* c, int m, int n, int k, int epilogue, int lnf, const float* rows,
-                                                                const float* c0, const float* c1, float* part, void* stream) {
-    GemmParams g{};
-    g.A = (const uint16_t*)a; g.lda = k; g.W = (const uint16_t*)w; g.bias = bias; g.residual = (const uint16_t*)residual; g.ldr = n;
-    g.C = (uint16_t*)c; g.ldc = n; g.M = m; g.N = n; g.K = k;
-    g.lnf = lnf; g.lnf_rows = rows; g.lnf_c0 = c0; g.lnf_c1 = c1; g.lnf_part = part;
-    return tt_gemm_launch(g, epilogue, (hipStream_t)stream);
-}
-
-// diagnostic only (not in tt_hip.h): run the bias GEMM with a stamp buffer in GemmParams.vt
-__attribute__((visibility("default"))) int tt_gemm_debug_stamps(const void* a, const void* w, const float* bias, void* c, int m, int n, int k, void* stamps,
-                         void* stream) {
-    GemmParams g{};
-    g.A = (const uint16_t*)a; g.lda = k; g.W = (const uint16_t*)w; g.bias = bias; g.C = (uint16_t*)c; g.ldc = n;
-    g.M = m; g.N = n; g.K = k; g.vt = (uint16_t*)stamps;
-    return tt_gemm_launch(g, TT_EPI_BIAS, (hipStream_t)stream);
 }
 
 #endif

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "encoder.h"
+#include "gemm_plan.h"
 #include "f16c.h"
 
 namespace {
@@ -117,9 +118,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
 // lanes of even 16-lane rows their right-hand neighbour's 4 columns of m-tile 2j and the lanes of
 // odd rows their left-hand neighbour's 4 columns of m-tile 2j+1: every lane then owns 8 consecutive
 // columns of ONE row -> one 16-B store (and 16-B residual load) per pair of tiles.
-// CM (experiment, TT_GEMM_ABLATE=7): store feature-chunk-major, C[(n / 8) * M + m][8] -- every lane's 16-byte chunk goes out
-// directly (256-byte runs per 16-lane group), no LDS transposition; times what a chunk-major activation layout would cost.
-template <int EPI, int NT, int MT, bool CM = false>
+template <int EPI, int NT, int MT>
 __device__ __forceinline__ void gemm_epilogue_wide(const GemmParams& p, f32x4 (&acc)[NT][MT], int mw, int nw, int lane) {
     static_assert(MT % 2 == 0, "m-tiles are processed in pairs");
     const int g = lane >> 4;           // 16-lane row: columns 4g..4g+3 of the tile before the swap
@@ -178,8 +177,7 @@ __device__ __forceinline__ void gemm_epilogue_wide(const GemmParams& p, f32x4 (&
             uint4 o;
             o.x = pack_e2(v[0], v[1]); o.y = pack_e2(v[2], v[3]);
             o.z = pack_e2(v[4], v[5]); o.w = pack_e2(v[6], v[7]);
-            if constexpr (CM) *reinterpret_cast<uint4*>(p.C + ((size_t)(n >> 3) * p.M + m) * 8) = o;
-            else *reinterpret_cast<uint4*>(p.C + (size_t)m * p.ldc + n) = o;
+            *reinterpret_cast<uint4*>(p.C + (size_t)m * p.ldc + n) = o;
         }
     }
 }
@@ -373,15 +371,19 @@ __device__ __forceinline__ void glds16(const void* base, uint32_t voff, uint32_t
 // One half-tile = 2 global->LDS copies per wave.  The source is addressed as a wave-uniform base
 // (SGPR pair: operand + first row of the half + K offset) plus a per-lane 32-bit byte offset that is
 // constant for the whole kernel (voff[j]), so a copy costs no vector address arithmetic.
-template <int OPERAND, int ES = 2>
+// A0: gemm_kernel_v3 keeps the run-time test of the closed A-miss experiment on every A-tile address -- bit 17 of the parameter word that
+// is now scan_wave_lists, never set: every tile reads its own rows.  Without the test the compiler schedules the one-tile kernels' scalar
+// address arithmetic differently and the K = 1024 shapes at M = 473600 measured 0.5-0.7 % slower (profiles/gemm_prune_ab.log); with it their
+// code is the code that was measured all along.  gemm_kernel_p stayed inside its bound without it.
+template <int OPERAND, int ES = 2, bool A0 = false>
 __device__ __forceinline__ void stage_half(const GemmParams& p, char* smem, int half, int buf, int tile, int wave,
                                            const uint32_t (&voff)[2], int m0, int n0, int tile_bytes = 128) {
     char* dst = smem + slot_off(OPERAND, half, buf);
     // ES = bytes per element (2 bf16, 1 fp8); a K-tile is 128 bytes of every row either way (split planes: 64 bytes of the
     // hi plane + 64 of the lo plane, tile_bytes = 64; the plane offset is part of the per-lane voff)
     const char* base;
-    // (p.xp bit 17, TT_GEMM_DEBUG_A0: every tile reads the A rows of row-block 0 -- wrong results, all A reads L2 hits: what the A misses cost)
-    if constexpr (OPERAND == 0) base = reinterpret_cast<const char*>(p.A) + ((size_t)(((p.xp & 0x20000) ? 0 : m0) + half * 128) * p.lda) * ES + tile * tile_bytes;
+    if constexpr (OPERAND == 0 && A0) base = reinterpret_cast<const char*>(p.A) + ((size_t)(((p.scan_wave_lists & 0x20000) ? 0 : m0) + half * 128) * p.lda) * ES + tile * tile_bytes;
+    else if constexpr (OPERAND == 0) base = reinterpret_cast<const char*>(p.A) + ((size_t)(m0 + half * 128) * p.lda) * ES + tile * tile_bytes;
     else base = reinterpret_cast<const char*>(p.W) + ((size_t)(n0 + half * 32) * (p.ldw ? p.ldw : p.K)) * ES + tile * tile_bytes;   // see w_row_of()
     // keep the base in SGPRs (otherwise hipcc folds it into per-lane 64-bit VGPR addresses and
     // pays two 64-bit vector adds per copy)
@@ -445,7 +447,7 @@ __device__ __forceinline__ float lds_read32_sync(uint32_t addr) {
 template <int EPI, bool STAGE, bool FP8, class Next>
 __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2][2][2][4], const char* smem, int bias_off,
                                              int scale_off, int m0, int n0, int wm, int wn, int wave, int lane, bool has_next,
-                                             Next issue_next, int lnf_col_off = 0, int lnf_row_off = 0) {
+                                             Next issue_next) {
     const int g = lane >> 4;
     const bool odd = (g & 1) != 0;
     const int ncol = wn * 64 + (g & ~1) * 4;           // + qn*32 + nt*16: first of this lane's 8 columns
@@ -476,26 +478,6 @@ __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2
             bias[i >> 2][(i >> 1) & 1][i & 1] = float4{__uint_as_float(b[i].x), __uint_as_float(b[i].y), __uint_as_float(b[i].z),
                                                        __uint_as_float(b[i].w)};
     }
-#if TT_DIAG
-    // LayerNorm-folding experiment (GemmParams.lnf): the column strip(s) and the tile's row statistics sit in LDS behind the bias
-    // strips (staged in the prologue like them); consumer form: the column sums of the folded weight, kept in registers like the bias
-    const int lnf = (FP8 || EPI == TT_EPI_TANH) ? 0 : p.lnf;
-    float4 lcs[2][2][2];
-    if (lnf == 1) {
-        const uint32_t caddr = lds0 + lnf_col_off + ncol * 4;
-        u32x4 b[8];
-        b[0] = lds_read128_async<0>(caddr);        b[1] = lds_read128_async<16>(caddr);
-        b[2] = lds_read128_async<64>(caddr);       b[3] = lds_read128_async<80>(caddr);
-        b[4] = lds_read128_async<128>(caddr);      b[5] = lds_read128_async<144>(caddr);
-        b[6] = lds_read128_async<192>(caddr);      b[7] = lds_read128_async<208>(caddr);
-        lds_wait(b[0], b[1], b[2], b[3]);
-        lds_wait(b[4], b[5], b[6], b[7]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            lcs[i >> 2][(i >> 1) & 1][i & 1] = float4{__uint_as_float(b[i].x), __uint_as_float(b[i].y), __uint_as_float(b[i].z),
-                                                      __uint_as_float(b[i].w)};
-    }
-#endif
     float4 wsc[2][2][2];
     float asc[2][2];   // [qm][pr]: this lane's output row of the block
     if constexpr (FP8) {
@@ -548,15 +530,6 @@ __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2
                 lds_wait(res[0][0], res[0][1], res[1][0], res[1][1]);
                 if (has_next) issue_next(qm * 2 + pr);
             }
-#if TT_DIAG
-            float lrs = 1.f, lnm = 0.f, lsum = 0.f, lsq = 0.f;       // this lane's row of the block: rstd, -mu rstd; output partials
-            if (lnf) {
-                const uint32_t ra = lds0 + lnf_row_off + (uint32_t)(qm * 128 + mrow + (pr * 2 + (odd ? 1 : 0)) * 16) * 8u;
-                // (two 32-bit reads into registers of their own: read as one 64-bit pair, broadcasting the pair's HIGH dword into a packed-f32
-                // FMA is the op_sel form csrc/check_isa.py bans -- profiles/r03_pk_mfma_hazard.log)
-                asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:4\n\ts_waitcnt lgkmcnt(0)" : "=&v"(lrs), "=&v"(lnm) : "v"(ra));
-            }
-#endif
 #pragma unroll
             for (int qn = 0; qn < 2; ++qn)
 #pragma unroll
@@ -571,15 +544,6 @@ __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2
                         v[4 + k] = __uint_as_float(r[1]);
                     }
                     const float4 b0 = bias[qn][nt][0], b1 = bias[qn][nt][1];
-#if TT_DIAG
-                    if (lnf == 1) {          // consumer: rstd acc + (nmr cs + bias)
-                        const float4 c0 = lcs[qn][nt][0], c1 = lcs[qn][nt][1];
-                        v[0] = fmaf(v[0], lrs, fmaf(lnm, c0.x, b0.x)); v[1] = fmaf(v[1], lrs, fmaf(lnm, c0.y, b0.y));
-                        v[2] = fmaf(v[2], lrs, fmaf(lnm, c0.z, b0.z)); v[3] = fmaf(v[3], lrs, fmaf(lnm, c0.w, b0.w));
-                        v[4] = fmaf(v[4], lrs, fmaf(lnm, c1.x, b1.x)); v[5] = fmaf(v[5], lrs, fmaf(lnm, c1.y, b1.y));
-                        v[6] = fmaf(v[6], lrs, fmaf(lnm, c1.z, b1.z)); v[7] = fmaf(v[7], lrs, fmaf(lnm, c1.w, b1.w));
-                    } else
-#endif
                     if constexpr (FP8) {
                         const float sa = asc[qm][pr];
                         const float4 s0 = wsc[qn][nt][0], s1 = wsc[qn][nt][1];
@@ -605,57 +569,22 @@ __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2
                         for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
                     } else if constexpr (EPI == TT_EPI_RESIDUAL) {
                         const u32x4 r = res[qn][nt];
-#if TT_DIAG
-                        if (lnf == 2) {      // producer: the residual tile is the raw pre-LayerNorm sum; LayerNorm rebuilt in fp32
-                            const uint32_t ga = lds0 + lnf_col_off + (uint32_t)(ncol + qn * 32 + nt * 16) * 4u;
-                            u32x4 g0 = lds_read128_async<0>(ga), g1 = lds_read128_async<16>(ga);
-                            u32x4 e0 = lds_read128_async<1024>(ga), e1 = lds_read128_async<1040>(ga);
-                            lds_wait(g0, g1, e0, e1);
-                            const float gm[8] = {__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z), __uint_as_float(g0.w),
-                                                 __uint_as_float(g1.x), __uint_as_float(g1.y), __uint_as_float(g1.z), __uint_as_float(g1.w)};
-                            const float bt[8] = {__uint_as_float(e0.x), __uint_as_float(e0.y), __uint_as_float(e0.z), __uint_as_float(e0.w),
-                                                 __uint_as_float(e1.x), __uint_as_float(e1.y), __uint_as_float(e1.z), __uint_as_float(e1.w)};
-                            const float y[8] = {elo(r.x), ehi(r.x), elo(r.y), ehi(r.y), elo(r.z), ehi(r.z), elo(r.w), ehi(r.w)};
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) v[k] += fmaf(y[k], lrs * gm[k], fmaf(lnm, gm[k], bt[k]));
-                        } else
-#endif
-                        {
                         v[0] += elo(r.x); v[1] += ehi(r.x);
                         v[2] += elo(r.y); v[3] += ehi(r.y);
                         v[4] += elo(r.z); v[5] += ehi(r.z);
                         v[6] += elo(r.w); v[7] += ehi(r.w);
-                        }
                     }
                     const int m = m0 + qm * 128 + mrow + (pr * 2 + (odd ? 1 : 0)) * 16;
                     const int n = n0 + qn * 32 + nt * 16 + ncol;
                     uint4 o;
                     o.x = pack_e2(v[0], v[1]); o.y = pack_e2(v[2], v[3]);
                     o.z = pack_e2(v[4], v[5]); o.w = pack_e2(v[6], v[7]);
-#if TT_DIAG
-                    if (lnf == 2) {          // statistics of the values the consumer will read: the bf16-rounded outputs
-                        const float w8[8] = {elo(o.x), ehi(o.x), elo(o.y), ehi(o.y), elo(o.z), ehi(o.z), elo(o.w), ehi(o.w)};
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) { lsum += w8[k]; lsq = fmaf(w8[k], w8[k], lsq); }
-                    }
-#endif
                     if constexpr (STAGE) {
                         lds_write128_async(raddr[qn][nt] + kOffB[qm * 2 + pr], o);
                     } else {
                         *reinterpret_cast<uint4*>(p.C + (size_t)m * p.ldc + n) = o;
                     }
                 }
-#if TT_DIAG
-            if (lnf == 2) {
-                // the row's 64 columns of this wave sit in two lanes (g and g ^ 2: lanes 32 apart)
-                lsum += __shfl_xor(lsum, 32, 64);
-                lsq += __shfl_xor(lsq, 32, 64);
-                if ((g >> 1) == 0) {
-                    const int m = m0 + qm * 128 + mrow + (pr * 2 + (odd ? 1 : 0)) * 16;
-                    *reinterpret_cast<float2*>(p.lnf_part + ((size_t)m * (p.N >> 6) + (size_t)((n0 >> 6) + wn)) * 2) = float2{lsum, lsq};
-                }
-            }
-#endif
             if constexpr (STAGE) {
                 // the block's 32 rows x 128 B now sit row-major in this wave's two private pieces: read them back a
                 // row per 8 lanes and store whole 128-byte lines instead of 32-byte runs
@@ -666,15 +595,8 @@ __device__ __forceinline__ void epilogue_all(const GemmParams& p, f32x4 (&acc)[2
                 t[2] = lds_read128_async<0>(saddr[0] + kOffB[qm * 2 + pr] + 4 * kHalf);
                 t[3] = lds_read128_async<0>(saddr[1] + kOffB[qm * 2 + pr] + 4 * kHalf);
                 lds_wait(t[0], t[1], t[2], t[3]);
-                size_t crow = (size_t)(m0 + qm * 128 + wm * 64 + pr * 32 + (lane >> 3)) * p.ldc + n0 + wn * 64 + (lane & 7) * 8;
-#if TT_DIAG
-                // experiment (TT_GEMM_HEAD_MAJOR=1, diagnostic library): the output head-major, C[n / 64][M][64] -- a wave's 32 rows
-                // x 128 bytes become ONE 4-KiB run instead of 32 lines 2 N bytes apart (profiles/r04_gemm_writeback_ab.log)
-                if (p.xp & 0x40000) crow = ((size_t)((n0 + wn * 64) >> 6) * p.M + (m0 + qm * 128 + wm * 64 + pr * 32 + (lane >> 3))) * 64 + (lane & 7) * 8;
-                const size_t rstride = (p.xp & 0x40000) ? 64 : (size_t)p.ldc;
-#else
+                const size_t crow = (size_t)(m0 + qm * 128 + wm * 64 + pr * 32 + (lane >> 3)) * p.ldc + n0 + wn * 64 + (lane & 7) * 8;
                 const size_t rstride = (size_t)p.ldc;
-#endif
                 if (p.C8) {
                     // e4m3 output: quantise the bf16-rounded values with the tensor's static scale, 8 bytes per lane
                     // (64 contiguous bytes per row and instruction)
@@ -1168,7 +1090,7 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-template <int EPI, int SLOTS, bool FP8 = false, bool X3 = false, bool XC = false, bool RP = false>
+template <int EPI, bool FP8 = false, bool X3 = false, bool XC = false, bool RP = false>
 __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
     static_assert(!(FP8 && X3), "split-bf16 operands are bf16");
     static_assert(!XC || (!FP8 && !X3 && kF16), "f16c operands: the fp16 instantiation, no other operand mode");
@@ -1243,20 +1165,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
         voffW[j] = (uint32_t)wr * (uint32_t)(p.ldw ? p.ldw : p.K) * (uint32_t)ES + coff;
     }
 
-    unsigned long long* dbg0 = reinterpret_cast<unsigned long long*>(p.vt);
-    auto cstamp = [&](int slot) {
-        if constexpr (SLOTS == 46) {
-            if ((int)blockIdx.x == (p.xp >> 20) && tid == 0 && dbg0) dbg0[20 + slot] = __builtin_amdgcn_s_memtime();   // stamped workgroup: TT_GEMM_STAMP_BLOCK
-            // every workgroup: entry / exit time and where it ran (tools/gemm_stamps: dispatch gaps per CU)
-            if ((slot == 0 || slot == 3) && tid == 0 && dbg0) {
-                unsigned long long* rec = dbg0 + 256 + (size_t)blockIdx.x * 4;
-                rec[slot == 0 ? 0 : 1] = __builtin_amdgcn_s_memtime();
-                if (slot == 0)
-                    rec[2] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) |   // HW_REG_XCC_ID
-                             (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));              // HW_REG_HW_ID
-            }
-        }
-    };
     // residual tile -> LDS, four parts of (2 pieces x 2 copies) per wave; layout: see epilogue_all
     constexpr bool kResLds = (EPI == TT_EPI_RESIDUAL) && !X3 && !XC;   // (split-bf16 / f16c: the residual is fp32, read by the epilogue)
     uint32_t voffR[2] = {0u, 0u};
@@ -1286,11 +1194,10 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
         }
     };
 
-    cstamp(0);
     if constexpr (EPI == TT_EPI_SCAN) {
-        // survivor counts of this tile: the shared list's, or (wave-private lists, p.xp bit 16) one per wave
+        // survivor counts of this tile: the shared list's, or (p.scan_wave_lists) one per wave
         if (tid == 0) *reinterpret_cast<int*>(smem + kScanHitOff) = 0;
-        if ((p.xp & 0x10000) && lane == 0) *reinterpret_cast<int*>(smem + kScanHitOff + wave * 1024) = 0;
+        if (p.scan_wave_lists && lane == 0) *reinterpret_cast<int*>(smem + kScanHitOff + wave * 1024) = 0;
     }
     // bias strip of this tile (256 floats = one 1-KiB copy), oldest operation of wave 0's queue
     if (wave == 0) {
@@ -1305,24 +1212,13 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
         if (wave == 1) glds16(p.a_scale + m0, lane * 16, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + kScaleOff);
         if (wave == 2) glds16(p.w_scale + n0, lane * 16, (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + kScaleOff + 1024);
     }
-#if TT_DIAG
-    if constexpr (!FP8 && !X3 && !XC && (EPI == TT_EPI_BIAS || EPI == TT_EPI_GELU || EPI == TT_EPI_RESIDUAL)) {
-        if (p.lnf) {      // LayerNorm-folding experiment: column strip(s) + the tile's 256 row statistics, oldest operations of their waves
-            const uint32_t l0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-            if (wave == 1) glds16(p.lnf_c0 + n0, lane * 16, l0 + kScaleOff);
-            if (wave == 2 && p.lnf == 2) glds16(p.lnf_c1 + n0, lane * 16, l0 + kScaleOff + 1024);
-            if (wave == 3) glds16(p.lnf_rows + (size_t)m0 * 2, lane * 16, l0 + kScaleOff + 2048);
-            if (wave == 4) glds16(p.lnf_rows + (size_t)(m0 + 128) * 2, lane * 16, l0 + kScaleOff + 3072);
-        }
-    }
-#endif
     // ---- prologue: tile 0 complete, tile 1 without its A-hi (issued in L1(0)); same order as steady state
-    stage_half<0, ES>(p, smem, 0, 0, 0, wave, voffA, m0, n0, TB);
+    stage_half<0, ES, true>(p, smem, 0, 0, 0, wave, voffA, m0, n0, TB);
     stage_half<1, ES>(p, smem, 0, 0, 0, wave, voffW, m0, n0, TB);
     stage_half<1, ES>(p, smem, 1, 0, 0, wave, voffW, m0, n0, TB);
-    stage_half<0, ES>(p, smem, 1, 0, 0, wave, voffA, m0, n0, TB);
+    stage_half<0, ES, true>(p, smem, 1, 0, 0, wave, voffA, m0, n0, TB);
     if (nk > 1) {
-        stage_half<0, ES>(p, smem, 0, 1, tile_a(1), wave, voffA, m0, n0, TB);
+        stage_half<0, ES, true>(p, smem, 0, 1, tile_a(1), wave, voffA, m0, n0, TB);
         stage_half<1, ES>(p, smem, 0, 1, tile_w(1), wave, voffW, m0, n0, TB);
     }
     if (nk > 1) {
@@ -1331,7 +1227,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     TT_SLOT_END();
-    cstamp(1);
     const bool late = wave >= 4;   // (grouping by SIMD parity instead, both waves of a SIMD in the same slot: -36 %)
     if (late) TT_SLOT_END();   // waves 4-7 run one slot behind
 
@@ -1437,18 +1332,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
     };
     // 4-slot variant: La (A-lo, W-lo, W-hi fragments) | Ca (quadrants 00, 01) | Lb (A-hi) | Cb (11, 10):
     // half as many barriers per MFMA.
-    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(p.vt);
-    int dbg_i = 0;
-    auto stamp = [&](int t) {
-        if constexpr (SLOTS == 46) {
-            if ((int)blockIdx.x == (p.xp >> 20) && t == 6 && (lane == 0) && dbg) {
-                __builtin_amdgcn_sched_barrier(0);
-                dbg[wave * 32 + dbg_i] = __builtin_amdgcn_s_memtime();
-                ++dbg_i;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
     auto wait_n = [&](int n) {
         if (n == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
         else if (n == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
@@ -1461,19 +1344,10 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
     // (Moving half of the copies into the C slots was measured neutral-to-worse: an LDS-DMA issue
     // costs ~100 cycles wherever it sits, and the C slot is then as long as the L slot.)
     // (f8c: the tile's flavour in the f16c stream -- false: fp16 MFMAs, true: scaled e4m3 MFMAs; always false otherwise)
-    // Energy ablations (diagnostic library only, TT_GEMM_ENERGY; wrong results): from the third K-tile on, 1 = no operand copies
-    // (the MFMAs run on stale LDS tiles: no LDS-DMA, L2 or HBM traffic), 2 = no fragment reads (stale registers: no LDS reads),
-    // 3 = both.  Run under the power cap with random operands, the rate each gains is that part's share of the energy per flop.
-#if TT_DIAG
-    const int eabl = (p.xp & 0x80000) ? ((p.xp >> 4) & 15) : 0;
-#else
-    constexpr int eabl = 0;
-#endif
     auto tile4 = [&](int t, auto bufc, auto f8c) {
         constexpr int B = decltype(bufc)::value;
         constexpr bool F8T = XC && decltype(f8c)::value;
-        const bool dma_on = !((eabl & 1) && t >= 2), rd_on = !((eabl & 2) && t >= 2);
-        const bool more1 = t + 1 < nk && dma_on, more2 = t + 2 < nk && dma_on;
+        const bool more1 = t + 1 < nk, more2 = t + 2 < nk;
         // f16c: vector-memory operations that may still be in flight at the two counted waits -- the copies of Lb(t - 1)
         // resp. Lb(t) include one scale strip when the tile they prefetch (t + 1 resp. t + 2) is an e4m3 tile
         // (a group of four e4m3 tiles, when the tile prefetched there opens one)
@@ -1481,28 +1355,20 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
         const int sc_lb = (XC && t + 2 >= nk1 && t + 2 < nk && ((t + 2 - nk1) & 3) == 0) ? 1 : 0;
         const char* sbuf = smem + kXcScaleOff + (((t - nk1) >> 2) & 1) * 8192 + ((t - nk1) & 3) * 2048;
         // La
-        stamp(t);                                  // 0: La start
         if (more1) {
             stage_half<1, ES>(p, smem, 1, B ^ 1, tile_w(t + 1), wave, voffW, m0, n0, TB);
-            stage_half<0, ES>(p, smem, 1, B ^ 1, tile_a(t + 1), wave, voffA, m0, n0, TB);
+            stage_half<0, ES, true>(p, smem, 1, B ^ 1, tile_a(t + 1), wave, voffA, m0, n0, TB);
         } else if (kResLds) {
             stage_res(1);                          // last tile (B = 1): hi slots of buffer 0
         }
-        stamp(t);                                  // 1: copies issued
-        if (rd_on) {
-            read_a(smem + slot_off(0, 0, B));
-            read_w(wf0, smem + slot_off(1, 0, B));
-            read_w(wf1, smem + slot_off(1, 1, B));
-        }
+        read_a(smem + slot_off(0, 0, B));
+        read_w(wf0, smem + slot_off(1, 0, B));
+        read_w(wf1, smem + slot_off(1, 1, B));
         if constexpr (F8T) {
             sa_reg[0] = *reinterpret_cast<const uint32_t*>(sbuf + sa_off);
             sw_reg = *reinterpret_cast<const uint32_t*>(sbuf + sw_off);
         }
-        stamp(t);                                  // 2: reads issued
-        if (SLOTS == 46) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp(t);                                  // 3: reads returned
         wait_n((t + 1 < nk || kResLds) ? 8 + sc_la : 0);
-        stamp(t);                                  // 4: past barrier (Ca start)
         if constexpr (F8T) {
             mma8(acc[0][0], wf0, sa_reg[0], sw_reg, std::integral_constant<int, 0>{});
             mma8(acc[0][1], wf1, sa_reg[0], sw_reg, std::integral_constant<int, 1>{});
@@ -1510,25 +1376,18 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
             mma(acc[0][0], wf0);                   // Ca
             mma(acc[0][1], wf1);
         }
-        stamp(t);                                  // 5: MFMAs issued
         TT_SLOT_END();
         // Lb
-        stamp(t);                                  // 6: Lb start
         if (more2) {
-            stage_half<0, ES>(p, smem, 0, B, tile_a(t + 2), wave, voffA, m0, n0, TB);
+            stage_half<0, ES, true>(p, smem, 0, B, tile_a(t + 2), wave, voffA, m0, n0, TB);
             stage_half<1, ES>(p, smem, 0, B, tile_w(t + 2), wave, voffW, m0, n0, TB);
             if (sc_lb) stage_scales(t + 2);
         } else if (kResLds) {
             stage_res(B == 0 ? 0 : 2);             // tile nk-2 (B = 0): lo slots of buffer 0; tile nk-1: of buffer 1
         }
-        stamp(t);                                  // 7
-        if (rd_on) read_a(smem + slot_off(0, 1, B));
+        read_a(smem + slot_off(0, 1, B));
         if constexpr (F8T) sa_reg[1] = *reinterpret_cast<const uint32_t*>(sbuf + 512 + sa_off);
-        stamp(t);                                  // 8
-        if (SLOTS == 46) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp(t);                                  // 9
         wait_n((t + 2 < nk || kResLds) ? 6 + sc_lb : 0);
-        stamp(t);                                  // 10: Cb start
         if constexpr (F8T) {
             mma8(acc[1][1], wf1, sa_reg[1], sw_reg, std::integral_constant<int, 1>{});
             mma8(acc[1][0], wf0, sa_reg[1], sw_reg, std::integral_constant<int, 0>{});
@@ -1536,9 +1395,7 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
             mma(acc[1][1], wf1);                   // Cb
             mma(acc[1][0], wf0);
         }
-        stamp(t);                                  // 11
         TT_SLOT_END();
-        stamp(t);                                  // 12
     };
 
     if constexpr (XC) {
@@ -1556,7 +1413,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
             if (t + 1 < nk) tile4(t + 1, std::integral_constant<int, 1>{}, std::false_type{});
         }
     }
-    cstamp(2);
     if (!late) TT_SLOT_END();   // match the extra barrier the late group took up front
     stage_res(3);               // every operand read is done: hi slots of buffer 1
 
@@ -1587,20 +1443,10 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
                 gemm_epilogue_wide<EPI, 2, 4>(p, acc[qm][qn], m0 + qm * 128 + wm * 64, n0 + wn * 64 + qn * 32, lane);
     } else if constexpr (EPI == TT_EPI_SCAN) {
         if (p.scan_dense) scan_sample_epilogue(p, acc, tm, wm, wn, lane);
-        else if (p.xp & 0x10000) scan_filter_epilogue<2>(p, acc, smem, kBiasOff, m0, wm, wn, lane);
+        else if (p.scan_wave_lists) scan_filter_epilogue<2>(p, acc, smem, kBiasOff, m0, wm, wn, lane);
         else scan_filter_epilogue<1>(p, acc, smem, kBiasOff, m0, wm, wn, lane);
-    } else if constexpr (SLOTS == 47) {
-#pragma unroll
-        for (int qm = 0; qm < 2; ++qm)
-#pragma unroll
-            for (int qn = 0; qn < 2; ++qn)
-                gemm_epilogue_wide<EPI, 2, 4, true>(p, acc[qm][qn], m0 + qm * 128 + wm * 64, n0 + wn * 64 + qn * 32, lane);
     } else {
-        epilogue_all<EPI, true, FP8>(p, acc, smem, kBiasOff, kScaleOff, m0, n0, wm, wn, wave, lane, false, NoNext{}, kScaleOff, kScaleOff + 2048);
-    }
-    if constexpr (SLOTS == 46) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        cstamp(3);
+        epilogue_all<EPI, true, FP8>(p, acc, smem, kBiasOff, kScaleOff, m0, n0, wm, wn, wave, lane, false, NoNext{});
     }
 }
 
@@ -1616,7 +1462,7 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_v3(GemmParams p) {
 // next tile (La(0)) are issued BEFORE the 16 epilogue stores, so the first two waits of a non-first tile allow
 // 8 + 16 and 6 + 16 operations; by the third the stores are four slots old.
 // The residual epilogue needs all eight slots for the residual tile and stays on the one-tile-per-block kernel.
-template <int EPI, bool FP8 = false, bool STAMP = false>
+template <int EPI, bool FP8 = false>
 __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int nwg) {
     constexpr int ES = FP8 ? 1 : 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1679,15 +1525,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
             if (wave == 1) glds16(p.a_scale + mm0, lane * 16, l0 + kScaleOff + par * 2048);
             if (wave == 2) glds16(p.w_scale + nn0, lane * 16, l0 + kScaleOff + par * 2048 + 1024);
         }
-#if TT_DIAG
-        if constexpr (!FP8 && (EPI == TT_EPI_BIAS || EPI == TT_EPI_GELU)) {
-            if (p.lnf == 1) {   // consumer form only: column sums at kScaleOff + par KiB, row statistics at kScaleOff + 2 KiB + par 2 KiB (launched with 2 KiB more LDS)
-                if (wave == 1) glds16(p.lnf_c0 + nn0, lane * 16, l0 + kScaleOff + par * 1024);
-                if (wave == 3) glds16(p.lnf_rows + (size_t)mm0 * 2, lane * 16, l0 + kScaleOff + 2048 + par * 2048);
-                if (wave == 5) glds16(p.lnf_rows + (size_t)(mm0 + 128) * 2, lane * 16, l0 + kScaleOff + 2048 + par * 2048 + 1024);
-            }
-        }
-#endif
     };
     // hi / lo halves of K-tile u of the current tile, or of K-tile u - nk of the next one (nk is even: same buffer)
     auto issue_hi = [&](int u) {
@@ -1712,28 +1549,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
     const bool late = wave >= 4;
     int bpar = 0;
     bool first = true;
-    // diagnostic build (TT_GEMM_ABLATE=8, tools/gemm_stamps_p): s_memtime of workgroup 0's waves 0 and 4 at the slot boundaries of
-    // the first K-tiles of its 2nd..7th output tile -> p.vt[(wave >= 4) * 1024 + tile_no * 128 + index]
-    int tile_no = 0;
-    unsigned long long* sdbg = reinterpret_cast<unsigned long long*>(p.vt);
-    auto pstamp = [&](int idx) {
-        if constexpr (STAMP) {
-            if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 4) && tile_no >= 1 && tile_no < 8 && idx < 128 && sdbg) {
-                __builtin_amdgcn_sched_barrier(0);
-                sdbg[(wave >= 4 ? 1024 : 0) + tile_no * 128 + idx] = __builtin_amdgcn_s_memtime();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    };
-    // De-phasing (p.xp >> 8 = phases, in 1024-cycle units of delay per phase step): every CU of an XCD finishes its tiles at
-    // the same moment, so the XCD's 32 x 128 KiB of output arrive at its 4 MiB L2 in one burst, which has to be written
-    // back before it is accepted -- and the in-order vector-memory queue holds the next tile's copies behind those
-    // stores.  A one-time start delay by position inside the XCD (blockIdx.x / 8: workgroups b and b + 8 share an XCD)
-    // spreads the bursts over the tile period for the whole kernel (static tile lists keep the phase).
-    if (const int ph = p.xp >> 8) {
-        const int steps = ((blockIdx.x >> 3) % 32) * ph;       // x 1024 cycles
-        for (int i = 0; i < steps; ++i) __builtin_amdgcn_s_sleep(16);
-    }
     if constexpr (EPI == TT_EPI_SCAN) {     // wave-private survivor lists (scan_filter_epilogue<2>): this wave's count
         if (lane == 0) *reinterpret_cast<int*>(smem + kScanHitOff + wave * 1024) = 0;
     }
@@ -1803,19 +1618,15 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
             // atomics return a value, so the compiler has already waited for them -- the plain counts are right)
             const bool after_epi = t == 0 && !first && EPI != TT_EPI_SCAN;
             // La: hi halves of K-tile t+1 (already issued, ahead of the stores, when after_epi)
-            pstamp(t * 4 + 0);                        // La start
             if (!(t == 0 && !first)) issue_hi(t + 1);
             read_a(smem + slot_off(0, 0, B));
             read_w(wf0, smem + slot_off(1, 0, B));
             read_w(wf1, smem + slot_off(1, 1, B));
-            // (xp bit 1: one more store-tolerant wait -- at La(1) the stores are still only behind hi(2'), lo(2'))
-            if (after_epi || (t == 1 && !first && EPI != TT_EPI_SCAN && (p.xp & 2))) wait_n(24);
+            if (after_epi) wait_n(24);
             else wait_n((t + 1 < nk || has_next) ? 8 : 0);
-            pstamp(t * 4 + 1);                        // Ca start (past La's wait + barrier)
             mma(acc[0][0], wf0);                       // Ca
             mma(acc[0][1], wf1);
             TT_SLOT_END();
-            pstamp(t * 4 + 2);                        // Lb start
             // Lb: lo halves of K-tile t+2; the other group's epilogue of the previous tile is over: the bias
             // strip it read can be refilled for the next tile
             if (t == 0 && has_next) stage_strips(m1, n1, bpar ^ 1);
@@ -1823,7 +1634,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
             read_a(smem + slot_off(0, 1, B));
             if (after_epi) wait_n(22);
             else wait_n((t + 2 < nk || has_next) ? 6 : 0);
-            pstamp(t * 4 + 3);                        // Cb start
             mma(acc[1][1], wf1);                       // Cb
             mma(acc[1][0], wf0);
             TT_SLOT_END();
@@ -1832,21 +1642,19 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
             tile4(t, std::integral_constant<int, 0>{});
             tile4(t + 1, std::integral_constant<int, 1>{});
         }
-        pstamp(100);                                  // main loop done
         if (has_next) issue_hi(nk + 1);   // La(0) of the next tile, ahead of this tile's stores
-        // Tile boundary.  With the groups one slot apart THROUGH the boundary their epilogues serialise: group A converts
+        // Tile boundary.  With the groups one slot apart THROUGH the boundary their epilogues would serialise: group A converts
         // and stores (4.3 k cycles for the bias epilogue, one wave per SIMD at half the vector issue rate) while B can only
         // run its last 512-cycle MFMA slot and then waits at a barrier A reaches after its epilogue; then B's epilogue runs
-        // while A waits at the end of Ca(0) (stamps, tools/gemm_stamps_p: 6.3 k cycles in that one slot) -- 11.7 k of a
-        // 59.7 k-cycle K = 1024 tile.  Aligned instead: A waits ONE slot for B's last MFMAs, both groups run their
-        // epilogues side by side, and B waits one slot after it to fall behind again, exactly as at kernel start.
+        // while A waits at the end of Ca(0) (profiles/r02_gemm_persistent_stamps_before.log: 6.3 k cycles in that one slot)
+        // -- 11.7 k of a 59.7 k-cycle K = 1024 tile.  So the groups are aligned: A waits ONE slot for B's last MFMAs, both
+        // groups run their epilogues side by side, and B waits one slot after it to fall behind again, exactly as at kernel start.
         // Measured: GELU 3.45 -> 3.41 ms, bias 3.18 -> 3.16 ms (N = 4096) -- only 1-2 %, because the stamps of the aligned
         // form show the real bound: the two epilogues together still take 8.6 k cycles, i.e. the 128 store instructions of
         // a tile (1 KiB each) issue at ~15 B/clk/CU whoever issues them (store-ISSUE bound, MI355X_MICROARCH.md's
         // "epilogue store tail" row); hiding them needs independent MFMA work on the CU, which one 8-wave workgroup with
         // 128 accumulator registers per wave does not have.
-        const bool align = (p.xp & 4) == 0;    // default on (bit 2 of TT_GEMM_XP turns it OFF: the A/B switch)
-        if (align && !late) TT_SLOT_END();
+        if (!late) TT_SLOT_END();
 
         // the epilogue's per-lane addresses are recomputed per tile from an opaque copy of the lane id: hoisted out
         // of the tile loop they would stay live through the main loop
@@ -1856,14 +1664,9 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
             scan_filter_epilogue<2>(p, acc, smem, kBiasOff + bpar * 1024, m0, wm, wn, lane_e);
         else
             epilogue_all<EPI, false, FP8>(p, acc, smem, kBiasOff + bpar * 1024, kScaleOff + bpar * 2048, m0, n0, wm, wn, wave, lane_e,
-                                          false, NoNext{}, kScaleOff + bpar * 1024, kScaleOff + 2048 + bpar * 2048);
-        pstamp(101);                                  // epilogue done (stores issued)
-        ++tile_no;
-        if (!has_next) {
-            if (!align && !late) TT_SLOT_END();   // match the extra barrier the late group took up front
-            break;
-        }
-        if (align && late) TT_SLOT_END();         // fall one slot behind again
+                                          false, NoNext{});
+        if (!has_next) break;
+        if (late) TT_SLOT_END();                  // fall one slot behind again
         v = vn; m0 = m1; n0 = n1; bpar ^= 1; first = false;
         vn = next_valid(v, m1, n1);
         has_next = vn < nwg;
@@ -1872,55 +1675,6 @@ __global__ __launch_bounds__(kThreads3, 2) void gemm_kernel_p(GemmParams p, int 
 #undef TT_SLOT_END
 }  // namespace v3
 
-// Super-tile shape: the 32 tiles an XCD works on at a time are SM row-blocks x SN column-blocks (SM * SN = 32); the A
-// row-blocks of a super-tile are shared through that XCD's L2 by its SN column tiles.
-inline int super_sn(int nt_n) {
-    static const int env = TT_DIAG_ENV_INT("TT_GEMM_SN", 0);
-    int sn = env > 0 ? env : 4;
-    if (sn > nt_n) sn = nt_n;
-    while (32 % sn) --sn;
-    return sn;
-}
-
-inline bool small_grid_v1() {
-    static const bool on = TT_DIAG_ENV_INT("TT_GEMM_SMALL_V1", 1) != 0;
-    return on;
-}
-
-// fp8 operands: the 256x256 kernels only (bias / GELU / V^T epilogues), K-tiles of 128 elements
-template <int EPI>
-int launch_fp8(const GemmParams& p, hipStream_t st) {
-    if constexpr (EPI == TT_EPI_BIAS || EPI == TT_EPI_GELU || EPI == TT_EPI_VT || EPI == TT_EPI_RESIDUAL) {
-        const int nk = p.K / 128;
-        if (EPI == TT_EPI_RESIDUAL && (!p.residual || p.ldr % 8)) {
-            tt_set_error("gemm fp8: residual epilogue without residual");
-            return TT_E_INVALID;
-        }
-        if (p.M % v3::BM3 || p.N % v3::BN3 || p.K % 128 || nk < 2 || (nk & 1) || p.ldc % 8 || p.lda % 16 || !p.a_scale || !p.w_scale) {
-            tt_set_error("gemm fp8: M=%d N=%d K=%d must be multiples of 256/256/256 with row / column scales", p.M, p.N, p.K);
-            return TT_E_UNSUPPORTED;
-        }
-        const int mt_n = p.M / v3::BM3, nt_n = p.N / v3::BN3;
-        const int SN = super_sn(nt_n), SM = 32 / SN;
-        const int supers = ((mt_n + SM - 1) / SM) * ((nt_n + SN - 1) / SN);
-        int blocks = supers * SM * SN;
-        blocks = (blocks + 7) / 8 * 8;
-        // (the persistent kernel's fp8 GELU form spills; every fp8 GEMM runs one tile per workgroup)
-        TT_SET_MAX_LDS((v3::gemm_kernel_v3<EPI, 4, true>), v3::kLds3);
-        {
-            TtProfScope prof(TT_K_GEMM, st);
-            GemmParams q = p;
-            q.sn = SN;
-            hipLaunchKernelGGL((v3::gemm_kernel_v3<EPI, 4, true>), dim3(blocks), dim3(v3::kThreads3), v3::kLds3, st, q);
-        }
-        TT_CHECK_LAUNCH();
-        return TT_OK;
-    } else {
-        tt_set_error("gemm fp8: epilogue %d has no fp8 form", EPI);
-        return TT_E_UNSUPPORTED;
-    }
-}
-
 // ---- skinny: M <= 256 rows (one query's embedding, the CLS-row tail of the last layer, the rerank head) -----------
 // With a few dozen token rows a GEMM is a stream of the weight matrix and nothing else: the tiled kernels put
 // 16 (N = 1024) to 64 workgroups on the chip and walk K in 64-element steps behind a barrier each (8 us at K = 1024,
@@ -1928,7 +1682,7 @@ int launch_fp8(const GemmParams& p, hipStream_t st) {
 // columns x 16 rows x all of K: no LDS, no barrier, operands straight from global memory into MFMA fragments (a
 // fragment is 16 contiguous bytes of a K-contiguous row in both operands), 24 K-steps of loads in flight per wave,
 // N/16 x M/16 waves per launch.  The activations (<= 256 x K) and, by the row tiles of a column block, the weights
-// are re-read from L2.  (Rounds 1-2: 16 columns x 64 rows per wave, 8 steps in flight -- TT_GEMM_SKINNY_MT=4.)
+// are re-read from L2.  (Rounds 1-2: 16 columns x 64 rows per wave, 8 steps in flight.)
 // Same instruction, operand order and K order as the tiled kernels, same epilogue code: results are bit-identical
 // to theirs, so an embedding does not depend on whether the text was embedded alone or in a large batch.
 
@@ -2264,13 +2018,6 @@ __global__ __launch_bounds__(kStagedThreads, 1) void gemm_staged_kernel(GemmPara
     else gemm_epilogue_tile<EPI, 2, 4>(p, acc, m0 + wm * 64, n0 + wn * 32, lane);
 }
 
-// (diagnostic library: TT_GEMM_STAGED=0 puts the 256x256 split-plane kernel back; TT_GEMM_STAGED_MAX = the 128x128-tile count up to
-// which the staged kernel takes a split-plane GEMM, default the CU count)
-inline bool staged_enabled() {
-    static const bool on = TT_DIAG_ENV_INT("TT_GEMM_STAGED", 1) != 0;
-    return on;
-}
-
 // ---- relay form of the skinny kernel (round 6) ------------------------------------------------------------------------------
 // The one-wave kernel above is a chain of memory round trips: a wave keeps PF K-steps of loads in flight and every refill waits
 // for HBM again -- a K = 4096 projection is 128 (split planes: 384) steps = 6 (16) round trips of ~2.5 us while 255 of the
@@ -2333,104 +2080,117 @@ __global__ __launch_bounds__(64 * NW) void gemm_relay_kernel(GemmParams p) {
     }
 }
 
-// (diagnostic library: TT_GEMM_RELAY=0 puts the one-wave kernel back -- the A/B switch)
-inline bool skinny_relay() {
-    static const bool on = TT_DIAG_ENV_INT("TT_GEMM_RELAY", 1) != 0;
-    return on;
-}
-inline bool skinny_relay_16() {
-    static const bool on = TT_DIAG_ENV_INT("TT_GEMM_RELAY", 1) == 2;
-    return on;
+// ---- launchers: validate, plan (gemm_plan.h: which kernel, on what grid), launch --------------------------------------------
+// The A/B switches of kept decisions, read once: the diagnostic library's environment, in the product library their defaults.
+const GemmSwitches& gemm_switches() {
+    static const GemmSwitches sw = [] {
+        GemmSwitches s;
+        s.skinny = TT_DIAG_ENV_INT("TT_GEMM_SKINNY", 1) != 0;
+        s.relay = TT_DIAG_ENV_INT("TT_GEMM_RELAY", 1) != 0;
+        s.staged = TT_DIAG_ENV_INT("TT_GEMM_STAGED", 1) != 0;
+        s.staged_max = TT_DIAG_ENV_INT("TT_GEMM_STAGED_MAX", 0);
+        s.staged16 = TT_DIAG_ENV_INT("TT_GEMM_STAGED16", 1);
+        s.small_v1 = TT_DIAG_ENV_INT("TT_GEMM_SMALL_V1", 1) != 0;
+        s.sn = TT_DIAG_ENV_INT("TT_GEMM_SN", 0);
+        s.qkv_split = TT_DIAG_ENV_INT("TT_GEMM_QKV_SPLIT", 1) != 0;
+        // whole-line stores as streaming stores: +1...3 % on the bias-only shapes, -0.7 ms per bench step (with the old 32-byte
+        // runs the same hint cost 18 %: no write combining in L2)
+        s.nt_store = TT_DIAG_ENV_INT("TT_GEMM_NT_STORE", 1);
+        s.trace = TT_DIAG_ENV_INT("TT_GEMM_TRACE", 0) == 1;
+        return s;
+    }();
+    return sw;
 }
 
-// TT_GEMM_SKINNY_MT=4: round 2's shape (four row tiles per wave, 8 steps in flight), the A/B switch
-inline bool skinny_mt4() {
-    static const bool on = TT_DIAG_ENV_INT("TT_GEMM_SKINNY_MT", 0) == 4;
-    return on;
+GemmPlan plan_of(GemmForm form, int epi, const GemmParams& p) {
+    return gemm_plan(form, epi, p.M, p.N, p.K, p.ldc, p.ldr, tt_cu_count_cached(), gemm_switches());
 }
 
-// split-bf16 operands (GemmParams.x3): the 256x256 one-tile kernel, bias / GELU (planes out), residual (fp32 out), V^T
+// one launch inside the profiler scope `scope`; a kernel with dynamic LDS is opted in to it first (once per device)
+template <auto Kern, class... Args>
+int run_kernel(int scope, dim3 grid, int threads, int lds, hipStream_t st, const Args&... args) {
+    if (lds) TT_SET_MAX_LDS(Kern, lds);
+    {
+        TtProfScope prof(scope, st);
+        hipLaunchKernelGGL(Kern, grid, dim3(threads), lds, st, args...);
+    }
+    TT_CHECK_LAUNCH();
+    return TT_OK;
+}
+
+// fp8 operands: the 256x256 one-tile kernel only (bias / GELU / residual / V^T epilogues), K-tiles of 128 elements
+template <int EPI>
+int launch_fp8(const GemmParams& p, hipStream_t st) {
+    if constexpr (EPI == TT_EPI_BIAS || EPI == TT_EPI_GELU || EPI == TT_EPI_VT || EPI == TT_EPI_RESIDUAL) {
+        const int nk = p.K / 128;
+        if (EPI == TT_EPI_RESIDUAL && (!p.residual || p.ldr % 8)) {
+            tt_set_error("gemm fp8: residual epilogue without residual");
+            return TT_E_INVALID;
+        }
+        if (p.M % v3::BM3 || p.N % v3::BN3 || p.K % 128 || nk < 2 || (nk & 1) || p.ldc % 8 || p.lda % 16 || !p.a_scale || !p.w_scale) {
+            tt_set_error("gemm fp8: M=%d N=%d K=%d must be multiples of 256/256/256 with row / column scales", p.M, p.N, p.K);
+            return TT_E_UNSUPPORTED;
+        }
+        const GemmPlan pl = plan_of(GemmForm::Fp8, EPI, p);
+        GemmParams q = p;
+        q.sn = pl.grid.sn;
+        return run_kernel<v3::gemm_kernel_v3<EPI, true>>(TT_K_GEMM, dim3(pl.gx), v3::kThreads3, v3::kLds3, st, q);
+    } else {
+        tt_set_error("gemm fp8: epilogue %d has no fp8 form", EPI);
+        return TT_E_UNSUPPORTED;
+    }
+}
+
+// Output of a split-plane GEMM: fp32 (residual), the V8 layout twice (V^T) or two planes.  The tiled kernels store 16 bytes per lane
+// and whole V8 groups, the skinny and relay kernels 8 bytes: strides in units of 8 resp. 4 elements.
+template <int EPI>
+int check_x3_output(const GemmParams& p, bool tiled) {
+    const int unit = tiled ? 8 : 4;
+    if constexpr (EPI == TT_EPI_RESIDUAL) {
+        if (!p.C32 || (!p.res32 && !p.res_planes) || p.ldc % 4 || p.ldr % 4 || (p.res_planes && (p.ldr % 8 || p.res_lo_off % 8))) {
+            tt_set_error("gemm x3: residual epilogue needs fp32 C32 and res32 or res_planes");
+            return TT_E_INVALID;
+        }
+    } else if constexpr (EPI == TT_EPI_VT) {
+        if (!p.vt || !p.vt_lo || (tiled && p.ldvt % 8)) { tt_set_error("gemm x3: V^T epilogue needs vt / vt_lo"); return TT_E_INVALID; }
+    } else {
+        if (!p.C || p.ldc % unit || p.c_lo_off % unit || p.c_lo_off < p.N) {
+            tt_set_error("gemm x3: planes output needs C, c_lo_off >= N");
+            return TT_E_INVALID;
+        }
+    }
+    return TT_OK;
+}
+
+// split-bf16 operands (GemmParams.x3): bias / GELU (planes out), residual (fp32 out), V^T.  Up to 256 rows (one query's embedding) the
+// weight-streaming kernels on the same virtual K stream -- a 256-row tile grid would put 4-16 workgroups on the chip (11.5 ms per
+// 24-layer forward instead of ~3); else the staged 128x128 or the 256x256 one-tile kernel
 template <int EPI>
 int launch_x3(const GemmParams& p, hipStream_t st) {
     if constexpr (EPI == TT_EPI_BIAS || EPI == TT_EPI_GELU || EPI == TT_EPI_VT || EPI == TT_EPI_RESIDUAL) {
-        const int ldw = p.ldw ? p.ldw : p.K;
-        // up to 256 rows (one query's embedding): the weight-streaming skinny kernel on the same virtual K stream -- a
-        // 256-row tile grid would put 4-16 workgroups on the chip (11.5 ms per 24-layer forward instead of ~3)
-        if (tt_gemm_skinny_enabled() && p.M > 0 && p.M <= 256 && p.M % 64 == 0 && p.N % 16 == 0 && p.K % 32 == 0 && p.lda >= 2 * p.K &&
-            ldw >= 2 * p.K && p.lda % 8 == 0 && ldw % 8 == 0 && p.A && p.W && p.bias) {
-            if constexpr (EPI == TT_EPI_RESIDUAL) {
-                if (!p.C32 || (!p.res32 && !p.res_planes) || p.ldc % 4 || p.ldr % 4 || (p.res_planes && (p.ldr % 8 || p.res_lo_off % 8))) { tt_set_error("gemm x3: residual epilogue needs fp32 C32 and res32 or res_planes"); return TT_E_INVALID; }
-            } else if constexpr (EPI == TT_EPI_VT) {
-                if (!p.vt || !p.vt_lo) { tt_set_error("gemm x3: V^T epilogue needs vt / vt_lo"); return TT_E_INVALID; }
-            } else {
-                if (!p.C || p.ldc % 4 || p.c_lo_off % 4 || p.c_lo_off < p.N) { tt_set_error("gemm x3: planes output needs C, c_lo_off >= N"); return TT_E_INVALID; }
-            }
-            GemmParams q = p;
-            q.ldw = ldw;
-            {
-                TtProfScope prof(TT_K_GEMM, st);
-                if (skinny_mt4()) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, true, 4, 8>), dim3(p.N / 16, p.M / 64), dim3(64), 0, st, q);
-                else if (skinny_relay()) hipLaunchKernelGGL((gemm_relay_kernel<EPI, true>), dim3(p.N / 16, p.M / 16), dim3(64 * 8), 0, st, q);
-                else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, true>), dim3(p.N / 16, p.M / 16), dim3(64), 0, st, q);
-            }
-            TT_CHECK_LAUNCH();
-            return TT_OK;
-        }
-        if (p.M % v3::BM3 || p.N % 64 || p.K % 64 || p.K < 128 || p.lda < 2 * p.K || ldw < 2 * p.K || p.lda % 8 || ldw % 8 || !p.A ||
-            !p.W || !p.bias) {
-            tt_set_error("gemm x3: M=%d N=%d K=%d lda=%d ldw=%d: M a multiple of 256, N and K of 64, planes [.][>= 2K]", p.M, p.N, p.K, p.lda, ldw);
+        const GemmPlan pl = plan_of(GemmForm::X3, EPI, p);
+        const bool tiled = pl.kernel != GemmKernel::Relay && pl.kernel != GemmKernel::Skinny;
+        GemmParams q = p;
+        q.ldw = p.ldw ? p.ldw : p.K;
+        if (p.lda < 2 * p.K || q.ldw < 2 * p.K || p.lda % 8 || q.ldw % 8 || !p.A || !p.W || !p.bias ||
+            (tiled && (p.M % v3::BM3 || p.N % 64 || p.K % 64 || p.K < 128))) {
+            tt_set_error("gemm x3: M=%d N=%d K=%d lda=%d ldw=%d: M a multiple of 256, N and K of 64, planes [.][>= 2K]", p.M, p.N, p.K, p.lda, q.ldw);
             return TT_E_UNSUPPORTED;
         }
+        if (int rc = check_x3_output<EPI>(p, tiled)) return rc;
+        switch (pl.kernel) {
+            case GemmKernel::Relay: return run_kernel<gemm_relay_kernel<EPI, true>>(TT_K_GEMM, dim3(pl.gx, pl.gy), 64 * 8, 0, st, q);
+            case GemmKernel::Skinny: return run_kernel<gemm_skinny_kernel<EPI, true>>(TT_K_GEMM, dim3(pl.gx, pl.gy), 64, 0, st, q);
+            case GemmKernel::Staged128:
+                return run_kernel<gemm_staged_kernel<EPI, true>>(TT_K_GEMM, dim3(pl.gx), kStagedThreads, kStagedLds, st, q);
+            default: break;
+        }
+        q.sn = pl.grid.sn;
         if constexpr (EPI == TT_EPI_RESIDUAL) {
-            if (!p.C32 || (!p.res32 && !p.res_planes) || p.ldc % 4 || p.ldr % 4 || (p.res_planes && (p.ldr % 8 || p.res_lo_off % 8))) { tt_set_error("gemm x3: residual epilogue needs fp32 C32 and res32 or res_planes"); return TT_E_INVALID; }
-        } else if constexpr (EPI == TT_EPI_VT) {
-            if (!p.vt || !p.vt_lo || p.ldvt % 8) { tt_set_error("gemm x3: V^T epilogue needs vt / vt_lo"); return TT_E_INVALID; }
-        } else {
-            if (!p.C || p.ldc % 8 || p.c_lo_off % 8 || p.c_lo_off < p.N) { tt_set_error("gemm x3: planes output needs C, c_lo_off >= N"); return TT_E_INVALID; }
+            if (p.res_planes)
+                return run_kernel<v3::gemm_kernel_v3<EPI, false, true, false, true>>(TT_K_GEMM, dim3(pl.gx), v3::kThreads3, v3::kLds3, st, q);
         }
-        // a lone caller's rerank (the reference's 10-20 pairs: M = 1-8 k rows): up to TWO rounds of 128x128 tiles the staged kernel beats
-        // the 256x256 kernel's one round on a fraction of the CUs -- one round 2.1-2.4 x (M = 3072: 63 -> 28 us, 190 -> 88 us), two rounds
-        // 1.1-1.2 x (M = 7424: 68 -> 57, 206 -> 182 us); beyond that the big tile's half fill per flop wins (profiles/r06_staged_ab.log)
-        static const int staged_max = TT_DIAG_ENV_INT("TT_GEMM_STAGED_MAX", 0);
-        const int mt1 = p.M / BM, nt1 = p.N / BN;
-        if (staged_enabled() && p.N % BN == 0 && (long long)mt1 * nt1 <= (staged_max ? staged_max : 2 * tt_cu_count_cached())) {
-            const int SN1 = nt1 < 8 ? nt1 : 8, SM1 = 8;
-            int blocks1 = ((mt1 + SM1 - 1) / SM1) * ((nt1 + SN1 - 1) / SN1) * SM1 * SN1;
-            blocks1 = (blocks1 + 7) / 8 * 8;
-            TT_SET_MAX_LDS((gemm_staged_kernel<EPI, true>), kStagedLds);
-            {
-                TtProfScope prof(TT_K_GEMM, st);
-                GemmParams q = p;
-                q.ldw = ldw;
-                hipLaunchKernelGGL((gemm_staged_kernel<EPI, true>), dim3(blocks1), dim3(kStagedThreads), kStagedLds, st, q);
-            }
-            TT_CHECK_LAUNCH();
-            return TT_OK;
-        }
-        const int mt_n = p.M / v3::BM3, nt_n = (p.N + v3::BN3 - 1) / v3::BN3;      // (N % 64 == 0: the last column tile may be partial)
-        const int SN = super_sn(nt_n), SM = 32 / SN;
-        const int supers = ((mt_n + SM - 1) / SM) * ((nt_n + SN - 1) / SN);
-        int blocks = supers * SM * SN;
-        blocks = (blocks + 7) / 8 * 8;
-        TT_SET_MAX_LDS((v3::gemm_kernel_v3<EPI, 4, false, true>), v3::kLds3);
-        {
-            TtProfScope prof(TT_K_GEMM, st);
-            GemmParams q = p;
-            q.sn = SN;
-            q.ldw = ldw;
-            if constexpr (EPI == TT_EPI_RESIDUAL) {
-                if (p.res_planes) {
-                    TT_SET_MAX_LDS((v3::gemm_kernel_v3<EPI, 4, false, true, false, true>), v3::kLds3);
-                    hipLaunchKernelGGL((v3::gemm_kernel_v3<EPI, 4, false, true, false, true>), dim3(blocks), dim3(v3::kThreads3), v3::kLds3, st, q);
-                } else {
-                    hipLaunchKernelGGL((v3::gemm_kernel_v3<EPI, 4, false, true>), dim3(blocks), dim3(v3::kThreads3), v3::kLds3, st, q);
-                }
-            } else {
-                hipLaunchKernelGGL((v3::gemm_kernel_v3<EPI, 4, false, true>), dim3(blocks), dim3(v3::kThreads3), v3::kLds3, st, q);
-            }
-        }
-        TT_CHECK_LAUNCH();
-        return TT_OK;
+        return run_kernel<v3::gemm_kernel_v3<EPI, false, true>>(TT_K_GEMM, dim3(pl.gx), v3::kThreads3, v3::kLds3, st, q);
     } else {
         tt_set_error("gemm x3: epilogue %d has no split-bf16 form", EPI);
         return TT_E_UNSUPPORTED;
@@ -2461,169 +2221,59 @@ int launch_xc(const GemmParams& p, hipStream_t st) {
                 return TT_E_INVALID;
             }
         }
-        const int mt_n = p.M / v3::BM3, nt_n = p.N / v3::BN3;
-        const int SN = super_sn(nt_n), SM = 32 / SN;
-        const int supers = ((mt_n + SM - 1) / SM) * ((nt_n + SN - 1) / SN);
-        int blocks = supers * SM * SN;
-        blocks = (blocks + 7) / 8 * 8;
-        TT_SET_MAX_LDS((v3::gemm_kernel_v3<EPI, 4, false, false, true>), v3::kLdsXc);
-        {
-            TtProfScope prof(TT_K_GEMM, st);
-            GemmParams q = p;
-            q.sn = SN;
-            q.ldw = ldw;
-            q.nt_store = 1;
-            hipLaunchKernelGGL((v3::gemm_kernel_v3<EPI, 4, false, false, true>), dim3(blocks), dim3(v3::kThreads3), v3::kLdsXc, st, q);
-        }
-        TT_CHECK_LAUNCH();
-        return TT_OK;
+        const GemmPlan pl = plan_of(GemmForm::Xc, EPI, p);
+        GemmParams q = p;
+        q.sn = pl.grid.sn;
+        q.ldw = ldw;
+        q.nt_store = 1;
+        return run_kernel<v3::gemm_kernel_v3<EPI, false, false, true>>(TT_K_GEMM, dim3(pl.gx), v3::kThreads3, v3::kLdsXc, st, q);
     } else {
         tt_set_error("gemm f16c: epilogue %d has no f16c form (fp16 instantiation: bias, GELU, residual, V^T)", EPI);
         return TT_E_UNSUPPORTED;
     }
 }
 
-bool skinny_shape(const GemmParams& p) {
-    return !p.fp8 && tt_gemm_skinny_enabled() && p.M > 0 && p.M <= 256 && p.M % 64 == 0 && p.N % 16 == 0 && p.K % 32 == 0 && p.K > 0;
-}
-
+// 16-bit operands (validated by tt_gemm_launch, which planned the launch), or e4m3 ones
 template <int EPI>
-int launch_skinny(const GemmParams& p, hipStream_t st) {
-    {
-        TtProfScope prof(TT_K_GEMM, st);
-#if TT_DIAG   // TT_GEMM_SKINNY_PF=32 / TT_GEMM_SKINNY_MT=2: shape experiments of round 5 (every K step of a K = 1024 projection in flight; two row tiles per wave)
-        static const int pf_env = TT_DIAG_ENV_INT("TT_GEMM_SKINNY_PF", 0);
-        static const int mt_env = TT_DIAG_ENV_INT("TT_GEMM_SKINNY_MT", 0);
-        if (pf_env == 32) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, false, 1, 32>), dim3(p.N / 16, p.M / 16), dim3(64), 0, st, p);
-        else if (mt_env == 2 && p.M % 32 == 0) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, false, 2, 16>), dim3(p.N / 16, p.M / 32), dim3(64), 0, st, p);
-        else
-#endif
-        if (skinny_mt4()) hipLaunchKernelGGL((gemm_skinny_kernel<EPI, false, 4, 8>), dim3(p.N / 16, p.M / 64), dim3(64), 0, st, p);
-        // (the relay form is for the split-plane stream, 3 K / 32 steps: on the 16-bit stream one wave's 24 steps in flight already cover
-        // K = 1024 in two round trips and the relay's barriers cost 5-10 % -- profiles/r06_relay_ab.log; TT_GEMM_RELAY=2 forces it here)
-#if TT_DIAG
-        else if (skinny_relay_16()) hipLaunchKernelGGL((gemm_relay_kernel<EPI, false>), dim3(p.N / 16, p.M / 16), dim3(64 * 8), 0, st, p);
-#endif
-        else hipLaunchKernelGGL((gemm_skinny_kernel<EPI, false>), dim3(p.N / 16, p.M / 16), dim3(64), 0, st, p);
-    }
-    TT_CHECK_LAUNCH();
-    return TT_OK;
-}
-
-template <int EPI>
-int launch(const GemmParams& p, hipStream_t st) {
+int launch_16(const GemmParams& p, const GemmPlan& pl, hipStream_t st) {
     if constexpr (!kF16) if (p.fp8) return launch_fp8<EPI>(p, st);
-    static const bool trace = TT_DIAG_ENV_INT("TT_GEMM_TRACE", 0) == 1;
-    if (trace) fprintf(stderr, "gemm launch<%d> M=%d N=%d K=%d lda=%d ldc=%d ldr=%d\n", EPI, p.M, p.N, p.K, p.lda, p.ldc, p.ldr);
-    static const int variant = TT_DIAG_ENV_INT("TT_GEMM_VARIANT", 5);
-    // (the residual epilogue stages the residual tile as two pseudo K-tiles: needs an even number of K-tiles)
-    // Fewer than half a CU-wave of 256x256 tiles (query embedding, the CLS tail): the 128x128 kernel spreads the
-    // work over 4x the workgroups and is 1.3-1.7x faster there (M = 768: 15 vs 23 us per K = 1024 GEMM).
-    const bool small_grid = EPI != TT_EPI_VT && (long long)(p.M / v3::BM3) * (p.N / v3::BN3) < 128 && small_grid_v1();
-    if (variant >= 4 && !small_grid && p.M % v3::BM3 == 0 && p.N % v3::BN3 == 0 && p.ldc % 8 == 0 &&
-        (EPI != TT_EPI_RESIDUAL || (p.ldr % 8 == 0 && (p.K / BK) % 2 == 0))) {
-        const int mt_n = p.M / v3::BM3, nt_n = p.N / v3::BN3;
-        const int SN = super_sn(nt_n), SM = 32 / SN;
-        const int supers = ((mt_n + SM - 1) / SM) * ((nt_n + SN - 1) / SN);
-        int blocks = supers * SM * SN;
-        blocks = (blocks + 7) / 8 * 8;
-        // measured (M = 236800): the persistent kernel wins where the epilogue is VALU-heavy (GELU: 1.74 vs 1.78 ms), the
-        // one-tile kernel with LDS-transposed full-line stores where it is store-bound (bias: 1.39 vs 1.40 ms)
-        static const int xp = TT_DIAG_ENV_INT("TT_GEMM_XP", 0);
-        if constexpr (EPI == TT_EPI_GELU || EPI == TT_EPI_BIAS) {
-            const int cus = tt_cu_count_cached() / 8 * 8;
-            if (variant == 5 && (EPI == TT_EPI_GELU || (xp & 1)) && (p.K / BK) % 2 == 0 && p.K / BK >= 2 && blocks > cus && cus >= 8) {
-                constexpr int kLdsP = v3::kLds3 + (TT_DIAG ? 2048 : 0);     // (diagnostic build: room for the LayerNorm-folding experiment's strips)
-                TT_SET_MAX_LDS(v3::gemm_kernel_p<EPI>, kLdsP);
-                {
-                    TtProfScope prof(TT_K_GEMM, st);
-                    GemmParams q = p;
-                    q.sn = SN;
-                    q.xp = xp;
-                    hipLaunchKernelGGL(v3::gemm_kernel_p<EPI>, dim3(cus), dim3(v3::kThreads3), kLdsP, st, q, blocks);
-                }
-                TT_CHECK_LAUNCH();
-                return TT_OK;
-            }
-        }
-        auto kern = v3::gemm_kernel_v3<EPI, 4>;
-#if TT_DIAG
-        if constexpr (EPI == TT_EPI_BIAS) {   // diagnostic build of the 4-slot loop with s_memtime stamps (tools/gemm_stamps)
-            static const int abl = TT_DIAG_ENV_INT("TT_GEMM_ABLATE", 0);
-            if (abl == 8) {   // stamped persistent kernel (tools/gemm_stamps_p)
-                const int cus8 = tt_cu_count_cached() / 8 * 8;
-                TT_SET_MAX_LDS((v3::gemm_kernel_p<EPI, false, true>), v3::kLds3);
-                GemmParams q8 = p;
-                q8.sn = SN;
-                q8.xp = xp;
-                hipLaunchKernelGGL((v3::gemm_kernel_p<EPI, false, true>), dim3(cus8), dim3(v3::kThreads3), v3::kLds3, st, q8, blocks);
-                TT_CHECK_LAUNCH();
-                return TT_OK;
-            }
-            if (abl == 6) kern = v3::gemm_kernel_v3<EPI, 46>;
-            if (abl == 7) kern = v3::gemm_kernel_v3<EPI, 47>;   // chunk-major store experiment (output layout differs!)
-            if (abl == 6 || abl == 7) TT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, v3::kLds3));
-        }
-#endif
-        TT_SET_MAX_LDS((v3::gemm_kernel_v3<EPI, 4>), v3::kLds3);
-        GemmParams q = p;
-        // whole-line stores as streaming stores: +1...3 % on the bias-only shapes, -0.7 ms per bench step (with the old 32-byte
-        // runs the same hint cost 18 %: no write combining in L2)
-        static const int nts = TT_DIAG_ENV_INT("TT_GEMM_NT_STORE", 1);
-        q.nt_store = nts;
-        q.sn = SN;
-        static const bool a0 = TT_DIAG_ENV_INT("TT_GEMM_DEBUG_A0", 0) == 1;      // (wrong results: diagnostic library only)
-        if (a0) q.xp |= 0x20000;
-        static const bool head_major = TT_DIAG_ENV_INT("TT_GEMM_HEAD_MAJOR", 0) == 1;   // (another output layout: diagnostic library only)
-        if (head_major) q.xp |= 0x40000;
-        static const int stamp_block = TT_DIAG_ENV_INT("TT_GEMM_STAMP_BLOCK", 0);
-        q.xp |= stamp_block << 20;
-        static const int energy = TT_DIAG_ENV_INT("TT_GEMM_ENERGY", 0);                 // (wrong results: diagnostic library only)
-        if (energy) q.xp |= 0x80000 | ((energy & 15) << 4);
-        {
-            TtProfScope prof(TT_K_GEMM, st);
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(v3::kThreads3), v3::kLds3, st, q);
-        }
-        TT_CHECK_LAUNCH();
-        return TT_OK;
+    const GemmSwitches& sw = gemm_switches();
+    GemmParams q = p;
+    if constexpr (EPI != TT_EPI_VT) {
+        // (skinny: the relay form is for the split-plane stream, 3 K / 32 steps -- on the 16-bit stream one wave's 24 steps in flight
+        // already cover K = 1024 in two round trips and the relay's barriers cost 5-10 %: profiles/r06_relay_ab.log)
+        if (pl.kernel == GemmKernel::Skinny) return run_kernel<gemm_skinny_kernel<EPI, false>>(TT_K_GEMM, dim3(pl.gx, pl.gy), 64, 0, st, q);
     }
-    if constexpr (EPI == TT_EPI_VT) {
+    if (sw.trace) fprintf(stderr, "gemm launch<%d> M=%d N=%d K=%d lda=%d ldc=%d ldr=%d\n", EPI, p.M, p.N, p.K, p.lda, p.ldc, p.ldr);
+    const bool tile128 = pl.kernel == GemmKernel::Staged128 || pl.kernel == GemmKernel::TwoStage128;
+    if (EPI == TT_EPI_VT && tile128) {
         tt_set_error("gemm: internal V^T epilogue needs the 256x256 kernel");
         return TT_E_UNSUPPORTED;
     }
-    const int mt_n = p.M / BM, nt_n = p.N / BN;
-    const int SN = nt_n < 8 ? nt_n : 8, SM = 8;
-    const int supers = ((mt_n + SM - 1) / SM) * ((nt_n + SN - 1) / SN);
-    int blocks = supers * SM * SN;
-    blocks = (blocks + 7) / 8 * 8;
-    // ONE round of 128x128 tiles (a lone caller's 10-pair rerank): the staged kernel (four-stage ring, LDS-DMA issues between the MFMAs)
-    // -- M = 3072: attention output 17 -> 15 us, FFN-down 49 -> 42 us; in two rounds the two-stage kernel's two workgroups per CU win
-    static const int staged16 = TT_DIAG_ENV_INT("TT_GEMM_STAGED16", 1);
-    if (staged16 && staged_enabled() && (long long)mt_n * nt_n <= (staged16 > 1 ? staged16 : tt_cu_count_cached()) && p.K % 64 == 0) {
-        TT_SET_MAX_LDS((gemm_staged_kernel<EPI, false>), kStagedLds);
-        {
-            TtProfScope prof(TT_K_GEMM, st);
-            hipLaunchKernelGGL((gemm_staged_kernel<EPI, false>), dim3(blocks), dim3(kStagedThreads), kStagedLds, st, p);
-        }
-        TT_CHECK_LAUNCH();
-        return TT_OK;
+    if (!tile128) q.sn = pl.grid.sn;
+    switch (pl.kernel) {
+        case GemmKernel::Persistent256:
+            if constexpr (EPI == TT_EPI_GELU)
+                return run_kernel<v3::gemm_kernel_p<EPI>>(TT_K_GEMM, dim3(pl.gx), v3::kThreads3, v3::kLds3, st, q, pl.grid.blocks);
+            break;
+        case GemmKernel::OneTile256:
+            q.nt_store = sw.nt_store;
+            return run_kernel<v3::gemm_kernel_v3<EPI>>(TT_K_GEMM, dim3(pl.gx), v3::kThreads3, v3::kLds3, st, q);
+        case GemmKernel::Staged128:
+            if constexpr (EPI != TT_EPI_VT) return run_kernel<gemm_staged_kernel<EPI, false>>(TT_K_GEMM, dim3(pl.gx), kStagedThreads, kStagedLds, st, q);
+            break;
+        case GemmKernel::TwoStage128:
+            if constexpr (EPI != TT_EPI_VT) return run_kernel<gemm_kernel<EPI>>(TT_K_GEMM, dim3(pl.gx), kGemmThreads, kGemmLds, st, q);
+            break;
+        default: break;
     }
-    auto kern = gemm_kernel<EPI>;
-    TT_SET_MAX_LDS(kern, kGemmLds);
-    {
-        TtProfScope prof(TT_K_GEMM, st);
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(kGemmThreads), kGemmLds, st, p);
-    }
-    TT_CHECK_LAUNCH();
-    return TT_OK;
+    tt_set_error("gemm: internal: the plan names kernel %d, which epilogue %d of 16-bit operands has not", (int)pl.kernel, EPI);
+    return TT_E_UNSUPPORTED;
 }
 
 }  // namespace
 
-bool tt_gemm_skinny_enabled() {
-    static const bool on = TT_DIAG_ENV_INT("TT_GEMM_SKINNY", 1) != 0;
-    return on;
-}
+bool tt_gemm_skinny_enabled() { return gemm_switches().skinny; }
 
 int tt_gemm_launch(const GemmParams& p, int epilogue, hipStream_t st) {
     if (p.M <= 0 || p.N <= 0) return TT_OK;
@@ -2659,74 +2309,57 @@ int tt_gemm_launch(const GemmParams& p, int epilogue, hipStream_t st) {
         }
         GemmParams a = p;
         a.N = p.vt_col0;
-        if (int rc = launch<TT_EPI_BIAS>(a, st)) return rc;
+        if (int rc = launch_fp8<TT_EPI_BIAS>(a, st)) return rc;
         GemmParams b = p;
         b.W = reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(p.W) + (size_t)p.vt_col0 * p.K);
         b.bias = p.bias + p.vt_col0;
         b.w_scale = p.w_scale + p.vt_col0;
         b.N = p.N - p.vt_col0;
         b.vt_col0 = 0;
-        return launch<TT_EPI_VT>(b, st);
+        return launch_fp8<TT_EPI_VT>(b, st);
     }
     if ((p.lda % 8) || (p.ldc % 4) || !p.A || !p.W || !p.C || !p.bias) {
         tt_set_error("gemm: bad leading dimension / null pointer");
         return TT_E_INVALID;
     }
-    if (skinny_shape(p)) {
-        switch (epilogue) {
-            case TT_EPI_BIAS: return launch_skinny<TT_EPI_BIAS>(p, st);
-            case TT_EPI_GELU: return launch_skinny<TT_EPI_GELU>(p, st);
-            case TT_EPI_RESIDUAL:
-                if (!p.residual || p.ldr % 4) { tt_set_error("gemm: residual epilogue without residual"); return TT_E_INVALID; }
-                return launch_skinny<TT_EPI_RESIDUAL>(p, st);
-            case TT_EPI_TANH: return launch_skinny<TT_EPI_TANH>(p, st);
-            case TT_EPI_RELU: return launch_skinny<TT_EPI_RELU>(p, st);
-            case TT_EPI_QKV:
-                if (!p.vt || p.vt_col0 % 16) { tt_set_error("gemm: qkv epilogue without vt"); return TT_E_INVALID; }
-                return launch_skinny<TT_EPI_QKV>(p, st);
-            default: tt_set_error("gemm: unknown epilogue %d", epilogue); return TT_E_INVALID;
-        }
-    }
-    if (p.M % BM || p.N % BN || p.K % BK || p.K <= 0) {
+    // (planned before the shape and the epilogue are checked: the plan is total, and of the epilogue it only asks which one it is;
+    // e4m3 operands plan as such -- never a skinny kernel -- and launch_fp8 validates and plans them again itself)
+    const GemmPlan pl = plan_of(p.fp8 ? GemmForm::Fp8 : GemmForm::Bits16, epilogue, p);
+    const bool skinny = pl.kernel == GemmKernel::Skinny;
+    if (!skinny && (p.M % BM || p.N % BN || p.K % BK || p.K <= 0)) {
         tt_set_error("gemm: M=%d N=%d K=%d must be multiples of %d/%d/%d (or M a multiple of 64 up to 256)", p.M, p.N, p.K, BM, BN, BK);
         return TT_E_UNSUPPORTED;
     }
     switch (epilogue) {
-        case TT_EPI_BIAS: return launch<TT_EPI_BIAS>(p, st);
-        case TT_EPI_GELU: return launch<TT_EPI_GELU>(p, st);
+        case TT_EPI_BIAS: return launch_16<TT_EPI_BIAS>(p, pl, st);
+        case TT_EPI_GELU: return launch_16<TT_EPI_GELU>(p, pl, st);
         case TT_EPI_RESIDUAL:
-            if (!p.residual) { tt_set_error("gemm: residual epilogue without residual"); return TT_E_INVALID; }
-            return launch<TT_EPI_RESIDUAL>(p, st);
-        case TT_EPI_TANH: return launch<TT_EPI_TANH>(p, st);
+            if (!p.residual || (skinny && p.ldr % 4)) { tt_set_error("gemm: residual epilogue without residual"); return TT_E_INVALID; }
+            return launch_16<TT_EPI_RESIDUAL>(p, pl, st);
+        case TT_EPI_TANH: return launch_16<TT_EPI_TANH>(p, pl, st);
         // (ReLU is a bias-grade epilogue: store-bound, so it takes the one-tile kernel's whole-line stores like TT_EPI_BIAS)
-        case TT_EPI_RELU: return launch<TT_EPI_RELU>(p, st);
+        case TT_EPI_RELU: return launch_16<TT_EPI_RELU>(p, pl, st);
         case TT_EPI_QKV: {
-            if (!p.vt) { tt_set_error("gemm: qkv epilogue without vt"); return TT_E_INVALID; }
-            static const int variant = TT_DIAG_ENV_INT("TT_GEMM_VARIANT", 5);
-            const int nv = p.N - p.vt_col0;
-            // (TT_GEMM_QKV_SPLIT=0: one launch with the mixed epilogue -- measured 2 % slower end to end)
-            static const int split = TT_DIAG_ENV_INT("TT_GEMM_QKV_SPLIT", 1);
-            const bool small_grid = (long long)(p.M / v3::BM3) * (p.N / v3::BN3) < 128 && small_grid_v1();
-            if (variant >= 3 && split && !small_grid && p.M % v3::BM3 == 0 && p.vt_col0 % v3::BN3 == 0 && nv % v3::BN3 == 0 &&
-                nv > 0 && p.ldc % 8 == 0 && p.ldvt % 8 == 0) {
-                // Q,K columns: plain bias GEMM; V columns: un-swapped tiles stored transposed (two launches,
-                // same number of tile rounds as one)
+            if (!p.vt || (skinny && p.vt_col0 % 16)) { tt_set_error("gemm: qkv epilogue without vt"); return TT_E_INVALID; }
+            if (!skinny && gemm_qkv_splits(p.M, p.N, p.vt_col0, p.ldc, p.ldvt, gemm_switches())) {
                 GemmParams a = p;
                 a.N = p.vt_col0;
-                if (int rc = launch<TT_EPI_BIAS>(a, st)) return rc;
+                if (int rc = launch_16<TT_EPI_BIAS>(a, plan_of(GemmForm::Bits16, TT_EPI_BIAS, a), st)) return rc;
                 GemmParams b = p;
                 b.W = p.W + (size_t)p.vt_col0 * p.K;
                 b.bias = p.bias + p.vt_col0;
-                b.N = nv;
+                b.N = p.N - p.vt_col0;
                 b.vt_col0 = 0;
-                return launch<TT_EPI_VT>(b, st);
+                return launch_16<TT_EPI_VT>(b, plan_of(GemmForm::Bits16, TT_EPI_VT, b), st);
             }
-            return launch<TT_EPI_QKV>(p, st);
+            return launch_16<TT_EPI_QKV>(p, pl, st);
         }
         default: tt_set_error("gemm: unknown epilogue %d", epilogue); return TT_E_INVALID;
     }
 }
 
+// the one-tile scan kernel takes either survivor list (shared or wave-private)
+constexpr int kLdsScanOne = v3::kLdsScan > v3::kLdsScanW ? v3::kLdsScan : v3::kLdsScanW;
 #ifndef TT_SCAN_PERSIST_DEFAULT
 #define TT_SCAN_PERSIST_DEFAULT 1        // persistent + wave-private lists: -3.6 % per batch (profiles/r03_scan_wave_private_ab.log)
 #endif
@@ -2752,15 +2385,8 @@ int tt_scan_gemm_sample_launch(const uint16_t* corpus, int tiles, int tile_strid
     p.scan_dense_stride = dense_stride;
     p.scan_tile_stride = tile_stride;
     p.sn = 1;
-    const int blocks = (tiles + 31) / 32 * 32;
-    constexpr int kLdsOne = v3::kLdsScan > v3::kLdsScanW ? v3::kLdsScan : v3::kLdsScanW;
-    TT_SET_MAX_LDS((v3::gemm_kernel_v3<TT_EPI_SCAN, 4>), kLdsOne);
-    {
-        TtProfScope prof(TT_K_SCAN_SAMPLE, st);
-        hipLaunchKernelGGL((v3::gemm_kernel_v3<TT_EPI_SCAN, 4>), dim3(blocks), dim3(v3::kThreads3), kLdsOne, st, p);
-    }
-    TT_CHECK_LAUNCH();
-    return TT_OK;
+    const int blocks = tile_grid_256(tiles, 1, 0).blocks;     // super-tiles of 32 row tiles x 1 column tile
+    return run_kernel<v3::gemm_kernel_v3<TT_EPI_SCAN>>(TT_K_SCAN_SAMPLE, dim3(blocks), v3::kThreads3, kLdsScanOne, st, p);
 }
 
 int tt_scan_gemm_launch(const uint16_t* corpus, int64_t rows, int dim, const uint16_t* queries256, const float* thr256,
@@ -2788,8 +2414,7 @@ int tt_scan_gemm_launch(const uint16_t* corpus, int64_t rows, int dim, const uin
     p.scan_cap = cap;
     p.scan_idx_base = idx_base;
     p.sn = 1;
-    const int mt_n = p.M / v3::BM3;
-    int blocks = (mt_n + 31) / 32 * 32;     // super-tiles of 32 row tiles x 1 column tile
+    const int blocks = tile_grid_256(p.M / v3::BM3, 1, 0).blocks;     // super-tiles of 32 row tiles x 1 column tile
     // persistent form (one workgroup per CU walks the row tiles, the K stream never drains): no per-tile prologue and no
     // dispatch gap, and -- unlike the storing epilogues -- nothing of the filter epilogue sits in the vector-memory queue
     // (measured on 10M x 1024, 256 queries: 5.7 ms persistent vs 5.2 ms one tile per workgroup -- the storing epilogues'
@@ -2800,24 +2425,8 @@ int tt_scan_gemm_launch(const uint16_t* corpus, int64_t rows, int dim, const uin
     // wave-private lists, 0 = one tile per workgroup + the workgroup-shared list (round 2's form), default = see below.
     static const int persist = TT_DIAG_ENV_INT("TT_SCAN_GEMM_PERSIST", TT_SCAN_PERSIST_DEFAULT);
     const int cus = tt_cu_count_cached() / 8 * 8;
-    if (persist == 1 && blocks > cus && cus >= 8) {
-        static const int sxp = TT_DIAG_ENV_INT("TT_SCAN_GEMM_XP", 0);
-        p.xp = sxp;      // (experiment switches of the persistent kernel: bit 2 = wave groups NOT aligned at the tile boundary)
-        TT_SET_MAX_LDS(v3::gemm_kernel_p<TT_EPI_SCAN>, v3::kLdsScanW);
-        {
-            TtProfScope prof(TT_K_SCAN_FILTER, st);
-            hipLaunchKernelGGL(v3::gemm_kernel_p<TT_EPI_SCAN>, dim3(cus), dim3(v3::kThreads3), v3::kLdsScanW, st, p, blocks);
-        }
-        TT_CHECK_LAUNCH();
-        return TT_OK;
-    }
-    if (persist != 0) p.xp |= 0x10000;      // wave-private lists in the one-tile kernel
-    constexpr int kLdsOne = v3::kLdsScan > v3::kLdsScanW ? v3::kLdsScan : v3::kLdsScanW;
-    TT_SET_MAX_LDS((v3::gemm_kernel_v3<TT_EPI_SCAN, 4>), kLdsOne);
-    {
-        TtProfScope prof(TT_K_SCAN_FILTER, st);
-        hipLaunchKernelGGL((v3::gemm_kernel_v3<TT_EPI_SCAN, 4>), dim3(blocks), dim3(v3::kThreads3), kLdsOne, st, p);
-    }
-    TT_CHECK_LAUNCH();
-    return TT_OK;
+    if (persist == 1 && blocks > cus && cus >= 8)
+        return run_kernel<v3::gemm_kernel_p<TT_EPI_SCAN>>(TT_K_SCAN_FILTER, dim3(cus), v3::kThreads3, v3::kLdsScanW, st, p, blocks);
+    if (persist != 0) p.scan_wave_lists = 1;      // wave-private lists in the one-tile kernel
+    return run_kernel<v3::gemm_kernel_v3<TT_EPI_SCAN>>(TT_K_SCAN_FILTER, dim3(blocks), v3::kThreads3, kLdsScanOne, st, p);
 }

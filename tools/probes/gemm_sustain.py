@@ -55,5 +55,4 @@ third = marks[len(marks) * 2 // 3:]
 print(f"{mode} ({data} operands): {len(marks) * 20} launches, {flops / (sum(marks) / len(marks) * 1e-3) / 1e12:.0f} TF/s of MFMA work over the window, "
       f"{flops / (sum(third) / len(third) * 1e-3) / 1e12:.0f} in its last third; sclk median {clock['sclk_mhz_median']} MHz "
       f"({clock['sclk_mhz_min']}-{clock['sclk_mhz_max']}), socket power {clock['socket_power_w_mean'] and round(clock['socket_power_w_mean'])} W "
-      f"[{os.environ.get('TT_LIB_NAME', 'libtt_hip.so')} ENERGY={os.environ.get('TT_GEMM_ENERGY')} A0={os.environ.get('TT_GEMM_DEBUG_A0')} "
-      f"TRAFFIC={os.environ.get('TT_GEMM_DEBUG_TRAFFIC')}]")
+      f"[{os.environ.get('TT_LIB_NAME', 'libtt_hip.so')}]")
