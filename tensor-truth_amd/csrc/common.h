@@ -23,7 +23,7 @@
 #endif
 
 // ---- diagnostic build -------------------------------------------------------------------------------------------------------
-// Switches that compute WRONG results by design (ablations of the attention loop, rounding masks of the reference-precision
+// Switches that compute WRONG results by design (ablations of the scan loop, rounding masks of the reference-precision
 // forward, the GEMM traffic / stamp experiments) or re-read the environment on every forward exist only in the diagnostic
 // library, `make DIAG=1` -> libtt_hip_diag.so (tools/ and tools/probes/ load that one: TT_LIB_NAME).  In the product library
 // TT_DIAG_ENV_INT is its default: a stray environment variable cannot change a score, and the ablation instantiations are
