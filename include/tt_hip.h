@@ -1134,6 +1134,23 @@ int tt_t5_pool_dense(const tt_t5_weights* w, const void* hidden, int ld, const i
  *   fp32, so a score does not depend on which other pairs are in the launch.  A negative candidate writes -inf; a document of
  *   length 0 scores 0.  dim a multiple of 32 up to 128 (anything else is refused before a launch); q_len 1 .. 128, d_len 0 .. 512:
  *   the kernel clamps a length into its range, and the host wrapper (colbert.py), which holds the lengths, refuses one outside it.
+ * tt_maxsim_scan_topk: the exact MaxSim top-k over documents 0 .. n_docs-1 for n_q (1 .. 64) queries, k 1 .. 1024, in ONE read of the
+ *   store per pass of queries.  Every score is tt_maxsim's value with cand NULL for the same (query, document), bit for bit: one
+ *   mfma_f32_16x16x32 chain per <Q_i, D_j> over kk = 0 .. dim/32 - 1 from 0 (document rows the A operand, query rows the B operand),
+ *   rows past d_len masked to -inf, the maximum from -inf, the q_len maxima added in index order in fp32 -- so a score does not
+ *   depend on n_q, on the other queries of the call, on where the document sits in the store, or on the wave that scored it.  A
+ *   document of length 0 scores 0 and is a valid result.  alive: uint8 [n_docs], 0 = a tombstone (NULL: every document is live); a
+ *   tombstone is not read, and its slot of the workspace (tt_maxsim_scan_workspace_bytes: n_q rows of n_docs rounded up to 32
+ *   floats, which hold every score after the call) holds NaN, which the selection never returns.  Selection: tt_lexical_scan_topk's
+ *   (tt_scan_topk_exact's).  out_scores / out_idx [n_q][k], ordered by (score descending, document number ascending), padded with
+ *   (-inf, -1); n_docs == 0 writes the padding without a scoring launch.  A persistent grid (two workgroups per compute unit) of
+ *   four-wave workgroups; a wave owns whole documents, two consecutive numbers per step of a static grid-stride walk.  The queries'
+ *   B fragments are staged in LDS, at most 16 blocks of 16 query rows (256 padded rows: 64 KB at dim 128) at a time: queries that
+ *   do not fit are taken in further sweeps of the store inside the same launch (eight 32-token queries, or two 128-token ones, per
+ *   sweep).  Refused before a launch: dim not a multiple of 32 up to 128, n_q outside 1 .. 64, k outside 1 .. 1024
+ *   (TT_E_UNSUPPORTED); n_docs outside 0 .. INT_MAX, a null output, a null array with n_docs > 0 (TT_E_INVALID); a workspace that is
+ *   NULL or too small (TT_E_WORKSPACE).  q_len 1 .. 128 and d_len 0 .. 512 are clamped in the kernel as tt_maxsim clamps them; the
+ *   host wrapper (colbert.py) refuses a value outside.
  * tt_colbert_project: for n < n_out, y = W hidden[rows[n]] (W [dim][H], no bias, fp32 accumulation), out[n] = y / max(||y||_2, 1e-12)
  *   in fp32, rounded once; out [n_out][dim].  Nothing is computed for rows that are not listed; a row number outside [0, n_rows)
  *   and an all-zero row give zeros.  H a multiple of 128 up to 1024, dim as above.
@@ -1145,6 +1162,10 @@ int tt_t5_pool_dense(const tt_t5_weights* w, const void* hidden, int ld, const i
  *   max_len <= 128. */
 int tt_maxsim(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs, const int64_t* d_start,
               const int32_t* d_len, const int32_t* cand, int n_cand, int dim, float* scores, void* stream);
+size_t tt_maxsim_scan_workspace_bytes(int64_t n_docs, int n_q);   /* one size for both element types */
+int tt_maxsim_scan_topk(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs,
+                        const int64_t* d_start, const int32_t* d_len, const uint8_t* alive, int64_t n_docs, int dim, int k,
+                        float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
 int tt_colbert_project(const void* hidden, int n_rows, int H, const void* w, int dim, const int32_t* rows, int n_out, void* out,
                        void* stream);
 int tt_attention_keylimit(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,
@@ -1156,6 +1177,9 @@ int tt_encoder_forward_keylen(const tt_encoder_weights* w, const int32_t* ids, c
 /* the fp16 twins (colbert.hip and encoder_api.hip compiled a second time) */
 int tt_maxsim_f16(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs, const int64_t* d_start,
                   const int32_t* d_len, const int32_t* cand, int n_cand, int dim, float* scores, void* stream);
+int tt_maxsim_scan_topk_f16(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs,
+                            const int64_t* d_start, const int32_t* d_len, const uint8_t* alive, int64_t n_docs, int dim, int k,
+                            float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
 int tt_colbert_project_f16(const void* hidden, int n_rows, int H, const void* w, int dim, const int32_t* rows, int n_out, void* out,
                            void* stream);
 int tt_attention_keylimit_f16(const void* qk, int ld_qk, int q_col0, int k_col0, const void* vt, int ldvt, void* out, int ld_out,

@@ -280,6 +280,11 @@ SIGNATURES = {
     # ColBERT late interaction (csrc/colbert.hip; the key-limited forward is encoder_api.hip's) and the fp16 twins (same signatures)
     "tt_maxsim": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                           c_void_p]),
+    "tt_maxsim_scan_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "tt_maxsim_scan_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_maxsim_scan_topk_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                        c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_colbert_project": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "tt_attention_keylimit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_int, c_int, c_int, c_int, c_void_p]),

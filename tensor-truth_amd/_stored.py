@@ -57,16 +57,17 @@ def rerank_result(scores: Sequence[float], top_n: Optional[int] = None) -> List[
     return [{"index": i, "relevance_score": float(scores[i])} for i in descending(scores, top_n)]
 
 
-def top_nodes(store, lexical, k: int, nodes: Dict[Any, Any], node_type) -> list:
-    """What a lexical or SPLADE retriever returns for ONE encoded query: ``store.search`` (through posting lists, built here if
-    the store has them on and none yet) -> ``node_type(node=nodes[id], score=...)`` of the hits, best first.  Hits with score <= 0
-    -- passages that share no weighted id with the query -- and hits whose id is not in ``nodes`` are dropped."""
-    if store.postings and store.index is None:
+def top_nodes(store, query, k: int, nodes: Dict[Any, Any], node_type, positive_only: bool = True) -> list:
+    """What a lexical, SPLADE or ColBERT retriever returns for ONE encoded query: ``store.search`` (through posting lists, built
+    here if the store has them on and none yet) -> ``node_type(node=nodes[id], score=...)`` of the hits, best first.  Hits whose id
+    is not in ``nodes`` are dropped, and -- ``positive_only``, the sparse retrievers -- hits with score <= 0: passages that share
+    no weighted id with the query.  (A MaxSim sum has no such point: ``HipColbertRetriever`` keeps every hit.)"""
+    if getattr(store, "postings", False) and store.index is None:
         store.seal()
-    scores, idx = store.search(lexical, k)
+    scores, idx = store.search(query, k)
     out = []
     for s, d in zip(scores[0].cpu().tolist(), idx[0].cpu().tolist()):
-        if d < 0 or not s > 0:
+        if d < 0 or (positive_only and not s > 0):
             continue
         node = nodes.get(store.node_id(d))
         if node is not None:

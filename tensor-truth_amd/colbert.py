@@ -1,10 +1,10 @@
-"""Late-interaction (ColBERT) reranking on the HIP path: ``colbert-ir/colbertv2.0`` (768 -> 128),
+"""Late-interaction (ColBERT) reranking and exact retrieval on the HIP path: ``colbert-ir/colbertv2.0`` (768 -> 128),
 ``answerdotai/answerai-colbert-small-v1`` (384, 32-wide heads -> 96) and the same models in PyLate's sentence-transformers layout.
 
 A cross-encoder pushes every (query, passage) pair through the whole encoder at query time.  A late-interaction model encodes a
 passage ONCE, when it is indexed, to one L2-normalised vector per kept token (``TokenVectorStore``, in HBM); at query time only the
 query runs through the encoder and every candidate is scored by MaxSim, ``sum_i max_j <q_i, d_j>``, over vectors already resident
-(``tt_maxsim``).  The encoder is the BERT forward of the 16-bit path (``tt_encoder_forward[_f16]``); a query is padded with
+(``tt_maxsim``) -- or every stored passage is, in one read of the store (``tt_maxsim_scan_topk``, ``HipColbertRetriever``).  The encoder is the BERT forward of the 16-bit path (``tt_encoder_forward[_f16]``); a query is padded with
 ``[MASK]`` tokens that are encoded and scored but -- unless the checkpoint says otherwise -- never attended to
 (``tt_encoder_forward_keylen``); the per-token projection and normalisation is ``tt_colbert_project``.  bf16 (default) or fp16.
 
@@ -39,12 +39,13 @@ import torch
 from . import _lib
 from ._hostargs import _check_range, _dev_i, _need_device, _stream, _suffix, grown, read_json, resolve_device
 from ._hostargs import resolve_dtype as _resolve_dtype
-from ._stored import IdTable, _StoredRerank
+from ._stored import IdTable, _StoredRerank, top_nodes
 from .encoder import Encoder, EncoderConfig, EncoderWeights, _scratch, pack_tokens
 
 logger = logging.getLogger(__name__)
 
 MAX_QUERY_LEN, MAX_DOC_LEN, MAX_DIM = 128, 512, 128      # tt_maxsim's limits (include/tt_hip.h)
+MAX_SCAN_QUERIES, MAX_SCAN_K = 64, 1024                  # tt_maxsim_scan_topk's (queries per call, k)
 
 
 # ---- settings ---------------------------------------------------------------------------------------------------------------------
@@ -423,6 +424,54 @@ def _maxsim(name: str, entry: str, max_q: int, max_d: int, check_dim, trailing: 
     return scores
 
 
+def maxsim_scan_topk(q_vecs: torch.Tensor, q_start, q_len, d_vecs: torch.Tensor, d_start, d_len, k: int, alive=None,
+                     workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``tt_maxsim_scan_topk`` -> (scores fp32 [n_q][k], document numbers int32 [n_q][k]) on the device: the exact MaxSim top-k over
+    every entry of the document arrays in one read of them, ordered by (score descending, document number ascending), padded with
+    (-inf, -1).  Every score is ``maxsim``'s for the same pair, bit for bit.  ``alive``: uint8 [n_docs], 0 = a tombstone that is
+    never returned (None: every document is live).  1 .. 64 queries, k 1 .. 1024; the arrays are checked as ``maxsim``'s.
+    ``workspace``: a caller-owned uint8 device tensor (``tt_maxsim_scan_workspace_bytes``), allocated here when missing or short."""
+    name = "maxsim_scan_topk"
+    _need_device(name, q_vecs, d_vecs)
+    if q_vecs.dtype != d_vecs.dtype or q_vecs.dim() != 2 or d_vecs.dim() != 2 or q_vecs.shape[1] != d_vecs.shape[1]:
+        raise ValueError(f"{name}: query and document vectors must be [*, dim] of one 16-bit type")
+    entry, dim = "tt_maxsim_scan_topk" + _suffix(q_vecs.dtype), int(q_vecs.shape[1])
+    if not (q_vecs.is_contiguous() and d_vecs.is_contiguous()):
+        raise ValueError(f"{name}: row-major vectors with a row stride of dim are needed")
+    n_q, n_docs = len(q_len), len(d_len)
+    if not 1 <= n_q <= MAX_SCAN_QUERIES:
+        raise ValueError(f"{name}: {n_q} queries (1 .. {MAX_SCAN_QUERIES})")
+    if not 1 <= int(k) <= MAX_SCAN_K:
+        raise ValueError(f"{name}: k={k} (1 .. {MAX_SCAN_K})")
+    if not isinstance(q_len, torch.Tensor):
+        _check_range("q_len", q_len, 1, MAX_QUERY_LEN)
+        _check_range("q_start", q_start, 0, q_vecs.shape[0] - np.asarray(q_len))
+    if not isinstance(d_len, torch.Tensor):
+        _check_range("d_len", d_len, 0, MAX_DOC_LEN)
+        _check_range("d_start", d_start, 0, d_vecs.shape[0] - np.asarray(d_len))
+    if alive is not None and len(alive) != n_docs:
+        raise ValueError(f"{name}: alive holds {len(alive)} entries for {n_docs} documents")
+    dev = _need_device(name, q_vecs, d_vecs)
+    qs, ql = _dev_i(q_start, torch.int32, dev), _dev_i(q_len, torch.int32, dev)
+    ds, dl = _dev_i(d_start, torch.int64, dev), _dev_i(d_len, torch.int32, dev)
+    al = None
+    if alive is not None:
+        al = _dev_i(alive, torch.uint8, dev) if isinstance(alive, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(alive, dtype=np.uint8)).to(dev)
+    lib = _lib.load_library()
+    need = int(lib.tt_maxsim_scan_workspace_bytes(n_docs, n_q))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    scores = torch.empty((n_q, int(k)), dtype=torch.float32, device=dev)
+    idx = torch.empty((n_q, int(k)), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = getattr(lib, entry)(q_vecs.data_ptr(), qs.data_ptr(), ql.data_ptr(), n_q, d_vecs.data_ptr(), ds.data_ptr(), dl.data_ptr(),
+                                 al.data_ptr() if al is not None else None, n_docs, dim, int(k), scores.data_ptr(), idx.data_ptr(),
+                                 workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream(dev))
+    _lib.check(rc, entry)
+    return scores, idx
+
+
 def project(hidden: torch.Tensor, weight: torch.Tensor, rows) -> torch.Tensor:
     """``tt_colbert_project`` -> [n_out][dim] in the operands' type: row n = normalize(weight @ hidden[rows[n]])."""
     dev = hidden.device
@@ -584,11 +633,12 @@ class ColbertEncoder:
 # ---- the store ----------------------------------------------------------------------------------------------------------------------
 class TokenVectorStore:
     """Token vectors of indexed passages, in HBM on one device: 2 * dim bytes per kept token (about 46 KB for a 180-token passage
-    at dim 128), plus 12 bytes per passage for its start and length.  ``add`` appends and grows by doubling; ``remove`` frees the
+    at dim 128), plus 13 bytes per passage for its start, its length and its ``alive`` byte.  ``add`` appends and grows by doubling; ``remove`` frees the
     id only -- the rows stay where they are and are NOT reclaimed (there is no compaction in this version; re-adding an id
-    appends a new copy).  No persistence.  Unlike ``LexicalStore`` it writes no tombstone on the device, on ``remove`` or on a
-    re-add: the shared id table forgets the older document number all the same, and nothing here searches the whole store, so a
-    document number no id leads to is never scored."""
+    appends a new copy).  No persistence.  ``search`` is the exact MaxSim top-k over every stored passage
+    (``tt_maxsim_scan_topk``): ``alive`` holds one byte per document number, 1 from ``add``, 0 once the id is removed or added
+    again, and a number whose byte is 0 is never returned.  ``score`` does not read it: a number no id leads to still scores as
+    before through ``tt_maxsim``, it is just never asked for."""
 
     # the limits of the kernel that scores the store (``tt_maxsim``); ``multivec.MultiVectorStore`` carries ``tt_maxsim_wide``'s
     DIM_STEP, DIM_LIMIT, DOC_LIMIT = 32, MAX_DIM, MAX_DOC_LEN
@@ -604,9 +654,11 @@ class TokenVectorStore:
         self.vectors = torch.empty((max(capacity_tokens, 1), dim), dtype=dtype, device=device)
         self.d_start = torch.zeros(max(capacity_docs, 1), dtype=torch.int64, device=device)
         self.d_len = torch.zeros(max(capacity_docs, 1), dtype=torch.int32, device=device)
+        self.alive = torch.zeros(max(capacity_docs, 1), dtype=torch.uint8, device=device)
         self.n_tokens = 0
         self.n_docs = 0
         self._ids = IdTable()
+        self._ws: Optional[torch.Tensor] = None          # search's workspace, grown on demand
 
     def __len__(self) -> int:
         return len(self._ids)
@@ -626,30 +678,41 @@ class TokenVectorStore:
         self.vectors = grown(self.vectors, self.n_tokens, self.n_tokens + total)
         self.d_start = grown(self.d_start, self.n_docs, self.n_docs + n)
         self.d_len = grown(self.d_len, self.n_docs, self.n_docs + n)
+        self.alive = grown(self.alive, self.n_docs, self.n_docs + n)
         starts = np.zeros(n, dtype=np.int64)
         np.cumsum(lens[:-1], out=starts[1:])
         starts += self.n_tokens
         self.vectors[self.n_tokens:self.n_tokens + total].copy_(vectors.to(self.device))
         self.d_start[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(starts))
         self.d_len[self.n_docs:self.n_docs + n].copy_(torch.from_numpy(lens))
+        self.alive[self.n_docs:self.n_docs + n].fill_(1)
         docs = np.arange(self.n_docs, self.n_docs + n, dtype=np.int32)
-        self._ids.assign(node_ids)
+        for old in self._ids.assign(node_ids):           # re-added: the older copy is never returned by ``search`` again
+            self.alive[old:old + 1].fill_(0)
         self.n_tokens += total
         self.n_docs += n
         return docs
 
     def remove(self, node_id: Any) -> bool:
-        """Forget ``node_id`` -> whether it was stored.  Its rows are not reclaimed."""
-        return self._ids.pop(node_id) is not None
+        """Forget ``node_id`` -> whether it was stored.  Its rows are not reclaimed; ``search`` no longer returns its number."""
+        doc = self._ids.pop(node_id)
+        if doc is None:
+            return False
+        self.alive[doc:doc + 1].fill_(0)
+        return True
 
     def lookup(self, node_ids: Sequence[Any]) -> np.ndarray:
         """-> document numbers (int32), -1 for an id that is not stored."""
         return self._ids.lookup(node_ids)
 
+    def node_id(self, doc: int) -> Any:
+        """The node id of document number ``doc`` (None: removed, or no such document)."""
+        return self._ids.node_id(doc)
+
     @property
     def nbytes(self) -> int:
         """Bytes the store holds in HBM (capacity, not fill)."""
-        return sum(t.numel() * t.element_size() for t in (self.vectors, self.d_start, self.d_len))
+        return sum(t.numel() * t.element_size() for t in (self.vectors, self.d_start, self.d_len, self.alive))
 
     def score(self, queries: TokenVectors, cand: np.ndarray) -> torch.Tensor:
         """MaxSim of every query against its row of ``cand`` (document numbers, -1 = none) -> fp32 [n_q][n_cand] (device)."""
@@ -659,12 +722,29 @@ class TokenVectorStore:
         return maxsim(queries.vectors, queries.starts.astype(np.int32), queries.lens, self.vectors, self.d_start[: self.n_docs],
                       self.d_len[: self.n_docs], cand=cand)
 
+    def search(self, queries: TokenVectors, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The exact MaxSim top-k over every stored passage, in one read of the store for up to eight 32-token queries -> (scores
+        fp32 [n_q][k], document numbers int32 [n_q][k]) on the device, ordered by (score descending, document number ascending),
+        padded with (-inf, -1).  A score is ``score``'s for the same pair, bit for bit; removed and replaced numbers are never
+        returned.  A store whose limits exceed the scan's (``MultiVectorStore``) raises ``NotImplementedError``."""
+        if self.DIM_LIMIT > MAX_DIM or self.DOC_LIMIT > MAX_DOC_LEN:
+            raise NotImplementedError(f"{type(self).__name__}.search: the exact MaxSim scan (tt_maxsim_scan_topk) serves dim <= {MAX_DIM} "
+                                      f"and passages of <= {MAX_DOC_LEN} vectors; this store (dim={self.dim}, up to {self.DOC_LIMIT} "
+                                      "vectors per passage) is a rerank-stage store: use score() on candidates")
+        need = int(_lib.load_library().tt_maxsim_scan_workspace_bytes(self.n_docs, len(queries.lens)))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return maxsim_scan_topk(queries.vectors, np.asarray(queries.starts).astype(np.int32), queries.lens, self.vectors,
+                                self.d_start[: self.n_docs], self.d_len[: self.n_docs], k, alive=self.alive[: self.n_docs],
+                                workspace=self._ws)
+
 
 # ---- postprocessor ---------------------------------------------------------------------------------------------------------------
 class HipColbertRerank(_StoredRerank):
     """Late-interaction rerank postprocessor with the surface of ``HipSentenceTransformerRerank``: ``postprocess_nodes`` (keyword
     or positional), ``rerank``, ``predict``, ``.model`` (the weights, with ``.parameters()``) -- plus ``index_nodes``, which
-    encodes nodes' EMBED-mode content into the instance's ``TokenVectorStore``.  At query time a stored node is scored from the
+    encodes nodes' EMBED-mode content into the instance's ``TokenVectorStore`` (and keeps the nodes, for ``HipColbertRetriever``),
+    and ``remove_node``.  At query time a stored node is scored from the
     store and any other node is encoded in the call; both give the same bits for the same text.  Scores are MaxSim sums (of the
     order of the query length), not probabilities."""
 
@@ -696,7 +776,12 @@ class HipColbertRerank(_StoredRerank):
         self.encoder = ColbertEncoder(self.model, cc, tk)
         self.store = TokenVectorStore(cc.dim, dtype, dev)
         self.precision = "fp16 (fp32 accumulate)" if dtype == torch.float16 else "bf16 (fp32 accumulate)"
+        self.nodes: Dict[Any, Any] = {}      # node id -> the indexed node (what HipColbertRetriever returns)
         self.stats = {"queries": 0, "stored": 0, "encoded": 0}
+
+    def remove_node(self, node_id: Any) -> bool:
+        self.nodes.pop(node_id, None)
+        return self.store.remove(node_id)
 
     # ---- what _StoredRerank asks for --------------------------------------------------------------------------------
     def encode_queries(self, texts) -> TokenVectors:
@@ -707,6 +792,7 @@ class HipColbertRerank(_StoredRerank):
 
     def add_documents(self, nodes, tv: TokenVectors) -> None:
         self.store.add([n.id_ for n in nodes], tv.vectors, tv.lens)
+        self.nodes.update((n.id_, n) for n in nodes)
 
     def lookup(self, ids) -> np.ndarray:
         return self.store.lookup(ids)
@@ -716,6 +802,30 @@ class HipColbertRerank(_StoredRerank):
 
     def score_fresh(self, qv: TokenVectors, tv: TokenVectors, cand) -> np.ndarray:
         return maxsim(qv.vectors, qv.starts.astype(np.int32), qv.lens, tv.vectors, tv.starts, tv.lens, cand=cand).cpu().numpy()
+
+
+class HipColbertRetriever:
+    """Exact late-interaction retrieval over the nodes a ``HipColbertRerank`` indexed: ``retrieve(query)`` encodes the query (one
+    key-limited forward), runs ``TokenVectorStore.search`` -- every stored passage is scored, none is approximated -- and returns
+    the best ``similarity_top_k`` stored nodes by MaxSim, best first, with the scores ``postprocess_nodes`` gives the same nodes.
+    Scores are MaxSim sums and are not thresholded: unlike a lexical zero ("no shared term") a MaxSim value has no such point."""
+
+    def __init__(self, reranker: HipColbertRerank, similarity_top_k: int = 10):
+        if not 1 <= int(similarity_top_k) <= MAX_SCAN_K:
+            raise ValueError(f"similarity_top_k={similarity_top_k} (1 .. {MAX_SCAN_K})")
+        self.reranker, self.similarity_top_k = reranker, int(similarity_top_k)
+
+    def retrieve(self, query):
+        from .schema import NodeWithScore, as_query_bundle
+
+        return self._retrieve(as_query_bundle(query), NodeWithScore)
+
+    def _retrieve(self, query_bundle, node_type=None):
+        if node_type is None:
+            from .schema import NodeWithScore as node_type
+        rr = self.reranker
+        qv = rr.encode_queries([query_bundle.query_str])
+        return top_nodes(rr.store, qv, self.similarity_top_k, rr.nodes, node_type, positive_only=False)
 
 
 def synthetic_state(cfg: EncoderConfig, dim: int, seed: int = 0) -> Dict[str, torch.Tensor]:

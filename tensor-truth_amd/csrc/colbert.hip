@@ -1,17 +1,21 @@
-// Late-interaction (ColBERT) reranking: the three kernels only this family needs (include/tt_hip.h, "ColBERT late interaction").
+// Late-interaction (ColBERT) reranking and retrieval: the kernels only this family needs (include/tt_hip.h, "ColBERT late interaction").
 //   tt_maxsim              scores[q][c] = sum_i max_j <Q_i, D_j> over token vectors that already sit in device memory
+//   tt_maxsim_scan_topk    that score for every stored document in one read of the store, then the library's exact selection (select.hip)
 //   tt_colbert_project     v = normalize(W h) for the listed rows of a hidden state, one rounding to the element type
 //   tt_attention_keylimit  attention in which every row of a sequence is a query and only its first key_len rows are keys
 //                          (a ColBERT query: [MASK] expansion tokens are encoded and scored, never attended to)
 // The encoder itself is encoder_api.hip's (tt_encoder_forward_keylen: the BERT forward with the third kernel in every layer).
 //
-// All three are one-wave MFMA tiles without LDS staging: a lane's operand fragment of mfma_f32_16x16x32 is 16 contiguous bytes of one
-// row.  The layout is attention_tile's (varlen.h): A rows on lane & 15, K offset 8 (lane >> 4); the accumulator of lane l holds rows
+// All but the scan (which stages its queries in LDS) are one-wave MFMA tiles without LDS staging: a lane's operand fragment of
+// mfma_f32_16x16x32 is 16 contiguous bytes of one row.  The layout is attention_tile's (varlen.h): A rows on lane & 15, K offset 8 (lane >> 4); the accumulator of lane l holds rows
 // 4 (l >> 4) + i, i = 0..3, of column l & 15.
 //
 // Compiled twice like the encoder path (common.h TT_F16): bf16 and fp16 (external names with an _f16 suffix, f16_names.h).
 #include "common.h"
 #include "encoder.h"
+#include "scan.h"
+
+#include <limits.h>
 
 #include <algorithm>
 
@@ -82,6 +86,168 @@ __global__ __launch_bounds__(64 * kMaxsimWaves) void maxsim_kernel(const uint16_
         float acc = 0.f;
         for (int i = 0; i < ql; ++i) acc += tok_max[i];
         *dst = acc;
+    }
+}
+
+// ---- MaxSim over the whole store ----------------------------------------------------------------------------------------------
+// tt_maxsim_scan_topk's scoring pass: every document is read ONCE and scored against every query of the pass.  A persistent grid of
+// four-wave workgroups; a wave owns whole documents, taken in a static grid-stride walk over chunks of kScanChunk consecutive document
+// numbers -- no atomics, nothing crosses a wave.
+//   Queries: the B fragments of up to kScanBlocks 16-token query blocks (256 padded query rows: 64 KB at dim 128, the LDS budget of a
+//     pass) are staged once per workgroup in fragment order -- qfrag[(block * DIM/32 + kk) * 64 + lane] is the 16 bytes lane `lane`
+//     feeds the MFMA, so a wave's ds_read_b128 covers 1 KB of consecutive addresses (conflict-free).  Rows past q_len are zeros, as in
+//     maxsim_kernel.  Queries that do not fit are taken by further passes INSIDE the launch (the lengths live on the device; every
+//     workgroup plans the same split): each pass is one sweep of the store into its own workspace rows.
+//   Documents: a 16-token tile is loaded once into registers as A fragments (16 contiguous bytes of one row per lane and kk, as in
+//     maxsim_kernel) and reused against every block of the pass; the NEXT tile of the wave's walk -- of this document or of the next
+//     live one -- is loaded into a second register buffer before the current tile's MFMAs are issued.
+//   Per (query block, lane) one running maximum in a register.  At a document's last tile the maxima are finished across the four lane
+//     groups (wave_max16), go to the wave's own LDS strip, and lane j adds the q_len maxima of the pass's query j in index order in
+//     fp32.  The chain per <Q_i, D_j>, the masking, the order of the fmaxf calls per lane and the sum are maxsim_kernel's: the same bits.
+//   A dead document (alive[doc] == 0) writes NaN without being read; a live one of length 0 writes 0.
+constexpr int kScanWaves = 4;       // waves per workgroup
+constexpr int kScanChunk = 2;       // consecutive documents a wave takes per step of its walk
+constexpr int kScanBlocks = 16;     // 16-token query blocks per pass
+constexpr int kScanWgPerCu = 2;     // workgroups the grid holds per compute unit: 2 x (64 KB of fragments + 6 KB) of its 160 KB
+constexpr int kScanMaxQueries = 64;
+
+template <int DIM>
+__global__ __launch_bounds__(64 * kScanWaves) void maxsim_scan_kernel(const uint16_t* __restrict__ qv, const int32_t* __restrict__ q_start,
+                                                                      const int32_t* __restrict__ q_len, int n_q,
+                                                                      const uint16_t* __restrict__ dv, const int64_t* __restrict__ d_start,
+                                                                      const int32_t* __restrict__ d_len, const uint8_t* __restrict__ alive,
+                                                                      int n_docs, float* __restrict__ ws, int64_t stride) {
+    constexpr int KK = DIM / 32;
+    __shared__ uint4 qfrag[kScanBlocks * KK * 64];
+    __shared__ float tok_max[kScanWaves][16 * kScanBlocks + kScanMaxQueries];   // (query j's maxima start j words late: no bank is shared)
+    __shared__ int q_first[kScanMaxQueries], q_rows[kScanMaxQueries];           // per query of the pass: its first block, its length
+    __shared__ int blk_q[kScanBlocks], blk_row[kScanBlocks];                    // per block: its query within the pass, its first row
+    __shared__ int pass_end, pass_blocks;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c = lane & 15, g = lane >> 4;
+    const int64_t n_waves = (int64_t)gridDim.x * kScanWaves;
+    const uint4 zero4 = uint4{0u, 0u, 0u, 0u};
+    float* tm = tok_max[wave];
+
+    for (int q_lo = 0; q_lo < n_q;) {   // (workgroup-uniform: one pass per turn)
+        if (threadIdx.x == 0) {
+            int nb = 0, q = q_lo;
+            for (; q < n_q; ++q) {
+                const int ql = min(max(q_len[q], 0), kMaxQueryLen), b = (ql + 15) >> 4;
+                if (nb + b > kScanBlocks) break;   // (a query holds at most 8 blocks: every pass takes at least one)
+                q_first[q - q_lo] = nb;
+                q_rows[q - q_lo] = ql;
+                for (int i = 0; i < b; ++i) {
+                    blk_q[nb + i] = q - q_lo;
+                    blk_row[nb + i] = 16 * i;
+                }
+                nb += b;
+            }
+            pass_end = q;
+            pass_blocks = nb;
+        }
+        __syncthreads();
+        const int q_hi = __builtin_amdgcn_readfirstlane(pass_end), nb = __builtin_amdgcn_readfirstlane(pass_blocks), nq = q_hi - q_lo;
+        for (int idx = threadIdx.x; idx < nb * KK * 64; idx += 64 * kScanWaves) {
+            const int l = idx & 63, kk = (idx >> 6) % KK, b = (idx >> 6) / KK;
+            const int qi = blk_q[b], row = blk_row[b] + (l & 15);
+            uint4 u = zero4;
+            if (row < q_rows[qi])
+                u = *reinterpret_cast<const uint4*>(qv + ((size_t)q_start[q_lo + qi] + row) * DIM + kk * 32 + 8 * (l >> 4));
+            qfrag[idx] = u;
+        }
+        __syncthreads();
+
+        // the wave's walk, one tile ahead: (doc, d0) is the tile that is loaded next
+        int64_t chunk = (int64_t)blockIdx.x * kScanWaves + wave - n_waves;
+        int in_chunk = kScanChunk - 1, doc = -1, dl = 0, d0 = 0;
+        bool more = true;
+        const uint16_t* base = dv;
+        auto advance = [&]() {
+            d0 += 16;
+            while (d0 >= dl) {
+                if (++in_chunk == kScanChunk) {
+                    in_chunk = 0;
+                    chunk += n_waves;
+                }
+                const int64_t d = chunk * kScanChunk + in_chunk;
+                if (d >= n_docs) {
+                    more = false;
+                    return;
+                }
+                doc = (int)d;
+                const bool live = !alive || alive[doc] != 0;
+                dl = live ? min(max(d_len[doc], 0), kMaxDocLen) : 0;
+                d0 = 0;
+                if (dl == 0) {
+                    if (lane < nq) ws[(size_t)(q_lo + lane) * stride + doc] = live ? 0.f : __builtin_nanf("");
+                } else {
+                    base = dv + (size_t)d_start[doc] * DIM + 8 * g;
+                }
+            }
+        };
+        auto load = [&](uint4(&a)[KK]) {
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk)
+                a[kk] = d0 + c < dl ? *reinterpret_cast<const uint4*>(base + (size_t)(d0 + c) * DIM + kk * 32) : zero4;
+        };
+
+        float m[kScanBlocks];
+#pragma unroll
+        for (int b = 0; b < kScanBlocks; ++b) m[b] = -INFINITY;
+        uint4 a0[KK], a1[KK];
+        advance();
+        bool have = more;
+        if (have) load(a0);
+        while (have) {   // (wave-uniform)
+            const int cdoc = doc, cdl = dl, cd0 = d0;
+            advance();
+            if (more) load(a1);
+#pragma unroll
+            for (int b = 0; b < kScanBlocks; ++b) {
+                if (b < nb) {
+                    f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int kk = 0; kk < KK; ++kk)
+                        s = TT_MFMA_16x16x32(__builtin_bit_cast(ex8, a0[kk]), __builtin_bit_cast(ex8, qfrag[(b * KK + kk) * 64 + lane]), s);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) m[b] = fmaxf(m[b], cd0 + 4 * g + i < cdl ? s[i] : -INFINITY);
+                }
+            }
+            if (cd0 + 16 >= cdl) {   // the document's last tile: finish its maxima and add them up
+#pragma unroll
+                for (int b = 0; b < kScanBlocks; ++b) {
+                    if (b < nb) {
+                        const float v = wave_max16(m[b]);
+                        if (g == 0) tm[16 * b + c + blk_q[b]] = v;
+                        m[b] = -INFINITY;
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                if (lane < nq) {
+                    const float* t = tm + 16 * q_first[lane] + lane;
+                    const int n = q_rows[lane];
+                    float acc = 0.f;
+                    for (int i = 0; i < n; ++i) acc += t[i];
+                    ws[(size_t)(q_lo + lane) * stride + cdoc] = acc;
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+            }
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) a0[kk] = a1[kk];
+            have = more;
+        }
+        __syncthreads();   // (the next pass restages the fragments and the tables)
+        q_lo = q_hi;
+    }
+}
+
+__global__ void maxsim_scan_pad_kernel(float* __restrict__ out_scores, int32_t* __restrict__ out_idx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        out_scores[i] = -INFINITY;
+        out_idx[i] = -1;
     }
 }
 
@@ -289,6 +455,80 @@ int tt_maxsim(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, 
     }
     TT_CHECK_LAUNCH();
     return TT_OK;
+}
+
+#if !TT_F16
+size_t tt_maxsim_scan_workspace_bytes(int64_t n_docs, int n_q) {
+    if (n_docs < 0 || n_q <= 0) return 0;
+    const int64_t stride = (n_docs + 31) / 32 * 32;
+    return tt_align_up((size_t)n_q * stride * sizeof(float), 256);
+}
+#endif
+
+int tt_maxsim_scan_topk(const void* q_vecs, const int32_t* q_start, const int32_t* q_len, int n_q, const void* d_vecs,
+                        const int64_t* d_start, const int32_t* d_len, const uint8_t* alive, int64_t n_docs, int dim, int k,
+                        float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* name = kF16 ? "tt_maxsim_scan_topk_f16" : "tt_maxsim_scan_topk";
+    if (dim <= 0 || dim % 32 || dim > kMaxDim) {
+        tt_set_error("%s: dim=%d must be a multiple of 32 and <= %d", name, dim, kMaxDim);
+        return TT_E_UNSUPPORTED;
+    }
+    if (n_q < 1 || n_q > kScanMaxQueries || k < 1 || k > 1024) {
+        tt_set_error("%s: n_q=%d (1 .. %d), k=%d (1 .. 1024)", name, n_q, kScanMaxQueries, k);
+        return TT_E_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(n_docs >= 0 && n_docs <= INT_MAX, "%s: n_docs=%lld", name, (long long)n_docs);
+    TT_CHECK_ARG(out_scores && out_idx, "%s: null output", name);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_docs == 0) {
+        const int64_t n = (int64_t)n_q * k;
+        hipLaunchKernelGGL(maxsim_scan_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out_scores, out_idx, n);
+        TT_CHECK_LAUNCH();
+        return TT_OK;
+    }
+    TT_CHECK_ARG(q_vecs && q_start && q_len && d_vecs && d_start && d_len, "%s: null pointer", name);
+    const size_t need = tt_maxsim_scan_workspace_bytes(n_docs, n_q);
+    if (!workspace || workspace_bytes < need) {
+        tt_set_error("%s: workspace %zu < required %zu bytes", name, workspace_bytes, need);
+        return TT_E_WORKSPACE;
+    }
+    const int cus = tt_cu_count_cached();
+    TT_CHECK_ARG(cus > 0, "%s: no device", name);
+    const int64_t stride = (n_docs + 31) / 32 * 32;
+    float* dense = (float*)workspace;
+    // a persistent grid: kScanWgPerCu workgroups per compute unit, never more than there are chunks for their waves
+    const int64_t chunks = (n_docs + kScanChunk - 1) / kScanChunk;
+    const int grid = (int)std::min<int64_t>((int64_t)cus * kScanWgPerCu, (chunks + kScanWaves - 1) / kScanWaves);
+    const uint16_t* q = (const uint16_t*)q_vecs;
+    const uint16_t* d = (const uint16_t*)d_vecs;
+    {
+        TtProfScope prof(TT_K_ROWOPS, st);
+#define TT_MAXSIM_SCAN(D)                                                                                                        \
+    hipLaunchKernelGGL(maxsim_scan_kernel<D>, dim3(grid), dim3(64 * kScanWaves), 0, st, q, q_start, q_len, n_q, d, d_start, d_len, \
+                       alive, (int)n_docs, dense, stride)
+        switch (dim) {
+            case 32: TT_MAXSIM_SCAN(32); break;
+            case 64: TT_MAXSIM_SCAN(64); break;
+            case 96: TT_MAXSIM_SCAN(96); break;
+            default: TT_MAXSIM_SCAN(128); break;
+        }
+#undef TT_MAXSIM_SCAN
+        TT_CHECK_LAUNCH();
+    }
+    // the lexical scan's selection: a dead document's slot holds NaN, which the selection's key rejects
+    SelectParams se{};
+    se.scores = dense;
+    se.idx = nullptr;
+    se.stride = stride;
+    se.cnt = nullptr;
+    se.m_fixed = (int)n_docs;
+    se.cap = INT_MAX;
+    se.idx_base = 0;
+    se.k = k;
+    se.out_scores = out_scores;
+    se.out_idx = out_idx;
+    se.out_stride = k;
+    return tt_select_launch(se, n_q, st);
 }
 
 int tt_colbert_project(const void* hidden, int n_rows, int H, const void* w, int dim, const int32_t* rows, int n_out, void* out,

@@ -75,6 +75,7 @@
 #define tt_attention_alibi tt_attention_alibi_f16
 // colbert.hip a second time: late-interaction scoring, projection and key-limited attention in fp16
 #define tt_maxsim tt_maxsim_f16
+#define tt_maxsim_scan_topk tt_maxsim_scan_topk_f16
 #define tt_colbert_project tt_colbert_project_f16
 #define tt_attention_keylimit tt_attention_keylimit_f16
 // lexical.hip a second time: the lexical weights of an fp16 hidden state (the scores are fp32 / bf16 by definition: compiled once)

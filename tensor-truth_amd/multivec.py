@@ -253,7 +253,8 @@ class MultiVectorStore(TokenVectorStore):
     """``TokenVectorStore`` with ``tt_maxsim_wide``'s limits: dim a multiple of 128 up to 1024, passages of up to 8192 vectors,
     queries of up to 512.  2 * dim bytes per kept token plus 12 bytes per passage -- about 369 KB for a 180-token passage at dim
     1024, some 700 k such passages in 288 GB: a rerank-stage store for a working set, not the corpus.  ``add``, ``remove``,
-    ``lookup`` and ``nbytes`` are the base class's."""
+    ``lookup`` and ``nbytes`` are the base class's.  ``search`` raises ``NotImplementedError``: the exact MaxSim scan
+    (``tt_maxsim_scan_topk``) serves dim <= 128 and passages of <= 512 vectors, so the 1024-wide head stays a rerank-stage store."""
 
     DIM_STEP, DIM_LIMIT, DOC_LIMIT = DIM_STEP, MAX_DIM, MAX_DOC_LEN
 
