@@ -1233,7 +1233,28 @@ int tt_encoder_forward_keylen_f16(const tt_encoder_weights* w, const int32_t* id
  *   tt_lexical_score's bits with cand NULL, written to the workspace (tt_lexical_scan_workspace_bytes: n_q rows of n_docs rounded
  *   up to 32 floats); a tombstone's slot holds NaN there, which the selection never returns (what a deleted row of the dense
  *   index scores).  Selection: tt_scan_topk_exact's.  out_scores / out_idx [n_q][k], ordered by (score descending, document
- *   number ascending), padded with (-inf, -1); a document that shares no id with the query scores 0 and is a valid result. */
+ *   number ascending), padded with (-inf, -1); a document that shares no id with the query scores 0 and is a valid result.
+ * tt_hybrid_scan_topk: the exact top-k by the hybrid score over documents 0 .. n_docs-1 for n_q (1 .. 64) queries, k 1 .. 1024, in
+ *   ONE read of the store per pass of queries.  Every score is tt_lexical_score's out_hybrid for the same (query, document) with
+ *   cand NULL, bit for bit: the lexical sum (lane l: the document's entries l, l + 64, ..., fmaf(q_w, d_w, acc), then the
+ *   butterfly), the dense sum (lane l: elements 128 c + 2 l, + 1 for ascending c, bf16 operands converted to fp32, fmaf, the same
+ *   butterfly) and the one mixing expression both kernels share -- so a score does not depend on n_q, on the other queries of the
+ *   call, on the pass a query falls into, on where the document sits in the store, or on the wave that scored it.  The operands
+ *   are tt_lexical_score's; q_dense [n_q][dim] and d_dense [n_docs][dim] bf16 are required.  After the call the workspace
+ *   (tt_hybrid_scan_workspace_bytes: n_q rows of n_docs rounded up to 32 floats, tt_lexical_scan_workspace_bytes's rule) holds
+ *   every score.  A tombstone (d_nnz < 0) writes NaN to its slot, which the selection never returns; neither its dense row nor its
+ *   entries are read.  A live document with d_nnz == 0 scores the formula with lex = 0 and is a valid result.  Selection:
+ *   tt_lexical_scan_topk's.  out_scores / out_idx [n_q][k], ordered by (score descending, document number ascending), padded with
+ *   (-inf, -1); n_docs == 0 writes the padding without a scoring launch.  A persistent grid (three workgroups per compute unit) of
+ *   four-wave workgroups; a wave owns whole documents, four consecutive numbers per step of a static grid-stride walk, loads each
+ *   once into registers and scores it against every query of the pass; the pass's queries (entries and bf16 dense rows) are staged
+ *   once per workgroup in LDS.  max_q_nnz_host (>= every q_nnz; the wrapper holds the lengths) sizes a query's slot: up to 64 ids,
+ *   16 queries per pass (at most 40 KB of LDS); up to 512 ids, 8 per pass (at most 48 KB); the host launches one sweep per pass
+ *   into the pass's own workspace rows.  Refused before a launch: dim not a multiple of 128 up to 1024, n_q outside 1 .. 64, k
+ *   outside 1 .. 1024, max_q_nnz_host outside 0 .. 512 (TT_E_UNSUPPORTED); n_docs outside 0 .. INT_MAX, a null output, a negative
+ *   weight or weights that sum to 0, and with n_docs > 0 a null q_dense, d_dense or array (TT_E_INVALID); a workspace that is NULL
+ *   or too small (TT_E_WORKSPACE).  q_nnz and d_nnz are clamped in the kernel as tt_lexical_score clamps them (a q_nnz beyond
+ *   max_q_nnz_host's class is cut to the class); the host wrapper (lexical.py) refuses a value outside. */
 int tt_lexical_weights(const void* hidden, int n_rows, int ld, int H, const void* w, float bias_host, const int32_t* ids,
                        const int32_t* seq_start, const int32_t* seq_len, int n_seq, int max_len, int skip0_host, int skip1_host,
                        int skip2_host, int skip3_host, int32_t* out_terms, float* out_weights, int32_t* out_nnz, void* stream);
@@ -1251,6 +1272,12 @@ size_t tt_lexical_scan_workspace_bytes(int64_t n_docs, int n_q);
 int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
                          const int32_t* d_terms, const float* d_weights, const int64_t* d_start, const int32_t* d_nnz, int64_t n_docs,
                          int k, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+size_t tt_hybrid_scan_workspace_bytes(int64_t n_docs, int n_q);
+int tt_hybrid_scan_topk(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                        int max_q_nnz_host, const int32_t* d_terms, const float* d_weights, const int64_t* d_start,
+                        const int32_t* d_nnz, int64_t n_docs, const void* q_dense, const void* d_dense, int dim, float w_dense,
+                        float w_lex, int k, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ---- Posting lists: an exact candidate generator for the lexical scan (csrc/postings.hip) --------------------------------------
  * tt_lexical_scan_topk scores every document for every query.  A document that shares no id with a query scores +0 (or is a

@@ -309,6 +309,10 @@ SIGNATURES = {
     "tt_lexical_scan_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "tt_lexical_scan_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                      c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tt_hybrid_scan_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "tt_hybrid_scan_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
     # posting lists over the lexical / SPLADE stores (csrc/postings.hip): the build, and the scan's top-k over a query's lists
     "tt_postings_build_workspace_bytes": (c_size_t, [c_int]),
     "tt_postings_build": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p,

@@ -57,14 +57,18 @@ def rerank_result(scores: Sequence[float], top_n: Optional[int] = None) -> List[
     return [{"index": i, "relevance_score": float(scores[i])} for i in descending(scores, top_n)]
 
 
-def top_nodes(store, query, k: int, nodes: Dict[Any, Any], node_type, positive_only: bool = True) -> list:
+def top_nodes(store, query, k: int, nodes: Dict[Any, Any], node_type, positive_only: bool = True, search=None) -> list:
     """What a lexical, SPLADE or ColBERT retriever returns for ONE encoded query: ``store.search`` (through posting lists, built
     here if the store has them on and none yet) -> ``node_type(node=nodes[id], score=...)`` of the hits, best first.  Hits whose id
     is not in ``nodes`` are dropped, and -- ``positive_only``, the sparse retrievers -- hits with score <= 0: passages that share
-    no weighted id with the query.  (A MaxSim sum has no such point: ``HipColbertRetriever`` keeps every hit.)"""
-    if getattr(store, "postings", False) and store.index is None:
-        store.seal()
-    scores, idx = store.search(query, k)
+    no weighted id with the query.  (A MaxSim sum has no such point: ``HipColbertRetriever`` keeps every hit.)  ``search``: a
+    callable ``(query, k) -> (scores, idx)`` to run instead of ``store.search`` (``HipM3HybridRetriever``: the store's hybrid
+    scan, which uses no posting lists -- none are built for it)."""
+    if search is None:
+        if getattr(store, "postings", False) and store.index is None:
+            store.seal()
+        search = store.search
+    scores, idx = search(query, k)
     out = []
     for s, d in zip(scores[0].cpu().tolist(), idx[0].cpu().tolist()):
         if d < 0 or (positive_only and not s > 0):

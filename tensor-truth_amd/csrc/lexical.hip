@@ -4,6 +4,8 @@
 //   tt_lexical_score               lex[q][c] = sum over shared ids of q_w * d_w, the dense dot product and their weighted mean, over
 //                                  entries that already sit in device memory
 //   tt_lexical_scan_topk           that lexical score for every stored document, then the library's exact selection (select.hip)
+//   tt_hybrid_scan_topk            the hybrid score of tt_lexical_score for every stored document in one read of the store per pass
+//                                  of queries, then the same selection
 //   tt_lexical_score_lists         (internal, scan.h) the scan's lexical scores over per-query candidate lists, for postings.hip
 //
 // Compiled twice like the encoder path (common.h TT_F16): the bf16 object holds everything; the fp16 object only
@@ -174,6 +176,15 @@ __global__ __launch_bounds__(DedupShape<NCAP>::threads) void lexical_dedup_kerne
 constexpr int kScoreWaves = 4;
 constexpr int kMaxQueryNnz = 512, kMaxDocNnz = 8192;
 
+// the hybrid score of one pair, (w_dense * dense + w_lex * lex) / (w_dense + w_lex): ONE expression, shared by lexical_score_kernel
+// and hybrid_scan_kernel.  The fusion is spelled out -- the dense product rounded, the lexical one fused into the addition, which is
+// what the compiler made of the plain expression in lexical_score_kernel -- because left to -ffp-contract=fast the choice of the
+// fused product depends on the code around the expression: inlined into hybrid_scan_kernel the same line fused the OTHER product,
+// one ulp apart wherever lex != 0 (measured, tests/test_hybrid_scan_gpu.py).
+__device__ __forceinline__ float hybrid_mix(float w_dense, float dense, float w_lex, float lex) {
+    return fmaf(w_lex, lex, w_dense * dense) / (w_dense + w_lex);
+}
+
 __global__ __launch_bounds__(64 * kScoreWaves) void lexical_score_kernel(
     const int32_t* __restrict__ q_terms, const float* __restrict__ q_weights, const int32_t* __restrict__ q_start,
     const int32_t* __restrict__ q_nnz, const int32_t* __restrict__ d_terms, const float* __restrict__ d_weights,
@@ -244,8 +255,192 @@ __global__ __launch_bounds__(64 * kScoreWaves) void lexical_score_kernel(
         if (lane == 0) {
             out_lex[o] = lex;
             out_dense[o] = dense;
-            out_hybrid[o] = (w_dense * dense + w_lex * lex) / (w_dense + w_lex);
+            out_hybrid[o] = hybrid_mix(w_dense, dense, w_lex, lex);
         }
+    }
+}
+
+// ---- the hybrid score over the whole store ------------------------------------------------------------------------------------
+// tt_hybrid_scan_topk's scoring pass: every document is read ONCE and scored against every query of the pass.  A persistent grid
+// (kHybWgPerCu workgroups per compute unit) of four-wave workgroups; a wave owns whole documents, taken in a static grid-stride
+// walk over runs of kHybRun consecutive document numbers -- no atomics, nothing crosses a wave, so which wave scores a document
+// cannot matter.
+//   Queries: the pass's entries (ids and weights as lexical_score_kernel stores them, QCAP slots per query: 64 or 512) and dense
+//     rows are staged once per workgroup in LDS.  A dense row stays bf16, as it lies in memory: word 64 c + l of a row is the pair
+//     (128 c + 2 l, + 1) that lane l owns in chunk c, so a wave's read of one query's chunk covers 256 consecutive bytes
+//     (conflict-free); the pair is converted to fp32 where it is used.
+//   Documents: a run's live documents are loaded once -- the dense row as <= 8 converted register pairs per lane, entries lane,
+//     lane + 64, .. lane + 192 of the CSR entry (its first 256 ids and weights) as kHybRegs more pairs -- before the first of them is
+//     scored, and reused against every query of the pass.  Entries 256 and up stream from memory per query (the caches hold
+//     them), in lexical_score_kernel's order.  The run's d_nnz and d_start were fetched one step of the walk earlier.
+//   Per pair the two sums are lexical_score_kernel's: lane l adds the matches of entries l, l + 64, ... by fmaf(q_w, d_w, acc), the
+//     products of elements 128 c + 2 l, + 1 for ascending c by fmaf, x then y; wave_sum joins the lanes.  The bisections of a
+//     lane's register entries run side by side (the same comparisons as one after the other; their LDS reads overlap); the
+//     matches are added in entry order.  Every lane then holds the
+//     pair's sums; lane kHybRun * q + r keeps those of (query q of the pass, document r of the run), mixes them once (hybrid_mix)
+//     and stores: a query's run is 16 consecutive bytes of its workspace row.  A tombstone (d_nnz < 0) is not read and writes NaN.
+constexpr int kHybWaves = 4;        // waves per workgroup
+constexpr int kHybRun = 4;          // consecutive documents a wave takes per step of its walk
+constexpr int kHybRegs = 4;         // entries of a document a lane holds in registers: its first 256 ids and weights in all
+constexpr int kHybWgPerCu = 3;      // workgroups the grid holds per compute unit (3 x <= 49 KB of its 160 KB of LDS)
+constexpr int kHybShort = 64;       // the short class of max_q_nnz_host: a query's LDS slot holds 64 ids; the long one kMaxQueryNnz
+// queries per pass: kHybRun x this many (query, document) slots are the wave's 64 lanes, or half of them
+template <int QCAP>
+struct HybPass {
+    static constexpr int queries = QCAP <= kHybShort ? 16 : 8;
+};
+
+// acc + q_w * d_w if the query holds id t (lexical_score_kernel's bisection and fmaf)
+__device__ __forceinline__ float hybrid_match(const int32_t* qt, const float* qw, int nq, int32_t t, const float* dw, float acc) {
+    int lo = 0, hi = nq;   // first query position whose id is >= t
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (qt[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    if (lo < nq && qt[lo] == t) acc = fmaf(qw[lo], *dw, acc);
+    return acc;
+}
+
+// DC: the dense row's chunks of 128 elements the registers hold (2, 4 or 8: dim <= 256, 512, 1024); QCAP: ids per query slot
+template <int DC, int QCAP>
+__global__ __launch_bounds__(64 * kHybWaves) void hybrid_scan_kernel(
+    const int32_t* __restrict__ q_terms, const float* __restrict__ q_weights, const int32_t* __restrict__ q_start,
+    const int32_t* __restrict__ q_nnz, int n_q, const int32_t* __restrict__ d_terms, const float* __restrict__ d_weights,
+    const int64_t* __restrict__ d_start, const int32_t* __restrict__ d_nnz, int n_docs, const uint16_t* __restrict__ q_dense,
+    const uint16_t* __restrict__ d_dense, int dim, float w_dense, float w_lex, float* __restrict__ ws, int64_t stride) {
+    constexpr int QP = HybPass<QCAP>::queries;
+    __shared__ int32_t qt[QP * QCAP];
+    __shared__ float qw[QP * QCAP];
+    __shared__ uint32_t qd[QP * DC * 64];
+    __shared__ int qn[QP];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int chunks = dim >> 7, row_words = dim >> 1;
+    // n_q <= QP: the queries of this pass (the host loops over passes)
+    for (int q = 0; q < n_q; ++q) {
+        const int nq = min(min(max(q_nnz[q], 0), kMaxQueryNnz), QCAP);   // (QCAP: max_q_nnz_host promised no more)
+        const int qs = q_start[q];
+        for (int i = threadIdx.x; i < nq; i += 64 * kHybWaves) {
+            qt[q * QCAP + i] = q_terms[qs + i];
+            qw[q * QCAP + i] = q_weights[qs + i];
+        }
+        for (int i = threadIdx.x; i < row_words; i += 64 * kHybWaves)
+            qd[q * DC * 64 + i] = reinterpret_cast<const uint32_t*>(q_dense + (size_t)q * dim)[i];
+        if (threadIdx.x == 0) qn[q] = nq;
+    }
+    __syncthreads();
+
+    // lane kHybRun * q + r keeps the sums of (query q, document r of the run)
+    const int my_q = lane / kHybRun, my_r = lane % kHybRun;
+    const int64_t n_runs = ((int64_t)n_docs + kHybRun - 1) / kHybRun, n_waves = (int64_t)gridDim.x * kHybWaves;
+    // a run's lengths and starts are fetched one step of the walk ahead: the loads of its rows and entries then wait for nothing
+    int dn_next[kHybRun];
+    int64_t ds_next[kHybRun];
+    auto fetch_head = [&](int64_t run) {
+#pragma unroll
+        for (int r = 0; r < kHybRun; ++r) {
+            const int64_t doc = run * kHybRun + r;
+            const bool in = run < n_runs && doc < n_docs;
+            dn_next[r] = in ? d_nnz[doc] : -1;
+            ds_next[r] = in ? d_start[doc] : 0;
+        }
+    };
+    int64_t run = (int64_t)blockIdx.x * kHybWaves + wave;
+    fetch_head(run);
+    for (; run < n_runs; run += n_waves) {   // (wave-uniform)
+        const int doc0 = (int)(run * kHybRun);
+        int dn[kHybRun];
+        int64_t ds[kHybRun];
+        int32_t dt[kHybRun][kHybRegs];
+        float dw[kHybRun][kHybRegs];
+        f32x2 dd[kHybRun][DC];
+#pragma unroll
+        for (int r = 0; r < kHybRun; ++r) {
+            // (< 0: a tombstone, or behind the last document -- neither is read; the same value in every lane)
+            dn[r] = __builtin_amdgcn_readfirstlane(min(dn_next[r], kMaxDocNnz));
+            ds[r] = ds_next[r];
+#pragma unroll
+            for (int e = 0; e < kHybRegs; ++e) {
+                dt[r][e] = 0;
+                dw[r][e] = 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < DC; ++c) dd[r][c] = f32x2{0.f, 0.f};
+            if (dn[r] >= 0) {   // (wave-uniform)
+                const int doc = doc0 + r;
+#pragma unroll
+                for (int c = 0; c < DC; ++c)
+                    if (c < chunks) dd[r][c] = load_pair<false>(d_dense, (size_t)doc * dim + 128 * c + 2 * lane);
+#pragma unroll
+                for (int e = 0; e < kHybRegs; ++e) {
+                    if (lane + 64 * e < dn[r]) {
+                        dt[r][e] = d_terms[ds[r] + lane + 64 * e];
+                        dw[r][e] = d_weights[ds[r] + lane + 64 * e];
+                    }
+                }
+            }
+        }
+        fetch_head(run + n_waves);
+        float my_lex = 0.f, my_dense = 0.f;
+        bool my_live = false;
+#pragma unroll
+        for (int r = 0; r < kHybRun; ++r) {
+            if (dn[r] < 0) continue;   // (wave-uniform)
+            if (my_r == r) my_live = true;
+            const int n_e = min((dn[r] + 63) >> 6, kHybRegs);   // register entries per lane this document uses (wave-uniform)
+            for (int q = 0; q < n_q; ++q) {
+                const int nq = __builtin_amdgcn_readfirstlane(qn[q]);
+                const int32_t* qtq = qt + q * QCAP;
+                const float* qwq = qw + q * QCAP;
+                // lexical_score_kernel's bisection for each of the lane's register entries, the n_e of them side by side: a range of
+                // nq halves to nothing in floor(log2 nq) + 1 steps, and a finished one stands still
+                int lo[kHybRegs], hi[kHybRegs];
+#pragma unroll
+                for (int e = 0; e < kHybRegs; ++e) {
+                    lo[e] = 0;
+                    hi[e] = lane + 64 * e < dn[r] ? nq : 0;
+                }
+                for (int s = nq; s > 0; s >>= 1) {
+#pragma unroll
+                    for (int e = 0; e < kHybRegs; ++e) {
+                        if (e < n_e) {
+                            const bool on = lo[e] < hi[e];
+                            const int mid = (lo[e] + hi[e]) >> 1;
+                            const bool less = qtq[on ? mid : 0] < dt[r][e];
+                            lo[e] = on && less ? mid + 1 : lo[e];
+                            hi[e] = on && !less ? mid : hi[e];
+                        }
+                    }
+                }
+                float acc = 0.f;
+#pragma unroll
+                for (int e = 0; e < kHybRegs; ++e) {   // (entries lane, lane + 64, ... in that order)
+                    if (e < n_e) {
+                        const bool in = lane + 64 * e < dn[r] && lo[e] < nq;
+                        const int at = in ? lo[e] : 0;
+                        if (in && qtq[at] == dt[r][e]) acc = fmaf(qwq[at], dw[r][e], acc);
+                    }
+                }
+                for (int j = lane + 64 * kHybRegs; j < dn[r]; j += 64) acc = hybrid_match(qtq, qwq, nq, d_terms[ds[r] + j], d_weights + ds[r] + j, acc);
+                const float lex = wave_sum(acc);
+                const uint32_t* qdq = qd + q * DC * 64 + lane;
+                float dacc = 0.f;
+#pragma unroll
+                for (int c = 0; c < DC; ++c) {
+                    if (c < chunks) {
+                        const uint32_t u = qdq[64 * c];
+                        dacc = fmaf(elo(u), dd[r][c].x, dacc);
+                        dacc = fmaf(ehi(u), dd[r][c].y, dacc);
+                    }
+                }
+                const float dense = wave_sum(dacc);
+                if (lane == kHybRun * q + r) {
+                    my_lex = lex;
+                    my_dense = dense;
+                }
+            }
+        }
+        if (my_q < n_q && doc0 + my_r < n_docs)
+            ws[(size_t)my_q * stride + doc0 + my_r] = my_live ? hybrid_mix(w_dense, my_dense, w_lex, my_lex) : __builtin_nanf("");
     }
 }
 
@@ -399,6 +594,88 @@ int tt_lexical_scan_topk(const int32_t* q_terms, const float* q_weights, const i
     rc = score_launch(q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, nullptr, nullptr, 0, (int)n_docs,
                       (int)n_docs, stride, nullptr, nullptr, 0, 0.f, 0.f, __builtin_nanf(""), dense, nullptr, nullptr, st);
     if (rc) return rc;
+    SelectParams se{};
+    se.scores = dense;
+    se.idx = nullptr;
+    se.stride = stride;
+    se.cnt = nullptr;
+    se.m_fixed = (int)n_docs;
+    se.cap = INT_MAX;
+    se.idx_base = 0;
+    se.k = k;
+    se.out_scores = out_scores;
+    se.out_idx = out_idx;
+    se.out_stride = k;
+    return tt_select_launch(se, n_q, st);
+}
+
+size_t tt_hybrid_scan_workspace_bytes(int64_t n_docs, int n_q) { return tt_lexical_scan_workspace_bytes(n_docs, n_q); }
+
+int tt_hybrid_scan_topk(const int32_t* q_terms, const float* q_weights, const int32_t* q_start, const int32_t* q_nnz, int n_q,
+                        int max_q_nnz_host, const int32_t* d_terms, const float* d_weights, const int64_t* d_start,
+                        const int32_t* d_nnz, int64_t n_docs, const void* q_dense, const void* d_dense, int dim, float w_dense,
+                        float w_lex, int k, float* out_scores, int32_t* out_idx, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    const char* name = "tt_hybrid_scan_topk";
+    if (dim <= 0 || dim % 128 || dim > kMaxH) {
+        tt_set_error("%s: dim=%d must be a multiple of 128 and <= %d", name, dim, kMaxH);
+        return TT_E_UNSUPPORTED;
+    }
+    if (n_q < 1 || n_q > 64 || k < 1 || k > 1024 || max_q_nnz_host < 0 || max_q_nnz_host > kMaxQueryNnz) {
+        tt_set_error("%s: n_q=%d (1 .. 64), k=%d (1 .. 1024), max_q_nnz=%d (0 .. %d)", name, n_q, k, max_q_nnz_host, kMaxQueryNnz);
+        return TT_E_UNSUPPORTED;
+    }
+    TT_CHECK_ARG(n_docs >= 0 && n_docs <= INT_MAX, "%s: n_docs=%lld", name, (long long)n_docs);
+    TT_CHECK_ARG(out_scores && out_idx, "%s: null output", name);
+    TT_CHECK_ARG(w_dense >= 0.f && w_lex >= 0.f && w_dense + w_lex > 0.f, "%s: w_dense=%g w_lex=%g (both >= 0, not both 0)", name,
+                 (double)w_dense, (double)w_lex);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_docs == 0) {   // (an empty store's arrays may be null)
+        const int64_t n = (int64_t)n_q * k;
+        hipLaunchKernelGGL(lexical_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out_scores, out_idx, n);
+        TT_CHECK_LAUNCH();
+        return TT_OK;
+    }
+    TT_CHECK_ARG(q_dense && d_dense, "%s: null dense vectors", name);
+    int rc = check_score_args(name, q_terms, q_weights, q_start, q_nnz, n_q, d_terms, d_weights, d_start, d_nnz, q_dense, d_dense,
+                              dim, w_dense, w_lex);
+    if (rc) return rc;
+    const size_t need = tt_hybrid_scan_workspace_bytes(n_docs, n_q);
+    if (!workspace || workspace_bytes < need) {
+        tt_set_error("%s: workspace %zu < required %zu bytes", name, workspace_bytes, need);
+        return TT_E_WORKSPACE;
+    }
+    const int cus = tt_cu_count_cached();
+    TT_CHECK_ARG(cus > 0, "%s: no device", name);
+    const int64_t stride = (n_docs + 31) / 32 * 32;
+    float* dense = (float*)workspace;
+    // a persistent grid: kHybWgPerCu workgroups per compute unit, never more than there are runs for their waves
+    const int64_t runs = (n_docs + kHybRun - 1) / kHybRun;
+    const int grid = (int)std::min<int64_t>((int64_t)cus * kHybWgPerCu, (runs + kHybWaves - 1) / kHybWaves);
+    const bool shrt = max_q_nnz_host <= kHybShort;
+    const int per_pass = shrt ? HybPass<kHybShort>::queries : HybPass<kMaxQueryNnz>::queries;
+    const uint16_t* qd = (const uint16_t*)q_dense;
+    {
+        TtProfScope prof(TT_K_ROWOPS, st);
+        // one sweep of the store per pass, into the pass's own workspace rows: a score does not know which pass it is in
+        for (int q_lo = 0; q_lo < n_q; q_lo += per_pass) {
+            const int n_pass = std::min(per_pass, n_q - q_lo);
+#define TT_HYBRID_SCAN(DC, QCAP)                                                                                                   \
+    hipLaunchKernelGGL((hybrid_scan_kernel<DC, QCAP>), dim3(grid), dim3(64 * kHybWaves), 0, st, q_terms, q_weights, q_start + q_lo,    \
+                       q_nnz + q_lo, n_pass, d_terms, d_weights, d_start, d_nnz, (int)n_docs, qd + (size_t)q_lo * dim,               \
+                       (const uint16_t*)d_dense, dim, w_dense, w_lex, dense + (size_t)q_lo * stride, stride)
+            if (dim <= 256) {
+                if (shrt) TT_HYBRID_SCAN(2, kHybShort); else TT_HYBRID_SCAN(2, kMaxQueryNnz);
+            } else if (dim <= 512) {
+                if (shrt) TT_HYBRID_SCAN(4, kHybShort); else TT_HYBRID_SCAN(4, kMaxQueryNnz);
+            } else {
+                if (shrt) TT_HYBRID_SCAN(8, kHybShort); else TT_HYBRID_SCAN(8, kMaxQueryNnz);
+            }
+#undef TT_HYBRID_SCAN
+            TT_CHECK_LAUNCH();
+        }
+    }
+    // the lexical scan's selection: a tombstone's slot holds NaN, which the selection's key rejects
     SelectParams se{};
     se.scores = dense;
     se.idx = nullptr;

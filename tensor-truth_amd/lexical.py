@@ -248,6 +248,62 @@ def lexical_scan_topk(q_terms: torch.Tensor, q_weights: torch.Tensor, q_start, q
     return scores, idx
 
 
+def hybrid_scan_topk(q_terms: torch.Tensor, q_weights: torch.Tensor, q_start, q_nnz, d_terms: torch.Tensor, d_weights: torch.Tensor,
+                     d_start, d_nnz, q_dense: torch.Tensor, d_dense: torch.Tensor, hybrid_weights: Tuple[float, float], k: int,
+                     workspace: Optional[torch.Tensor] = None, max_q_nnz: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``tt_hybrid_scan_topk`` -> (scores fp32 [n_q][k], document numbers int32 [n_q][k]) on the device: the exact top-k by the
+    hybrid score ``(w_dense * <q, d> + w_lex * lex(q, d)) / (w_dense + w_lex)`` over every entry of the document arrays, each
+    score ``lexical_score``'s hybrid bits for the pair; ordered by (score descending, document number ascending), padded with
+    (-inf, -1); tombstones (``d_nnz`` -1) are never returned.  1 .. 64 queries, k 1 .. 1024; the arrays and the dense vectors
+    (contiguous bfloat16 ``q_dense`` [n_q][dim], ``d_dense`` [n_docs][dim]) are checked as ``lexical_score``'s.  ``max_q_nnz``: the
+    longest query entry, which sizes the kernel's LDS slots -- taken from a host ``q_nnz``; with a device ``q_nnz`` it is the
+    caller's promise (default 512, the widest slot).  After the call ``workspace`` (caller-owned, optional) holds every score:
+    row q, ``n_docs`` rounded up to 32 floats apart."""
+    n_q, n_docs = len(q_nnz), len(d_nnz)
+    if not 1 <= n_q <= MAX_SCAN_QUERIES:
+        raise ValueError(f"hybrid_scan_topk: {n_q} queries (1 .. {MAX_SCAN_QUERIES})")
+    if not 1 <= int(k) <= MAX_SCAN_K:
+        raise ValueError(f"hybrid_scan_topk: k={k} (1 .. {MAX_SCAN_K})")
+    _check_entries("q", q_terms, q_weights, q_start, q_nnz, 0, MAX_QUERY_NNZ)
+    _check_entries("d", d_terms, d_weights, d_start, d_nnz, -1, MAX_DOC_NNZ)
+    if not isinstance(q_nnz, torch.Tensor):
+        max_q_nnz = int(np.max(q_nnz)) if max_q_nnz is None else max(int(max_q_nnz), int(np.max(q_nnz)))
+    elif max_q_nnz is None:
+        max_q_nnz = MAX_QUERY_NNZ
+    if not 0 <= int(max_q_nnz) <= MAX_QUERY_NNZ:
+        raise ValueError(f"hybrid_scan_topk: max_q_nnz={max_q_nnz} (0 .. {MAX_QUERY_NNZ})")
+    wd, wl = check_hybrid_weights({"hybrid_weights": hybrid_weights})
+    if q_dense is None or d_dense is None or q_dense.dtype != torch.bfloat16 or d_dense.dtype != torch.bfloat16 \
+            or q_dense.dim() != 2 or d_dense.dim() != 2 or q_dense.shape[1] != d_dense.shape[1] \
+            or not (q_dense.is_contiguous() and d_dense.is_contiguous()):
+        raise ValueError("hybrid_scan_topk: dense vectors must be contiguous bfloat16 [*, dim]")
+    dim = int(q_dense.shape[1])
+    if dim <= 0 or dim % 128 or dim > MAX_HIDDEN:
+        raise NotImplementedError(f"hybrid_scan_topk: dim={dim}: a multiple of 128 up to {MAX_HIDDEN}")
+    if q_dense.shape[0] < n_q or d_dense.shape[0] < n_docs:
+        raise ValueError(f"hybrid_scan_topk: {q_dense.shape[0]} / {d_dense.shape[0]} dense rows for {n_q} queries / {n_docs} documents")
+    dev = _need_device("hybrid_scan_topk", q_terms, q_weights, d_terms, d_weights, q_dense, d_dense)
+    qs, qn = _dev_i(q_start, torch.int32, dev), _dev_i(q_nnz, torch.int32, dev)
+    ds, dn = _dev_i(d_start, torch.int64, dev), _dev_i(d_nnz, torch.int32, dev)
+    if q_terms.numel() == 0:      # (queries without a kept token still have a dense score; the entry point takes no null array)
+        q_terms, q_weights = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
+    if d_terms.numel() == 0 and n_docs:
+        d_terms, d_weights = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
+    lib = _lib.load_library()
+    need = int(lib.tt_hybrid_scan_workspace_bytes(n_docs, n_q))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    scores = torch.empty((n_q, int(k)), dtype=torch.float32, device=dev)
+    idx = torch.empty((n_q, int(k)), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.tt_hybrid_scan_topk(q_terms.data_ptr(), q_weights.data_ptr(), qs.data_ptr(), qn.data_ptr(), n_q, int(max_q_nnz),
+                                     d_terms.data_ptr(), d_weights.data_ptr(), ds.data_ptr(), dn.data_ptr(), n_docs,
+                                     q_dense.data_ptr(), d_dense.data_ptr(), dim, wd, wl, int(k), scores.data_ptr(), idx.data_ptr(),
+                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream(dev))
+    _lib.check(rc, "tt_hybrid_scan_topk")
+    return scores, idx
+
+
 # ---- encoder ------------------------------------------------------------------------------------------------------------------------
 @dataclass
 class LexicalWeights:
@@ -541,6 +597,30 @@ class LexicalStore:
         return lexical_scan_topk(lexical.terms, lexical.weights, self._check_query(lexical), lexical.nnz, self.terms, self.weights,
                                  self.d_start[: self.n_docs], self.d_nnz[: self.n_docs], k, workspace=self._ws)
 
+    def search_hybrid(self, lexical: LexicalWeights, dense: torch.Tensor, k: int,
+                      hybrid_weights: Tuple[float, float]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The exact top-k by the hybrid score ``(w_dense * <q, d> + w_lex * lex(q, d)) / (w_dense + w_lex)`` over every stored
+        document -> (scores fp32 [n_q][k], document numbers int32 [n_q][k]) on the device, ordered by (score descending, document
+        number ascending), padded with (-inf, -1); each score is ``score``'s hybrid bits for the pair.  ``dense``: the queries'
+        fp32 or bf16 [n_q][dim] vectors.  Removed documents are never returned.  This is ALWAYS the full scan
+        (``tt_hybrid_scan_topk``: one read of the store per pass of queries), also when posting lists are sealed: a passage that
+        shares no id with the query still has a dense score, so the lists cannot bound the result.  A store without dense rows
+        (``dim`` 0) has no hybrid score."""
+        if not self.dim:
+            raise ValueError(f"search_hybrid: {type(self).__name__} holds no dense rows (dim=0): there is no hybrid score")
+        if dense is None or dense.dim() != 2 or tuple(dense.shape) != (len(lexical), self.dim):
+            raise ValueError(f"search_hybrid: dense {None if dense is None else tuple(dense.shape)} does not match "
+                             f"[{len(lexical)}][{self.dim}]")
+        qs = self._check_query(lexical)
+        qd = dense.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        n_q = len(lexical)
+        need = int(_lib.load_library().tt_hybrid_scan_workspace_bytes(self.n_docs, n_q)) if 1 <= n_q <= MAX_SCAN_QUERIES else 0
+        if self._ws is None or self._ws.numel() < need:      # (the scratch `search` caches: either call leaves nothing in it to keep)
+            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return hybrid_scan_topk(lexical.terms, lexical.weights, qs, lexical.nnz, self.terms, self.weights,
+                                self.d_start[: self.n_docs], self.d_nnz[: self.n_docs], qd, self.dense, hybrid_weights, k,
+                                workspace=self._ws)
+
 
 # ---- postprocessor and retriever ---------------------------------------------------------------------------------------------------
 class _M3Model:
@@ -644,3 +724,30 @@ class HipLexicalRetriever:
         rr = self.reranker
         _, lw = rr.encoder.encode([query_bundle.query_str], is_query=True)
         return top_nodes(rr.store, lw, self.similarity_top_k, rr.nodes, node_type)
+
+
+class HipM3HybridRetriever:
+    """Exact retrieval by BGE-M3's hybrid ("dense+sparse") score over the nodes a ``HipM3HybridRerank`` indexed:
+    ``retrieve(query)`` encodes the query (one short forward gives both heads), runs ``LexicalStore.search_hybrid`` with the
+    reranker's own ``hybrid_weights`` and returns the best ``similarity_top_k`` stored nodes, best first, each with the score
+    ``postprocess_nodes`` gives it.  A hybrid score has no "no shared token" point, so every hit is kept -- except with
+    ``w_dense == 0``, where the score is the lexical one and the result is ``HipLexicalRetriever``'s (scores <= 0 dropped)."""
+
+    def __init__(self, reranker: HipM3HybridRerank, similarity_top_k: int = 10):
+        if not 1 <= int(similarity_top_k) <= MAX_SCAN_K:
+            raise ValueError(f"similarity_top_k={similarity_top_k} (1 .. {MAX_SCAN_K})")
+        self.reranker, self.similarity_top_k = reranker, int(similarity_top_k)
+
+    def retrieve(self, query):
+        from .schema import NodeWithScore, as_query_bundle
+
+        return self._retrieve(as_query_bundle(query), NodeWithScore)
+
+    def _retrieve(self, query_bundle, node_type=None):
+        if node_type is None:
+            from .schema import NodeWithScore as node_type
+        rr = self.reranker
+        w_dense, w_lex = rr.hybrid_weights
+        dense, lw = rr.encoder.encode([query_bundle.query_str], is_query=True)
+        return top_nodes(rr.store, lw, self.similarity_top_k, rr.nodes, node_type, positive_only=w_dense == 0,
+                         search=lambda q, k: rr.store.search_hybrid(q, dense, k, (w_dense, w_lex)))

@@ -3,6 +3,7 @@
 
     python tools/lexical_bench.py [--repeat 20] [--dtype bfloat16] [--scan-docs 1000000] [--out profiles/lexical_bench.jsonl]
     python tools/lexical_bench.py --postings-only [--out profiles/lexical_postings_bench.jsonl]
+    python tools/lexical_bench.py --hybrid [--out profiles/hybrid_scan_bench.log]
 
 One JSON line per leg, appended to ``--out``:
   lone_caller_stored   one query against 50 candidates that sit in the ``LexicalStore``: query encode + ``tt_lexical_score`` (lexical,
@@ -27,8 +28,14 @@ One JSON line per leg, appended to ``--out``:
                        where every id has a list.  The leg records the profile it met (list length
                        by decile of the id range, the share of ids without a list, the query ids that had one).  Real
                        vocabularies have stopword-like ids whose lists are far longer than any here
+  hybrid_scan          (``--hybrid`` only) ``tt_hybrid_scan_topk`` (k = 50) over the same ``--scan-docs`` arrays
+                       plus one unit bf16 row of 1024 per document, for 1, 4, 16 and 64 queries of 8 ids, against
+                       ``tt_lexical_score`` over the whole store with the dense arguments followed by ``torch.topk``: median, minimum
+                       and maximum of ``--repeat`` event pairs each, bytes per sweep (n_docs * (12 + 2048) + nnz * 8) over the
+                       scan's time against 8 TB/s, and whether the two top-50 are equal
 with the shader clock sampled (amdsmi, read only) while the windows ran.  ``--postings-only`` runs the last leg alone (no model is
-built) and writes to ``profiles/lexical_postings_bench.jsonl`` unless ``--out`` says otherwise.
+built) and writes to ``profiles/lexical_postings_bench.jsonl`` unless ``--out`` says otherwise; ``--hybrid`` likewise runs the
+hybrid leg alone and writes to ``profiles/hybrid_scan_bench.log``.
 """
 import argparse
 import json
@@ -48,6 +55,7 @@ def main():
     ap.add_argument("--dtype", default="bfloat16", choices=("bfloat16", "float16"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--postings-only", action="store_true")
+    ap.add_argument("--hybrid", action="store_true")
     args = ap.parse_args()
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.dirname(here))
@@ -64,6 +72,7 @@ def main():
     from tensor_truth_amd.schema import NodeWithScore, TextNode
 
     out_path = args.out or os.path.join(os.path.dirname(here), "profiles",
+                                        "hybrid_scan_bench.log" if args.hybrid else
                                         "lexical_postings_bench.jsonl" if args.postings_only else "lexical_bench.jsonl")
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(5)
@@ -161,6 +170,69 @@ def main():
                  warmup=args.warmup)
             del ws
 
+    def hybrid_leg():
+        """the hybrid scan against what the library could do before it -- ``tt_lexical_score`` over the whole
+        store with the dense arguments, then ``torch.topk`` -- on the corpus above plus one unit bf16 row of 1024 per document."""
+        n_docs, dim, k, hw = args.scan_docs, 1024, 50, (0.4, 0.2)
+        gd = torch.Generator(device=dev).manual_seed(3)
+        d_terms, d_weights, d_start, nnz, total = scan_corpus(n_docs, gd)
+        d_dense = torch.empty((n_docs, dim), dtype=torch.bfloat16, device=dev)
+        for lo in range(0, n_docs, 1 << 17):      # (in pieces: the fp32 image of the whole corpus is never held)
+            n = min(1 << 17, n_docs - lo)
+            d_dense[lo:lo + n] = torch.nn.functional.normalize(torch.randn(n, dim, generator=gd, device=dev), dim=-1).to(torch.bfloat16)
+        nbytes = n_docs * (12 + 2 * dim) + total * 8
+
+        def spread(fn):
+            for _ in range(args.warmup):
+                fn()
+            torch.cuda.synchronize()
+            ev = []
+            for _ in range(args.repeat):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ev.append(a.elapsed_time(b))
+            return statistics.median(ev), min(ev), max(ev)
+
+        for n_q in (1, 4, 16, 64):
+            q_terms = torch.sort(torch.randint(4, 250002, (n_q, 8), generator=gd, device=dev, dtype=torch.int32), dim=1).values.reshape(-1)
+            q_terms = q_terms.contiguous()
+            q_weights = torch.rand(n_q * 8, generator=gd, device=dev) + 0.5
+            q_dense = torch.nn.functional.normalize(torch.randn(n_q, dim, generator=gd, device=dev), dim=-1).to(torch.bfloat16)
+            qs, qn = np.arange(n_q, dtype=np.int32) * 8, np.full(n_q, 8, dtype=np.int32)
+            qs_t, qn_t = torch.from_numpy(qs).to(dev), torch.from_numpy(qn).to(dev)
+            ws = torch.empty(int(_lib.load_library().tt_hybrid_scan_workspace_bytes(n_docs, n_q)), dtype=torch.uint8, device=dev)
+            scan = lambda: lexical.hybrid_scan_topk(q_terms, q_weights, qs_t, qn_t, d_terms, d_weights, d_start, nnz, q_dense, d_dense,  # noqa: E731
+                                                    hw, k, workspace=ws, max_q_nnz=8)
+            base = lambda: torch.topk(lexical.lexical_score(q_terms, q_weights, qs_t, qn_t, d_terms, d_weights, d_start, nnz,  # noqa: E731
+                                                            q_dense=q_dense, d_dense=d_dense, hybrid_weights=hw)[2], k, dim=1)
+            got, want = scan(), base()
+            same_scores = bool(torch.equal(got[0].view(torch.int32), want[0].view(torch.int32)))
+            same_docs = bool(torch.equal(got[1].to(torch.int64), want[1]))
+            clock = _clock_sampler()
+            s_med, s_min, s_max = spread(scan)
+            b_med, b_min, b_max = spread(base)
+            # what the selection costs at this size: the lexical scan of the same queries (scoring + the same selection) less its
+            # scoring kernel alone -- an estimate by subtraction, not a timing of the selection itself
+            lws = torch.empty(int(_lib.load_library().tt_lexical_scan_workspace_bytes(n_docs, n_q)), dtype=torch.uint8, device=dev)
+            ls_med, _, _ = spread(lambda: lexical.lexical_scan_topk(q_terms, q_weights, qs_t, qn_t, d_terms, d_weights, d_start, nnz, k,
+                                                                    workspace=lws))
+            lk_med, _, _ = spread(lambda: lexical.lexical_score(q_terms, q_weights, qs_t, qn_t, d_terms, d_weights, d_start, nnz))
+            del lws
+            emit(leg="hybrid_scan", selection_ms_by_subtraction=round(ls_med - lk_med, 4),
+                 scoring_ms_by_subtraction=round(s_med - (ls_med - lk_med), 4), n_docs=n_docs, nnz=total, dim=dim, k=k, queries=n_q, query_ids=8, bytes_per_sweep=nbytes,
+                 scan_ms=round(s_med, 4), scan_min_ms=round(s_min, 4), scan_max_ms=round(s_max, 4),
+                 baseline_ms=round(b_med, 4), baseline_min_ms=round(b_min, 4), baseline_max_ms=round(b_max, 4),
+                 sweep_fraction_of_8_tb_per_s=round(nbytes / s_med / 1e9 / 8.0, 4), baseline_over_scan=round(b_med / s_med, 3),
+                 same_top_k_scores=same_scores, same_top_k_documents=same_docs, sclk_mhz=clock(), repeat=args.repeat,
+                 warmup=args.warmup)
+            del ws
+
+    if args.hybrid:
+        hybrid_leg()
+        return
     if args.postings_only:
         postings_leg()
         return
