@@ -114,6 +114,44 @@ int tt_scan_topk_shadow(const void* corpus_bf16, const void* shadow, int64_t cap
                         float* out_scores, int32_t* out_idx,
                         void* workspace, size_t workspace_bytes, int32_t* status_flag, void* stream);
 
+/* ---- MMR: diversified top-k over the scan's hits (csrc/mmr.hip) -----------------
+ * Replaces the vector store's query mode "mmr" (index.as_retriever(vector_store_query_mode="mmr", ...): maximal marginal
+ * relevance, Carbonell & Goldstein 1998) for the dense path: of the P best rows of a scan, pick k one at a time, each the
+ * candidate that is most relevant AND least similar to what has been picked.
+ *
+ * tt_mmr_select: cand / rel are [n_queries][n_cand] (1 <= n_cand <= 1024), tt_scan_topk's out_idx / out_scores untouched: list
+ *   entries in the scan's order (score descending, row ascending), corpus row = entry - idx_base, entries < 0 are padding, and an
+ *   entry whose row falls outside [0, n_rows) is treated as padding too -- no row outside the matrix is read.
+ *   Similarity: G[i][j] = the fp32 dot product of the bf16 corpus rows of list positions i and j: ONE mfma_f32_16x16x32_bf16 chain
+ *   over kk = 0 .. dim/32 - 1 from a zero accumulator (the scan's and tt_maxsim's convention: unit rows, so the dot product is the
+ *   cosine; nothing is renormalised).  An entry depends on its two corpus rows alone -- not on the list positions, on n_cand, on
+ *   the other queries of the call or on the wave that computed it -- and G[i][j] and G[j][i] are one value written twice.
+ *   Selection, fp32, every product and difference rounded once (no fused multiply-add), oml = 1.0f - lambda:
+ *     step 0:     v[d] = lambda * rel[d]
+ *     step s > 0: v[d] = (lambda * rel[d]) - (oml * pen[d])
+ *     the pick p = the not yet picked, non-padding position with the largest v; ties (-0 == +0 is one) go to the LOWER position;
+ *       a candidate whose v is NaN is never picked;
+ *     penalty 0 (the maximum over everything picked, the default of the Python surface): pen[d] = G[p][d] after the first pick,
+ *       fmaxf(pen[d], G[p][d]) after every later one -- fmaxf keeps a finite pen when G is NaN (a row tombstoned after the scan);
+ *     penalty 1 (the last pick only): pen[d] = G[p][d] after every pick.
+ *   Outputs, each [n_queries][k] in selection order (1 <= k <= n_cand): out_mmr the v the pick won with, out_rel its rel, out_idx
+ *   its entry of cand, out_pos its list position.  When nothing can be picked the remaining outputs are (-inf, -inf, -1, -1).
+ *   Workspace (tt_mmr_workspace_bytes, 16-byte aligned): n_queries matrices of Ppad x Ppad floats, Ppad = n_cand rounded up to
+ *   16, row-major: G of query q, positions i, j is ((float*)workspace)[(q * Ppad + i) * Ppad + j].  After the call it holds every
+ *   entry of non-padding pairs (an entry with a padding position holds +0; nothing is written for n_rows == 0).
+ *   Two launches: the Gram tiles (one wave per 16 x 16 block pair on or above the diagonal, operands gathered straight from the
+ *   matrix, 16 contiguous bytes of one row per lane and kk), then one workgroup per query whose threads keep lambda * rel, pen
+ *   and the taken flags of up to four candidates each in registers and read one row of G per step.
+ *   Refused before a launch: dim not a multiple of 128 up to 1024, n_cand outside 1 .. 1024, k outside 1 .. n_cand, penalty not
+ *   0 or 1 (TT_E_UNSUPPORTED); lambda NaN or outside [0, 1], n_queries < 0, n_rows < 0, a null array (TT_E_INVALID); a workspace
+ *   that is NULL, misaligned or too small (TT_E_WORKSPACE for the size).  n_queries == 0 returns 0 and writes nothing. */
+size_t tt_mmr_workspace_bytes(int n_queries, int n_cand);
+int tt_mmr_select(const void* corpus_bf16, int64_t n_rows, int dim,
+                  const int32_t* cand, const float* rel, int n_queries, int n_cand, int k,
+                  float lambda, int penalty, int32_t idx_base,
+                  float* out_mmr, float* out_rel, int32_t* out_idx, int32_t* out_pos,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- metadata-filtered exact search ----------------------------------------
  * Replaces the `where=` metadata filter of the reference's vector-store query
  * (src/tensortruth/rag_engine.py:286-365 builds it; index.as_retriever(filters=...)).

@@ -82,6 +82,10 @@ SIGNATURES = {
     "tt_scan_shadow_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "tt_scan_topk_shadow": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int32, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p, c_void_p]),
+    # MMR over the scan's hits (csrc/mmr.hip)
+    "tt_mmr_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "tt_mmr_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int32,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tt_filter_rows_workspace_bytes": (c_size_t, [c_int64]),
     "tt_filter_rows": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),

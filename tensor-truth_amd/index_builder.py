@@ -288,5 +288,7 @@ class HipDocumentIndex:
             self._persist()
         return True
 
-    def as_retriever(self, similarity_top_k: int = 10):
-        return self.index.as_retriever(similarity_top_k=similarity_top_k)
+    def as_retriever(self, similarity_top_k: int = 10, vector_store_query_mode=None, vector_store_kwargs=None):
+        """``vector_store_query_mode="mmr"`` and its ``vector_store_kwargs`` go through to ``HipVectorIndex.as_retriever``."""
+        return self.index.as_retriever(similarity_top_k=similarity_top_k, vector_store_query_mode=vector_store_query_mode,
+                                       vector_store_kwargs=vector_store_kwargs)

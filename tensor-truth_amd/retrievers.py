@@ -128,6 +128,9 @@ class MultiIndexRetriever:
         bases = [getattr(r, "_vector_retriever", r) for r in self.retrievers]
         if not all(isinstance(b, HipVectorRetriever) for b in bases) or len(bases) > 64:
             return None
+        # the packed scan answers plain top-k only: a retriever in MMR mode runs its own search (the thread pool path)
+        if any(getattr(b, "query_mode", "default") == "mmr" for b in bases):
+            return None
         indexes = [b.index for b in bases]
         if len({(ix.dim, ix.device) for ix in indexes}) != 1 or len({id(ix) for ix in indexes}) != len(indexes):
             return None

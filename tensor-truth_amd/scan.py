@@ -192,6 +192,62 @@ def scan_topk_host(corpus: torch.Tensor, queries: torch.Tensor, k: int, idx_base
     return host[: q * k].view(torch.float32).view(q, k), host[q * k: 2 * q * k].view(q, k)
 
 
+MMR_PENALTIES = {"max": 0, "last": 1}
+MMR_MAX_CANDIDATES = 1024
+_MMR_WS_CAP = 64 << 20          # mmr_select's Gram matrices per launch: queries go in chunks that stay at or below this
+
+
+def mmr_select(corpus: torch.Tensor, cand: torch.Tensor, rel: torch.Tensor, k: int, lam: float, penalty: str = "max",
+               idx_base: int = 0, _packed: Optional[torch.Tensor] = None):
+    """``tt_mmr_select``: maximal marginal relevance over candidate lists.  corpus [N,D] bf16; cand [Q,P] int32 and rel [Q,P] fp32
+    exactly as ``scan_topk`` returned them (same device; P <= 1024, entries < 0 are padding) ->
+    (mmr [Q,k] fp32, rel [Q,k] fp32, idx [Q,k] int32, pos [Q,k] int32) in selection order: the value each pick won with, its scan
+    score, its entry of ``cand`` and its position in the list; padding (-inf, -inf, -1, -1) when fewer than k can be picked.
+
+    ``lam`` in [0, 1] weighs relevance against the similarity penalty (1: plain top-k order).  ``penalty``: "max", the maximum
+    similarity to everything picked so far (Carbonell & Goldstein), or "last", the similarity to the most recent pick only.
+    Stream-ordered, no host sync; the pairwise similarities live in the thread-local workspace."""
+    lib = _lib.load_library()
+    _require_cuda(corpus, "corpus")
+    _require_cuda(cand, "cand")
+    _require_cuda(rel, "rel")
+    if corpus.dtype != torch.bfloat16 or cand.dtype != torch.int32 or rel.dtype != torch.float32:
+        raise TypeError("corpus must be torch.bfloat16, cand torch.int32 and rel torch.float32")
+    if corpus.dim() != 2 or cand.dim() != 2 or cand.shape != rel.shape:
+        raise ValueError(f"shape mismatch: corpus {tuple(corpus.shape)} cand {tuple(cand.shape)} rel {tuple(rel.shape)}")
+    if corpus.device != cand.device or corpus.device != rel.device:
+        raise ValueError("corpus, cand and rel must be on the same device")
+    if not corpus.is_contiguous() or not cand.is_contiguous() or not rel.is_contiguous():
+        raise ValueError("corpus, cand and rel must be contiguous row-major")
+    if penalty not in MMR_PENALTIES:
+        raise ValueError(f"penalty {penalty!r}: one of {sorted(MMR_PENALTIES)}")
+    n, d = corpus.shape
+    q, p = cand.shape
+    dev = corpus.device
+    if _packed is not None:      # search_mmr_host: the four outputs in one buffer
+        m = q * k
+        outs = (_packed[:m].view(torch.float32).view(q, k), _packed[m: 2 * m].view(torch.float32).view(q, k),
+                _packed[2 * m: 3 * m].view(q, k), _packed[3 * m: 4 * m].view(q, k))
+    else:
+        outs = (torch.empty((q, k), dtype=torch.float32, device=dev), torch.empty((q, k), dtype=torch.float32, device=dev),
+                torch.empty((q, k), dtype=torch.int32, device=dev), torch.empty((q, k), dtype=torch.int32, device=dev))
+    if q == 0:
+        return outs
+    per_query = int(lib.tt_mmr_workspace_bytes(1, p))
+    chunk = q if per_query == 0 else max(1, min(q, _MMR_WS_CAP // per_query))     # (per_query == 0: the call below refuses p)
+    with torch.cuda.device(dev):
+        st = _stream_ptr(dev)
+        ws = _ws.get(dev, chunk * per_query + 256)
+        base = (ws.data_ptr() + 255) // 256 * 256
+        for lo in range(0, q, chunk):
+            nq = min(chunk, q - lo)
+            rc = lib.tt_mmr_select(corpus.data_ptr(), n, d, cand[lo:].data_ptr(), rel[lo:].data_ptr(), nq, p, k, float(lam),
+                                   MMR_PENALTIES[penalty], idx_base, outs[0][lo:].data_ptr(), outs[1][lo:].data_ptr(),
+                                   outs[2][lo:].data_ptr(), outs[3][lo:].data_ptr(), base, ws.numel() - (base - ws.data_ptr()), st)
+            _lib.check(rc, "tt_mmr_select")
+    return outs
+
+
 def scan_topk_segmented(corpus: torch.Tensor, queries: torch.Tensor, k: int, seg_offsets) -> Tuple[torch.Tensor, torch.Tensor]:
     """Several index modules in one matrix: rows ``[seg_offsets[s], seg_offsets[s+1])`` are module ``s``.
     One pass over the matrix, then an exact top-k per (query, module) ->

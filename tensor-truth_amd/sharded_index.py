@@ -279,6 +279,9 @@ class ShardedHipVectorIndex:
         ``queries="replicated"`` keeps one collective round per call (the front end hands every rank the same request)."""
         if _kw.get("filters") is not None:
             raise NotImplementedError("metadata filters are not supported on a row-sharded index")
+        mode = _kw.get("vector_store_query_mode")
+        if str(getattr(mode, "value", mode)).lower() == "mmr":
+            raise NotImplementedError("vector_store_query_mode='mmr' is not supported on a row-sharded index")
         if self.leaf_ids is None or self.docstore is None:
             raise ValueError("this ShardedHipVectorIndex was built without node tables (search-only)")
         world, _ = _world(self.group)

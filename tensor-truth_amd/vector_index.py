@@ -318,15 +318,82 @@ class HipVectorIndex:
             return self._filtered(snap, self._unit_bf16(query_emb), k, filters, host=True)
         return _scan.scan_topk_host(mat, self._unit_bf16(query_emb), k, shadow=self._shadow_for(mat, query_emb.shape[0]))
 
+    # ---- MMR ---------------------------------------------------------------------------------------
+    def _mmr(self, query_emb: torch.Tensor, k: int, lam: float, prefetch_factor: float, penalty: str, snapshot, filters,
+             host: bool):
+        """``search_mmr`` / ``search_mmr_host``: the scan for the P best rows (the path ``search`` takes: shadow, filters, the same
+        bits), then ``scan.mmr_select`` over them on the same stream -- candidates, overflow flag and picks share ONE device
+        buffer, so nothing comes back to the host between the two and the flag arrives with the results."""
+        if not 0.0 <= float(lam) <= 1.0:            # (a NaN fails the comparison)
+            raise ValueError(f"lam={lam!r}: a weight in [0, 1]")
+        if not float(prefetch_factor) >= 1.0:
+            raise ValueError(f"prefetch_factor={prefetch_factor!r}: at least 1")
+        if penalty not in _scan.MMR_PENALTIES:
+            raise ValueError(f"penalty {penalty!r}: one of {sorted(_scan.MMR_PENALTIES)}")
+        if k < 1:
+            raise ValueError(f"k={k}: at least 1")
+        snap = snapshot if snapshot is not None else self.snapshot()
+        mat = snap[0]
+        q16 = self._unit_bf16(query_emb)
+        q = q16.shape[0]
+        p = min(int(mat.shape[0]), _scan.MMR_MAX_CANDIDATES, max(k, math.ceil(k * float(prefetch_factor))))
+        kk = min(k, p)
+        dev = torch.device("cpu") if host else self.device
+        out = (torch.full((q, k), float("-inf"), dtype=torch.float32, device=dev),
+               torch.full((q, k), -1, dtype=torch.int32, device=dev),
+               torch.full((q, k), float("-inf"), dtype=torch.float32, device=dev))
+        if q == 0 or kk < 1:
+            return out
+        n_c, m = q * p, q * kk
+        buf = torch.empty(2 * n_c + 1 + 4 * m, dtype=torch.int32, device=self.device)   # [scores | rows | flag | mmr rel idx pos]
+        if _mf.filter_key(filters) is not None:
+            cf = _mf.compile_filter(filters, lambda key: self._column(key, snap), mat.shape[0], self.device)
+            rows, offs = _scan.filter_rows(cf, mat.shape[0], self.device)
+            c_s, c_i = _scan.scan_topk_rows(mat, q16, p, rows, offs, cf.bound, _packed=buf[: 2 * n_c + 1])
+            exact = lambda: _scan.scan_topk_rows_exact(mat, q16, p, rows, offs)       # noqa: E731
+        else:
+            c_s, c_i = _scan.scan_topk(mat, q16, p, _packed=buf[: 2 * n_c + 1], shadow=self._shadow_for(mat, q))
+            exact = lambda: _scan.scan_topk(mat, q16, p, exact_dense=True)            # noqa: E731
+        _scan.mmr_select(mat, c_i, c_s, kk, lam, penalty, _packed=buf[2 * n_c + 1:])
+        tail = buf[2 * n_c:].cpu() if host else buf[2 * n_c:]                         # the one sync (current stream only)
+        if int(tail[0]) != 0:     # a candidate list of the scan overflowed: the dense exact path, and the selection again
+            c_s, c_i = exact()
+            _scan.mmr_select(mat, c_i.contiguous(), c_s.contiguous(), kk, lam, penalty, _packed=buf[2 * n_c + 1:])
+            tail = buf[2 * n_c:].cpu() if host else buf[2 * n_c:]
+        out[2][:, :kk] = tail[1: 1 + m].view(torch.float32).view(q, kk)
+        out[0][:, :kk] = tail[1 + m: 1 + 2 * m].view(torch.float32).view(q, kk)
+        out[1][:, :kk] = tail[1 + 2 * m: 1 + 3 * m].view(q, kk)
+        return out
+
+    def search_mmr(self, query_emb: torch.Tensor, k: int, lam: float = 0.5, prefetch_factor: float = 4.0, penalty: str = "max",
+                   snapshot=None, filters=None):
+        """Maximal marginal relevance: of the ``P = min(rows, 1024, max(k, ceil(k * prefetch_factor)))`` best rows by cosine
+        (``search``'s own candidates: fp8 shadow and ``filters`` included), pick ``k`` greedily by
+        ``lam * cosine - (1 - lam) * penalty`` (``scan.mmr_select``; ``penalty`` "max": the largest similarity to anything picked,
+        "last": to the most recent pick).  -> (scores [Q,k] fp32 cosine, rows [Q,k] int32, mmr [Q,k] fp32 the values the picks won
+        with), in SELECTION order -- not sorted by score -- padded with (-inf, -1, -inf).  ``lam = 1`` is ``search``."""
+        return self._mmr(query_emb, k, lam, prefetch_factor, penalty, snapshot, filters, host=False)
+
+    def search_mmr_host(self, query_emb: torch.Tensor, k: int, lam: float = 0.5, prefetch_factor: float = 4.0,
+                        penalty: str = "max", snapshot=None, filters=None):
+        """``search_mmr`` with the results on the host (CPU tensors): the picks and the scan's overflow flag come back in one
+        copy, the only host sync of the batch."""
+        return self._mmr(query_emb, k, lam, prefetch_factor, penalty, snapshot, filters, host=True)
+
     def node_score(self, cos: float) -> float:
         return math.exp(-(2.0 - 2.0 * cos)) if self.score_mode == "chroma" else cos
 
     def as_retriever(self, similarity_top_k: int = 10, coalesce: bool = True, max_batch: int = 64,
-                     max_wait_s: float = 0.0, filters=None, **_kw) -> "HipVectorRetriever":
+                     max_wait_s: float = 0.0, filters=None, vector_store_query_mode=None, vector_store_kwargs=None,
+                     **_kw) -> "HipVectorRetriever":
         """``filters``: a ``MetadataFilters`` (``metadata_filter.build_metadata_filters`` turns the reference's filter specs into
-        one) every search of the retriever applies."""
+        one) every search of the retriever applies.  ``vector_store_query_mode="mmr"`` with ``vector_store_kwargs`` (``mmr_threshold``,
+        ``mmr_prefetch_factor``, ``mmr_penalty``): maximal marginal relevance (``HipVectorRetriever``); None / "default": top-k."""
+        kw = dict(vector_store_kwargs or {})
         return HipVectorRetriever(self, similarity_top_k, coalesce=coalesce, max_batch=max_batch, max_wait_s=max_wait_s,
-                                  filters=filters)
+                                  filters=filters, query_mode=vector_store_query_mode,
+                                  mmr_threshold=kw.get("mmr_threshold"), mmr_prefetch_factor=kw.get("mmr_prefetch_factor"),
+                                  mmr_penalty=kw.get("mmr_penalty"))
 
     # ---- persistence ---------------------------------------------------------------------------------
     def persist(self, persist_dir: str, embedding_model: Optional[str] = None, chunk_sizes=None,
@@ -592,12 +659,33 @@ class HipVectorRetriever:
     ``coalesce`` (default on): concurrent ``retrieve`` calls are merged by a ``coalesce.Coalescer`` into ONE
     query-embedding batch and ONE scan (up to ``max_batch`` queries share a pass over the corpus); a lone caller
     runs immediately as a batch of one.  Results are identical to serial calls: embeddings and scan results do not
-    depend on the batch a query travels in (tests/test_coalesce_gpu.py)."""
+    depend on the batch a query travels in (tests/test_coalesce_gpu.py).
+
+    ``query_mode="mmr"`` (llama-index: ``vector_store_query_mode``): maximal marginal relevance, ``HipVectorIndex.search_mmr_host``
+    for the whole batch, with ``mmr_threshold`` (the relevance weight lambda, default 0.5; 1 is plain top-k), ``mmr_prefetch_factor``
+    (candidates per returned node, default 4) and ``mmr_penalty`` ("max": the largest similarity to anything already picked, the
+    Carbonell-Goldstein rule and the default; "last": the similarity to the most recent pick only, which is what llama-index's
+    ``get_top_k_mmr_embeddings`` does as far as recalled -- llama-index is not installed here, so that is unverified).  The nodes
+    come back in SELECTION order and each score is ``node_score(cosine)``, the node's relevance on the usual scale, not the MMR
+    value: the list is therefore NOT sorted by score, and a prefix of it is the MMR selection of that length."""
 
     def __init__(self, index: HipVectorIndex, similarity_top_k: int = 10, coalesce: bool = True, max_batch: int = 64,
-                 max_wait_s: float = 0.0, filters=None):
+                 max_wait_s: float = 0.0, filters=None, query_mode=None, mmr_threshold=None, mmr_prefetch_factor=None,
+                 mmr_penalty=None):
         self.index = index
         self.similarity_top_k = similarity_top_k
+        # llama-index's vector_store_query_mode: "mmr" is answered, None / "default" (and any other name, as before) is top-k
+        self.query_mode = "mmr" if str(getattr(query_mode, "value", query_mode)).lower() == "mmr" else "default"
+        self.mmr_threshold = 0.5 if mmr_threshold is None else float(mmr_threshold)
+        self.mmr_prefetch_factor = 4.0 if mmr_prefetch_factor is None else float(mmr_prefetch_factor)
+        self.mmr_penalty = "max" if mmr_penalty is None else mmr_penalty
+        if self.query_mode == "mmr":
+            if not 0.0 <= self.mmr_threshold <= 1.0:
+                raise ValueError(f"mmr_threshold={mmr_threshold!r}: a weight in [0, 1]")
+            if not self.mmr_prefetch_factor >= 1.0:
+                raise ValueError(f"mmr_prefetch_factor={mmr_prefetch_factor!r}: at least 1")
+            if self.mmr_penalty not in _scan.MMR_PENALTIES:
+                raise ValueError(f"mmr_penalty={mmr_penalty!r}: one of {sorted(_scan.MMR_PENALTIES)}")
         # metadata filters of every search (llama-index: a property of the retriever, so one coalesced batch shares one filter
         # and one row list); ValueError here for nested filters / unknown operators
         self.filters = filters
@@ -678,15 +766,22 @@ class HipVectorRetriever:
             return [[] for _ in bundles]
         stream = self._gpu_stream()
         fkw = {} if self.filter_key is None else {"filters": self.filters}
+        if self.query_mode == "mmr":       # the whole coalesced batch: one scan for the candidates, one selection
+            def search(qm):
+                return idx.search_mmr_host(qm, k, lam=self.mmr_threshold, prefetch_factor=self.mmr_prefetch_factor,
+                                           penalty=self.mmr_penalty, snapshot=snap, **fkw)[:2]
+        else:
+            def search(qm):
+                return idx.search_host(qm, k, snapshot=snap, **fkw)
         if stream is None:
-            scores, rows = idx.search_host(self._query_matrix(bundles), k, snapshot=snap, **fkw)
+            scores, rows = search(self._query_matrix(bundles))
             scores, rows = scores.tolist(), rows.tolist()
         else:
             written = getattr(idx, "_written", None)        # (read after the snapshot: covers every row the snapshot holds)
             with torch.cuda.stream(stream):
                 if written is not None:
                     stream.wait_event(written)
-                scores, rows = idx.search_host(self._query_matrix(bundles), k, snapshot=snap, **fkw)     # waits for THIS stream only
+                scores, rows = search(self._query_matrix(bundles))     # waits for THIS stream only
                 scores, rows = scores.tolist(), rows.tolist()
         return [self.nodes_from_hits(s, r, leaf_ids) for s, r in zip(scores, rows)]
 
