@@ -192,7 +192,13 @@ int tt_scan_topk_rows(const void* corpus_bf16, int64_t n_rows, int dim,
  * SURVEY.md section 8e; also MultiIndexRetriever's concatenate+sort,
  * rag_engine.py:463-507, when indexes live in one matrix).
  * in_scores/in_idx: [n_queries][n_lists * k_in] (per query, lists concatenated);
- * entries with idx < 0 are padding.  Output ordered by (score desc, idx asc). */
+ * entries with idx < 0 are padding.  Output ordered by (score desc, idx asc).
+ * The contract in full (tests/select_refs.py states it in numpy; every scan's final selection follows it too):
+ *   an entry is LIVE iff its score is not NaN and its idx is >= 0 -- (finite, idx < 0) never ranks, whatever its score, and
+ *   (-inf, idx >= 0) IS live: it ranks after every finite score and before the padding; (+inf, idx >= 0) ranks first;
+ *   -0 and +0 are one score (idx decides between them; the zero returned is +0);
+ *   the caller's idx column is taken as it is: duplicate (score, idx) pairs are all returned, next to each other;
+ *   the output is the first k_out live entries, then (-inf, -1); any n_candidates >= 0, rows of out_* are k_out apart. */
 int tt_topk_merge(const float* in_scores, const int32_t* in_idx,
                   int n_queries, int n_candidates, int k_out,
                   float* out_scores, int32_t* out_idx, void* stream);
